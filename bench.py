@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
-"""bench.py — MLUPS of the D2Q9-BGK timestep path on MI355X, with roofline and CPU baseline.
+"""bench.py — MLUPS of the D2Q9-BGK timestep path on MI355X; with --full also roofline, checks, variants and CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8192x8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 8192x8192] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run is the headline alone: set-up, W untimed warm-up steps, ONE timed region of exactly K steps, the
+line (`value`, `ms_per_step` = that region's time / K).  --dump-outputs DIR writes what that region computed.
+Everything below that goes beyond the headline (repeated regions, the profiled repetition, parity checks,
+variants, secondary decks, sustained line, power, CPU baseline) runs with --full only.
 
 `python bench.py --gpus N` with N > 1 and no rank environment starts the N rank processes itself (a child
 `python -m torch.distributed.run ... bench.py --gpus N ...`, before this process touches the GPU) and relays
@@ -18,7 +23,7 @@ a k-row halo exchange per k steps (direct peer-to-peer stores over xGMI, or RCCL
 reduction of the per-step sums at the end (d2q9-bgk.c:396).  The timed region is the reference's
 (d2q9-bgk.c:278-398): step loop + av_vels reduction, inputs resident in HBM, no file I/O.
 
-What one N > 1 invocation harvests (each part checked bit for bit against a single-GPU run of the same deck
+What one N > 1 invocation harvests with --full (each part checked bit for bit against a single-GPU run of the same deck
 on the rank's own device before it is timed, and again after):
   value / ms_per_step   the headline: loops tried in the order p2p, rccl, torch until one sets up on every
                         rank, completes the warm-up and passes the check (`exchange_attempts` says what was tried)
@@ -28,7 +33,7 @@ on the rank's own device before it is timed, and again after):
   secondary.input_1024x1024
                         BASELINE.json config 4: the shipped 1024x1024 deck, all 20 000 steps, on the same N ranks
                         (p2p and rccl), Reynolds line and av_vels compared with the reference binary's
-At N = 1 the line also carries `sustained` (the headline deck for 3 x >= 2000 steps back to back: what the socket power cap
+At N = 1 a --full line also carries `sustained` (the headline deck for 3 x >= 2000 steps back to back: what the socket power cap
 leaves) and `secondary.shipped_decks` (BASELINE.json configs 2 - 3: the reference's four input decks through lbm_run, each
 with seconds, us per step, MLUPS, final_state.dat digest == the reference binary's, av_vels under check.py's rule).
 Everything after the headline runs under a time budget (--budget-s): a part that does not fit is recorded as
@@ -66,9 +71,21 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="8192x8192", help="NXxNY of the synthetic deck (default: the BASELINE config)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: repeated timed regions (see --reps), the profiled repetition behind `roofline` / "
+                         "`phases`, socket power, the bit-exact check of partitioned runs against a single-GPU run, the variants, the "
+                         "secondary decks, the sustained line and the CPU baseline (each still switched off by its --no-* option).  "
+                         "Without it a run sets up, warms up (--warmup steps), times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed region computed as DIR/<name>.npy: av_vels.npy (float32, one "
+                         "value per timed step) and the populations, cells.npy (ny x nx x 9 float32) up to 2^20 cells, else "
+                         "cells_sample.npy (2^20 cells x 9 float32 at indices drawn with seed 0, sorted, duplicates dropped).  The deck "
+                         "is seeded; a plain run's state is that of warm-up + steps (with --full and --steps <= 50 the untimed settling "
+                         "repetitions, whose count follows the timing, come in between)")
     ap.add_argument("--reps", type=int, default=0,
                     help="the timed region (EXACTLY --steps steps between two barriers) is repeated this many times and the "
-                         "MEDIAN is reported: a single short region carries the first launches' ramp.  Default: 5, or 21 when "
+                         "MEDIAN is reported: a single short region carries the first launches' ramp.  Default without --full: 1.  "
+                         "With --full: 5, or 21 when "
                          "--steps <= 50: regions of 1-7 ms separated by host gaps keep speeding up for ten or more repetitions "
                          "(clocks, caches: 1.44, 1.14, 1.17, 1.17, 1.16, 1.16, 1.13, 1.12, 1.10 ms for nine 20-step runs of an 8-GPU "
                          "rank's share, 1.06 ms after sixty), and the median of nine sat in the middle of that ramp")
@@ -106,7 +123,10 @@ def parse_args(argv=None):
                     help="self-launch test: the rank processes only rendezvous (gloo), report their ranks and exit; no GPU is touched")
     args = ap.parse_args(argv)
     if args.reps <= 0:
-        args.reps = 21 if args.steps <= 50 else 5
+        args.reps = (21 if args.steps <= 50 else 5) if args.full else 1
+    if not args.full:
+        # a plain run: the headline alone
+        args.no_variants = args.no_secondary = args.no_phases = args.no_power = args.no_verify = args.no_cpu_baseline = True
     return args
 
 
@@ -549,6 +569,21 @@ def roofline_object(kernel: str, nx: int, ny: int, cells_per_launch: float, laun
     return roof
 
 
+DUMP_CELLS = 1 << 20                 # populations written by --dump-outputs: 2^20 cells x 9 floats = 36 MiB at most
+
+
+def dump_outputs(directory: str, av: np.ndarray, cells: np.ndarray) -> None:
+    """--dump-outputs: av_vels of the last timed region and the populations after it (all of them, or a fixed sample)."""
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "av_vels.npy"), np.ascontiguousarray(av, dtype=np.float32))
+    flat = cells.reshape(-1, cells.shape[-1])
+    if flat.shape[0] <= DUMP_CELLS:
+        np.save(os.path.join(directory, "cells.npy"), np.ascontiguousarray(cells, dtype=np.float32))
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, flat.shape[0], size=DUMP_CELLS))
+        np.save(os.path.join(directory, "cells_sample.npy"), np.ascontiguousarray(flat[idx], dtype=np.float32))
+
+
 def main() -> int:
     argv = sys.argv[1:]
     args = parse_args(argv)
@@ -838,6 +873,11 @@ def main() -> int:
         power = sampler.stop() if sampler is not None else None
     elapsed = float(np.median(times))
     assert av.shape == (args.steps,) and np.all(np.isfinite(av)) and np.all(av > 0)
+    if args.dump_outputs:
+        stage("dump outputs")
+        cells = sim.gather_cells()                         # collective: the whole grid on rank 0
+        if rank == 0:
+            dump_outputs(args.dump_outputs, av, cells)
     desc = sim.partition.describe()
     what = sim.describe()
     sim_layout = dict(sim.layout)
@@ -951,8 +991,9 @@ def main() -> int:
                                     "the part's clocks and caches take that long to settle whatever the region length)",
                        "ms_per_rep": [t * 1e3 for t in times]},
             "pct_hbm_roofline": 100.0 * mlups / world / (HBM_PEAK_GBS * 1e9 / ALGO_BYTES_PER_CELL / 1e6),
-            "roofline": roof,
         }
+        if args.full:                                      # per-kernel figures: they rest on the profiled repetition
+            out["roofline"] = roof
         if phases is not None:
             out["phases"] = phases
         if verify is not None:

@@ -224,6 +224,7 @@ def fuzz(a) -> int:
             if rng.random() < 0.4:
                 spec["env"]["LBM_TUNE_TILE_GHOST_ROWS"] = "1"      # column blocks (py = 1) that keep ghost rows instead of wrapping in the launch
             child_env = {k: v for k, v in os.environ.items() if k not in KNOBS}
+            child_env["GPU_MAX_HW_QUEUES"] = "16"        # whatever the caller's environment says: a queue per rank
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--tiles-case", json.dumps(spec)], capture_output=True, text=True, timeout=600, env=child_env)
             line = ([l for l in r.stdout.splitlines() if l.startswith("tiles ")] or ["tiles: no verdict"])[-1]
             if r.returncode != 0 or " ok" not in line:

@@ -82,7 +82,7 @@ step() {
       env ${ev//@/ } timeout -k 10 240 python scripts/ab_ring.py --single --grid $g --steps $st --rounds $ro - 2>&1 | grep -v amdgpu.ids | tail -1 | tee -a "$OUT/single1.txt" ;;
     ringbench)
       local g=${arg%%:*} st=20; [ "$g" != "$arg" ] && st=${arg#*:}
-      timeout -k 10 300 python bench.py --ring --workload $g --steps $st --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$OUT/ring_${g}_s$st.json" 2> "$OUT/ring_${g}_s$st.err"
+      timeout -k 10 300 python bench.py --full --ring --workload $g --steps $st --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$OUT/ring_${g}_s$st.json" 2> "$OUT/ring_${g}_s$st.err"
       local rc=$?; python - "$OUT/ring_${g}_s$st.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -90,20 +90,20 @@ ph = d.get("phases", {}).get("max_over_ranks", {})
 print(f"ring {d['config'].get('workload')}: {d['ms_per_step'] * 1e3:.2f} us/step; " + ", ".join(f"{k} {v:.1f}" for k, v in ph.items()))
 PY
       return $rc ;;
-    bench) timeout -k 10 500 python bench.py ${arg:---steps 20 --warmup 5} > "$OUT/bench.json" 2> "$OUT/bench.err"; local rc=$?; tail -c 1500 "$OUT/bench.json"; return $rc ;;
+    bench) timeout -k 10 500 python bench.py --full ${arg:---steps 20 --warmup 5} > "$OUT/bench.json" 2> "$OUT/bench.err"; local rc=$?; tail -c 1500 "$OUT/bench.json"; return $rc ;;
     prof)
       rm -rf "$OUT/prof"
-      timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- python3 bench.py ${arg:---steps 20 --warmup 5 --no-cpu-baseline --no-variants} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
+      timeout -k 10 500 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o trace --output-format csv -- python3 bench.py --full ${arg:---steps 20 --warmup 5 --no-cpu-baseline --no-variants} > "$OUT/prof_bench.json" 2> "$OUT/prof.err"
       local rc=$?; find "$OUT/prof" -name '*kernel_stats.csv' | head -1 | xargs -r head -8; find "$OUT/prof" -name '*kernel_trace.csv' -delete; return $rc ;;
     pmc)
       local ctr=${arg%%:*} rest=""; [ "$ctr" != "$arg" ] && rest=${arg#*:}
       local d="$OUT/pmc_$(echo $ctr | tr ' ' '_' | cut -c1-40)"; rm -rf "$d"
-      timeout -k 10 500 rocprofv3 --pmc $ctr -d "$d" -o pmc --output-format csv -- python3 bench.py ${rest:---steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-phases --no-power} > "$d.json" 2> "$d.err"
+      timeout -k 10 500 rocprofv3 --pmc $ctr -d "$d" -o pmc --output-format csv -- python3 bench.py --full ${rest:---steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-phases --no-power} > "$d.json" 2> "$d.err"
       local rc=$?; tail -3 "$d.err"; return $rc ;;
     pmcsum)
       local ctr lab rest; IFS=: read -r ctr lab rest <<< "$arg"
       local d="$OUT/pmcsum_${lab:-x}"; rm -rf "$d"
-      timeout -k 10 500 rocprofv3 --pmc $ctr -d "$d" -o pmc --output-format csv -- python3 bench.py ${rest:---steps 20 --warmup 5 --reps 2} --no-cpu-baseline --no-variants --no-secondary --no-phases --no-power > "$d.json" 2> "$d.err" || { tail -5 "$d.err"; return 1; }
+      timeout -k 10 500 rocprofv3 --pmc $ctr -d "$d" -o pmc --output-format csv -- python3 bench.py --full ${rest:---steps 20 --warmup 5 --reps 2} --no-cpu-baseline --no-variants --no-secondary --no-phases --no-power > "$d.json" 2> "$d.err" || { tail -5 "$d.err"; return 1; }
       python - "$d" "$lab" <<'PY' | tee -a "$OUT/pmcsum.txt"
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)
@@ -134,11 +134,11 @@ PY
     uselib) cp "mpilattice-boltzmann_amd/lib/variants/$arg.so" mpilattice-boltzmann_amd/lib/liblbm_d2q9.so && echo "now running lib/variants/$arg.so" ;;
     round)
       local wl=${arg:-8192x8192} P="$OUT/profiles"; mkdir -p "$P"
-      local B="bench.py --workload $wl --no-cpu-baseline --no-variants --no-secondary --reps 1" S="--steps 20 --warmup 5 --reps 2"
+      local B="bench.py --full --workload $wl --no-cpu-baseline --no-variants --no-secondary --reps 1" S="--steps 20 --warmup 5 --reps 2"
       rm -rf "$OUT/prof" "$OUT"/pmc_fetch "$OUT"/pmc_write "$OUT"/pmc_sq1 "$OUT"/pmc_sq2
       # the kernel trace runs the DEFAULT region (200 steps x 5 repetitions + warm-up: ~280 launches): launches made while the part ramps
       # up from idle weigh as little in its average as in bench.py's median
-      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o trace -- python3 bench.py --workload $wl --no-cpu-baseline --no-variants --no-secondary > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || return 1
+      timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o trace -- python3 bench.py --full --workload $wl --no-cpu-baseline --no-variants --no-secondary > "$OUT/prof_bench.json" 2> "$OUT/prof.err" || return 1
       # the PMC passes run the DRIVER's step count, each in its own run (no trace flags beside --pmc)
       timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o pmc -- python3 $B $S > /dev/null 2> "$OUT/pmc_fetch.err" || return 1
       timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/pmc_write" -o pmc -- python3 $B $S > /dev/null 2> "$OUT/pmc_write.err" || return 1
@@ -151,8 +151,8 @@ PY
       if [ "$wl" = 8192x8192 ]; then
         # the bench lines AFTER the PMC passes of this session: roofline.* rests on the counters of the same build on the same box
         # (bench.py reads profiles/<PROFILE_ROUND>/roofline.json, which make_roofline.py has just written on this box)
-        timeout -k 10 500 python bench.py > "$P/bench_n1.json" 2> "$OUT/bench_n1.err" || { tail -5 "$OUT/bench_n1.err"; return 1; }
-        timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$P/bench_n1_driver_style.json" 2>> "$OUT/bench_n1.err" || return 1
+        timeout -k 10 500 python bench.py --full > "$P/bench_n1.json" 2> "$OUT/bench_n1.err" || { tail -5 "$OUT/bench_n1.err"; return 1; }
+        timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > "$P/bench_n1_driver_style.json" 2>> "$OUT/bench_n1.err" || return 1
         cut -c1-300 "$P/bench_n1.json"; echo; cut -c1-200 "$P/bench_n1_driver_style.json"; echo
       fi
       cp profiles/$TAG/roofline*.json profiles/$TAG/pmc_*.csv "$P/" ;;
@@ -160,47 +160,47 @@ PY
       local P="$OUT/profiles"; mkdir -p "$P"
       short() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1].split('/')[-1], 'us/step %.2f' % (d['ms_per_step']*1e3), d['config']['loop'], d['config'].get('p2p'), (d.get('parity_check') or {}).get('ok'))" "$1"; }
       # the whole grid on THIS box, for the ratios (boxes differ by a few per cent): the default region and the driver's
-      python bench.py --no-cpu-baseline --no-variants --no-secondary > "$P/whole_8192x8192.json" && short "$P/whole_8192x8192.json" || return 1
-      python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/whole_8192x8192_s20.json" && short "$P/whole_8192x8192_s20.json" || return 1
-      python bench.py --workload 1024x1024 --steps 3000 --warmup 100 --no-cpu-baseline --no-secondary > "$P/bench_1024x1024.json" && short "$P/bench_1024x1024.json" || return 1
+      python bench.py --full --no-cpu-baseline --no-variants --no-secondary > "$P/whole_8192x8192.json" && short "$P/whole_8192x8192.json" || return 1
+      python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/whole_8192x8192_s20.json" && short "$P/whole_8192x8192_s20.json" || return 1
+      python bench.py --full --workload 1024x1024 --steps 3000 --warmup 100 --no-cpu-baseline --no-secondary > "$P/bench_1024x1024.json" && short "$P/bench_1024x1024.json" || return 1
       for wl in 8192x4096 8192x2048 8192x1024 1024x128; do
         local st=300; [ $wl = 1024x128 ] && st=3000
         for ex in p2p rccl; do
-          python bench.py --ring --exchange $ex --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_${ex}.json" && short "$P/ring_${wl}_${ex}.json" || return 1
+          python bench.py --full --ring --exchange $ex --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_${ex}.json" && short "$P/ring_${wl}_${ex}.json" || return 1
         done
-        python bench.py --ring --exchange p2p --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_p2p_s20.json" && short "$P/ring_${wl}_p2p_s20.json" || return 1
+        python bench.py --full --ring --exchange p2p --workload $wl --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_p2p_s20.json" && short "$P/ring_${wl}_p2p_s20.json" || return 1
       done
       for wl in 8192x1024 1024x128; do
         local st=300; [ $wl = 1024x128 ] && st=3000
-        python bench.py --ring --exchange rccl --step-allreduce --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_rccl_step_allreduce.json" && short "$P/ring_${wl}_rccl_step_allreduce.json" || return 1
-        python bench.py --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-secondary > "$P/single_${wl}.json" && short "$P/single_${wl}.json" || return 1
+        python bench.py --full --ring --exchange rccl --step-allreduce --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/ring_${wl}_rccl_step_allreduce.json" && short "$P/ring_${wl}_rccl_step_allreduce.json" || return 1
+        python bench.py --full --workload $wl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-secondary > "$P/single_${wl}.json" && short "$P/single_${wl}.json" || return 1
         for ex in p2p rccl; do
           rm -rf "$OUT/prof_ring_${wl}_$ex"
-          timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_ring_${wl}_$ex" -o trace -- python3 bench.py --ring --exchange $ex --workload $wl --steps $st --warmup 30 --reps 1 --no-cpu-baseline --no-verify --no-variants --no-secondary --no-phases > /dev/null 2> "$OUT/prof_ring_${wl}_$ex.err" || return 1
+          timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_ring_${wl}_$ex" -o trace -- python3 bench.py --full --ring --exchange $ex --workload $wl --steps $st --warmup 30 --reps 1 --no-cpu-baseline --no-verify --no-variants --no-secondary --no-phases > /dev/null 2> "$OUT/prof_ring_${wl}_$ex.err" || return 1
           find "$OUT/prof_ring_${wl}_$ex" -name '*kernel_stats.csv' -exec cp {} "$P/ring_${wl}_${ex}_kernel_stats.csv" \;
           find "$OUT/prof_ring_${wl}_$ex" -name '*kernel_trace.csv' -delete
         done
       done
-      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 2 --steps 20 --warmup 5 > "$P/bench_2ranks_one_gpu_8192.json" && short "$P/bench_2ranks_one_gpu_8192.json" ;;
+      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --full --gpus 2 --steps 20 --warmup 5 > "$P/bench_2ranks_one_gpu_8192.json" && short "$P/bench_2ranks_one_gpu_8192.json" ;;
     tilebench)
       local P="$OUT/profiles"; mkdir -p "$P"
       short() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1].split('/')[-1], 'us/step %.2f' % (d['ms_per_step']*1e3), d['config']['loop'], d['config'].get('p2p'), (d.get('parity_check') or {}).get('ok'))" "$1"; }
       # block of a 4 x 2 / 2 x 2 / 2 x 1 tiling of 8192^2 and of a 4 x 2 tiling of 1024^2, each beside the row share of the same cell count
       for pair in 2048x4096:8192x1024 4096x4096:8192x2048 4096x8192:8192x4096 256x512:1024x128; do
         local tl=${pair%%:*} rw=${pair#*:} st=300; [ $tl = 256x512 ] && st=3000
-        python bench.py --ring --rank-grid 1x1 --workload $tl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_ring_${tl}.json" && short "$P/tile_ring_${tl}.json" || return 1
-        python bench.py --ring --rank-grid 1x1 --workload $tl --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_ring_${tl}_s20.json" && short "$P/tile_ring_${tl}_s20.json" || return 1
-        python bench.py --ring --exchange p2p --workload $rw --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_session_row_ring_${rw}.json" && short "$P/tile_session_row_ring_${rw}.json" || return 1
+        python bench.py --full --ring --rank-grid 1x1 --workload $tl --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_ring_${tl}.json" && short "$P/tile_ring_${tl}.json" || return 1
+        python bench.py --full --ring --rank-grid 1x1 --workload $tl --steps 20 --warmup 5 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_ring_${tl}_s20.json" && short "$P/tile_ring_${tl}_s20.json" || return 1
+        python bench.py --full --ring --exchange p2p --workload $rw --steps $st --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/tile_session_row_ring_${rw}.json" && short "$P/tile_session_row_ring_${rw}.json" || return 1
       done
       for tl in 2048x4096 256x512; do
         local st=300; [ $tl = 256x512 ] && st=3000
         rm -rf "$OUT/prof_tile_$tl"
-        timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_tile_$tl" -o trace -- python3 bench.py --ring --rank-grid 1x1 --workload $tl --steps $st --warmup 30 --reps 1 --no-cpu-baseline --no-verify --no-variants --no-secondary --no-phases > /dev/null 2> "$OUT/prof_tile_$tl.err" || return 1
+        timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_tile_$tl" -o trace -- python3 bench.py --full --ring --rank-grid 1x1 --workload $tl --steps $st --warmup 30 --reps 1 --no-cpu-baseline --no-verify --no-variants --no-secondary --no-phases > /dev/null 2> "$OUT/prof_tile_$tl.err" || return 1
         find "$OUT/prof_tile_$tl" -name '*kernel_stats.csv' -exec cp {} "$P/tile_ring_${tl}_kernel_stats.csv" \;
         find "$OUT/prof_tile_$tl" -name '*kernel_trace.csv' -delete
       done
-      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 4 --rank-grid 2x2 --workload 4096x4096 --steps 20 --warmup 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_tiles_2x2.json" && short "$P/bench_4ranks_one_gpu_4096_tiles_2x2.json" || return 1
-      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 4 --workload 4096x4096 --steps 20 --warmup 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_rows.json" && short "$P/bench_4ranks_one_gpu_4096_rows.json" ;;
+      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --full --gpus 4 --rank-grid 2x2 --workload 4096x4096 --steps 20 --warmup 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_tiles_2x2.json" && short "$P/bench_4ranks_one_gpu_4096_tiles_2x2.json" || return 1
+      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --full --gpus 4 --workload 4096x4096 --steps 20 --warmup 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_rows.json" && short "$P/bench_4ranks_one_gpu_4096_rows.json" ;;
     tilewide)
       # grids much wider than tall on 8 ranks ("2-D decomposition for grids wider than tall"): a rank's share as a row block
       # (few rows: deep ghost rows cost a large share, 16 rows fall back to the one-step loop) and as a block of an 8 x 1 tiling
@@ -208,9 +208,9 @@ PY
       short() { python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1].split('/')[-1], 'us/step %.2f' % (d['ms_per_step']*1e3), d['config']['loop'], d['config'].get('p2p'), (d.get('parity_check') or {}).get('ok'))" "$1"; }
       for pair in 2048x512:16384x64 4096x256:32768x32 8192x128:65536x16; do
         local tl=${pair%%:*} rw=${pair#*:}
-        python bench.py --ring --rank-grid 1x1 --column-block --workload $tl --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_tile_ring_${tl}.json" && short "$P/wide_tile_ring_${tl}.json" || return 1
-        python bench.py --ring --rank-grid 1x1 --workload $tl --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_tile_ring_${tl}_ghost_rows.json" && short "$P/wide_tile_ring_${tl}_ghost_rows.json" || return 1
-        python bench.py --ring --exchange p2p --workload $rw --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_row_ring_${rw}.json" && short "$P/wide_row_ring_${rw}.json" || return 1
+        python bench.py --full --ring --rank-grid 1x1 --column-block --workload $tl --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_tile_ring_${tl}.json" && short "$P/wide_tile_ring_${tl}.json" || return 1
+        python bench.py --full --ring --rank-grid 1x1 --workload $tl --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_tile_ring_${tl}_ghost_rows.json" && short "$P/wide_tile_ring_${tl}_ghost_rows.json" || return 1
+        python bench.py --full --ring --exchange p2p --workload $rw --steps 1000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary > "$P/wide_row_ring_${rw}.json" && short "$P/wide_row_ring_${rw}.json" || return 1
       done ;;
     decks)
       for d in 128x128 128x256 256x256 1024x1024; do
@@ -223,7 +223,7 @@ PY
     timeline)
       # kernel-by-kernel timeline of short runs: rocprofv3 --kernel-trace of <bench args>, the dispatch table kept (timeline.csv: name, start, end in ns)
       rm -rf "$OUT/timeline"
-      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/timeline" -o trace -- python3 bench.py ${arg:---ring --workload 8192x1024 --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-variants --no-secondary --no-phases --no-verify --no-power} > "$OUT/timeline.json" 2> "$OUT/timeline.err" || return 1
+      timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$OUT/timeline" -o trace -- python3 bench.py --full ${arg:---ring --workload 8192x1024 --steps 20 --warmup 5 --reps 3 --no-cpu-baseline --no-variants --no-secondary --no-phases --no-verify --no-power} > "$OUT/timeline.json" 2> "$OUT/timeline.err" || return 1
       python - "$OUT/timeline" <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
@@ -240,10 +240,10 @@ PY
       # processes sharing this GPU for 400 steps x 5
       local P="$OUT/profiles"; mkdir -p "$P"
       for ex in p2p rccl; do
-        timeout -k 10 300 python bench.py --ring --exchange $ex --workload 8192x1024 --steps 2000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary --no-phases > "$P/ring_soak_$ex.json" 2>> "$OUT/soak.err" || return 1
+        timeout -k 10 300 python bench.py --full --ring --exchange $ex --workload 8192x1024 --steps 2000 --warmup 30 --reps 3 --no-cpu-baseline --no-variants --no-secondary --no-phases > "$P/ring_soak_$ex.json" 2>> "$OUT/soak.err" || return 1
         python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1].split('/')[-1], 'us/step %.2f' % (d['ms_per_step']*1e3), d['parity_check'])" "$P/ring_soak_$ex.json"
       done
-      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --gpus 4 --workload 4096x4096 --steps 400 --warmup 20 --reps 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_soak.json" 2>> "$OUT/soak.err" || return 1
+      LBM_FORCE_DEVICE=0 timeout -k 10 500 python bench.py --full --gpus 4 --workload 4096x4096 --steps 400 --warmup 20 --reps 5 --no-secondary > "$P/bench_4ranks_one_gpu_4096_soak.json" 2>> "$OUT/soak.err" || return 1
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1].split('/')[-1], 'us/step %.2f' % (d['ms_per_step']*1e3), d['config']['p2p'], d['parity_check']['ok'], {k: v.get('parity_ok', v.get('error')) for k, v in d['variants'].items()})" "$P/bench_4ranks_one_gpu_4096_soak.json" ;;
     ab)
       local libs=${arg%%:*} rest=""; [ "$libs" != "$arg" ] && rest=${arg#*:}

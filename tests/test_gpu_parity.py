@@ -1202,7 +1202,7 @@ def test_bench_on_two_gpus_harvests_every_part(lbm):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--workload", "4096x4096",
-                        "--secondary-steps", "2000"], capture_output=True, text=True, timeout=600, env=env)
+                        "--secondary-steps", "2000", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
     assert out["config"]["loop"] == "p2p" and out["parity_check"]["ok"] is True and "truncated" not in out
@@ -1381,7 +1381,7 @@ def test_bench_self_launch_two_ranks_on_one_gpu(lbm):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(LBM_FORCE_DEVICE="0", LBM_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--reps", "3",
-                        "--workload", "2048x2048", "--secondary-steps", "3000"], capture_output=True, text=True, timeout=900, env=env)
+                        "--workload", "2048x2048", "--secondary-steps", "3000", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1
@@ -1420,6 +1420,7 @@ def test_cli_drives_several_ranks_from_one_process(lbm, digests, tmp_path, gpus,
     allows; same stdout contract, byte-identical final_state.dat, same Reynolds line as one rank."""
     ppath, opath = deck_paths(name, digests)
     env = dict(os.environ, LBM_GPUS=str(gpus), LBM_DEVICES=",".join(["0"] * gpus), LBM_P2P_TIMEOUT_MS="20000")
+    env.pop("GPU_MAX_HW_QUEUES", None)          # the shim raises the queue budget for ranks that share a device unless one is set
     r = subprocess.run([lbm.CLI_PATH, ppath, opath], cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr
     out = r.stdout.splitlines()
@@ -1437,6 +1438,7 @@ def test_cli_drives_a_tile_decomposition_from_one_process(lbm, digests, tmp_path
     reference binary's final_state.dat byte for byte, whichever way the grid is cut (4 x 2: BASELINE.json config 4's eight ranks)."""
     ppath, opath = deck_paths(name, digests)
     env = dict(os.environ, LBM_GPUS=str(gpus), LBM_RANK_GRID=grid, LBM_DEVICES=",".join(["0"] * gpus), LBM_P2P_TIMEOUT_MS="20000")
+    env.pop("GPU_MAX_HW_QUEUES", None)          # the shim raises the queue budget for ranks that share a device unless one is set
     r = subprocess.run([lbm.CLI_PATH, ppath, opath], cwd=tmp_path, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr
     out = r.stdout.splitlines()
@@ -1459,7 +1461,7 @@ def test_cli_chooses_tiles_for_a_grid_much_wider_than_tall(lbm, tmp_path):
     for tag, extra in (("one", {}), ("auto", dict(LBM_GPUS="4", LBM_DEVICES="0,0,0,0", LBM_RANK_GRID="auto", LBM_P2P_TIMEOUT_MS="20000"))):
         d = tmp_path / tag
         d.mkdir()
-        env = {k: v for k, v in os.environ.items() if k not in ("LBM_GPUS", "LBM_DEVICES", "LBM_RANK_GRID")}
+        env = {k: v for k, v in os.environ.items() if k not in ("LBM_GPUS", "LBM_DEVICES", "LBM_RANK_GRID", "GPU_MAX_HW_QUEUES")}
         env.update(extra)
         r = subprocess.run([lbm.CLI_PATH, ppath, opath], cwd=d, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr
@@ -1485,7 +1487,7 @@ def test_cli_ranks_of_one_process_on_the_tall_geometry(lbm, tmp_path, devices):
     for tag, extra in (("one", {}), ("two", dict(LBM_GPUS="2", LBM_DEVICES=devices, LBM_P2P_TIMEOUT_MS="20000"))):
         d = tmp_path / tag
         d.mkdir()
-        env = {k: v for k, v in os.environ.items() if k not in ("LBM_GPUS", "LBM_DEVICES")}
+        env = {k: v for k, v in os.environ.items() if k not in ("LBM_GPUS", "LBM_DEVICES", "GPU_MAX_HW_QUEUES")}
         env.update(extra)
         r = subprocess.run([lbm.CLI_PATH, ppath, opath], cwd=d, capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr

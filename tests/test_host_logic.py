@@ -394,6 +394,31 @@ def _bench_module():
     return mod
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full a run times ONE region of exactly --steps steps and nothing beside it; --full brings back the repetitions and
+    every extra part.  --dump-outputs writes float32 arrays under 64 MB: all cells of a small grid, a fixed sample of a large one."""
+    import numpy as np
+    bench = _bench_module()
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not a.full and a.reps == 1 and a.dump_outputs == ""
+    assert a.no_variants and a.no_secondary and a.no_phases and a.no_power and a.no_verify and a.no_cpu_baseline
+    f = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert f.full and f.reps == 21 and bench.parse_args(["--full"]).reps == 5
+    assert not (f.no_variants or f.no_secondary or f.no_phases or f.no_power or f.no_verify or f.no_cpu_baseline)
+    assert bench.parse_args(["--full", "--no-variants"]).no_variants and bench.parse_args(["--reps", "3"]).reps == 3
+    av = np.linspace(1e-3, 2e-3, 20, dtype=np.float32)
+    small = np.random.default_rng(1).random((48, 64, 9), dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "small"), av, small)
+    assert np.array_equal(np.load(tmp_path / "small" / "av_vels.npy"), av)
+    assert np.array_equal(np.load(tmp_path / "small" / "cells.npy"), small)
+    big = np.arange((1 << 20) + 4096, dtype=np.float32)[:, None].repeat(9, axis=1).reshape(1, -1, 9)
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), av, big)
+    s1, s2 = np.load(tmp_path / "big1" / "cells_sample.npy"), np.load(tmp_path / "big2" / "cells_sample.npy")
+    assert s1.dtype == np.float32 and s1.shape[1] == 9 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1[:, 0]) > 0) and sum(p.stat().st_size for p in (tmp_path / "big1").iterdir()) < 64 << 20
+
+
 def test_bench_fallback_chain_and_budget_fit_the_drivers_limit():
     """the driver kills a bench run at 600 s.  Self-launched, the three-mode worst case (every set of rank
     processes hanging until --launch-timeout) must sum below 500 s, the ranks' own budget must end before their launcher
