@@ -33,7 +33,7 @@ namespace {
 #define LBM_MTY4 13
 #endif
 #ifndef LBM_MTY4T          // tile height and block size of the 4-step instantiation, tall geometry
-#define LBM_MTY4T 23
+#define LBM_MTY4T 24
 #define LBM_MLANES4T 768
 #endif
 constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY4Tall = LBM_MTY4T, kMLanes = LBM_MLANES, kMLanes4Tall = LBM_MLANES4T,
@@ -42,14 +42,18 @@ constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY
               kMaxGroup = 8;       // most launches of such a group
 constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall) : (kMTY4 < kMTY4Tall ? kMTY4 : kMTY4Tall);
 // Geometry of a launch: tile width, and by steps per launch tile height and block size.
-//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 72 x 20 frame, 51.8 KB, three blocks per CU).  K = 4 on the same tiles
-//                (rounds 1-2) needs a 76 x 22 frame = 60 KB, two blocks per CU: 353 - 363 us/step at 8192 x 8192 against 341 - 347 for
-//                K = 3.  On 64 x 13 tiles (round 3) its frame is 76 x 19 = 52.0 KB, three blocks per CU again: a tile recomputes 1.36 x
+//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4 on the same tiles
+//                (rounds 1-2) needed a 76 x 22 frame = 60 KB, two blocks per CU: 353 - 363 us/step at 8192 x 8192 against 341 - 347 for
+//                K = 3.  On 64 x 13 tiles (round 3) its frame is 72 x 19 = 49.0 KB (76 x 19 = 52.0 KB until round 4), three blocks per CU again: a tile recomputes 1.36 x
 //                its cells per step instead of 1.31 x but the launch moves 21.5 B per cell-step instead of 26.9 — 8192 x 8192 346.6
 //                (K = 3) -> 324.0, 4096 x 4096 87.2 -> 78.4, 1024 x 1024 8.16 -> 7.07, 8192 x 1024 53.0 -> 43.5 (profiles/r03/ab_k3_k4.txt).
-//   kGeomTall    K = 4 on 64 x 23 tiles with 768-lane blocks: 76 x 29 frame = 79.3 KB, TWO blocks of twelve waves per CU (the same 24
-//                waves): ring work 1.24 x, 60 wave-passes for 1.77 x the cells of 37.  With double-precision sum|u| terms this was a
-//                draw (310.8 against 311.9 - 317.3, ab_k4_big_blocks_8192.txt); the launch runs at the socket power limit, and with
+//   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24
+//                waves): 60 wave-passes per tile.  Until round 4 the columns grew by 2 (K - j) (multi_ex below) and the tiles were 64 x 23:
+//                76 x 29 frame = 79.3 KB (64 x 24 did not fit two blocks), ring work 1.24 x, 60 wave-passes for 1.77 x the cells of 37.
+//                The even-rounded growth and the 24th row, 8192 x 8192 in one process, us/step min of two interleaved runs each: 64 x 23 with
+//                the old growth 284.4 / 282.9, with the new 277.7 / 278.8, 64 x 24 269.6 / 272.0 (SQ_INSTS_VALU per launch 557.9 M ->
+//                535.9 M -> 529.3 M, FETCH_SIZE equal or lower: profiles/r05/).  Round 4, on 76-wide frames: with double-precision sum|u| terms
+//                this was a draw (310.8 against 311.9 - 317.3, ab_k4_big_blocks_8192.txt); the launch runs at the socket power limit, and with
 //                the compensated float terms the form that does less work per cell wins wherever a launch is rounds of blocks — us/step
 //                64 x 13 / 64 x 21 / 64 x 22 / 64 x 23 (768 lanes): 8192 x 8192 315.0 & 324.7 / 304.6 / 307.7 / 303.9, 4096 x 4096 81.0 & 85.4 /
 //                77.5 / 75.6 / 74.0, 8192 x 1024 43.6 & 44.1 / 40.5 / 40.2 / 39.9, 2048 x 2048 22.3 & 22.8 / 22.3 / 21.5 / 21.6, 1024 x 1024
@@ -64,10 +68,15 @@ constexpr int multi_ty(int k, int g) { return k >= 4 ? (g == kGeomTall ? kMTY4Ta
 constexpr int multi_lanes(int k, int g) { return (k >= 4 && g == kGeomTall) ? kMLanes4Tall : kMLanes; }
 constexpr int geom_for(int k, int g) { return (g == kGeomTall && k < 4) ? kGeomStd : g; }      // the instantiation a launch of k steps uses
 
-// Sub-step j of k (1-based) works on the owned tile grown by (k-j) rows and 2(k-j) columns on each
-// side: columns grow twice as fast so that every region starts on an even x and a lane can own an
-// x-PAIR of cells (8-byte accesses; the two cells' arithmetic is packed by the compiler into
-// v_pk_*_f32, which halves the instruction count - the one-cell form of this kernel was VALU-bound).
+// Sub-step j of k (1-based) works on the owned tile grown by (k-j) rows and multi_ex(k-j) = 2 ceil((k-j)/2)
+// columns on each side: the column growth is rounded up to even so that every region starts on an even x
+// and a lane can own an x-PAIR of cells (8-byte accesses; the two cells' arithmetic is packed by the
+// compiler into v_pk_*_f32, which halves the instruction count - the one-cell form of this kernel was
+// VALU-bound).  Where k-j is odd the region's outermost column lies outside every owned cell's dependency
+// cone: it is computed from whatever the frame holds there (stale values of an earlier sub-step, always
+// inside the frame) and never kept or counted.  (Rounds 1 - 4 grew the columns by 2(k-j): K = 4 regions
+// 76 / 72 / 68 / 64 wide instead of 72 / 68 / 68 / 64, frames 12 columns wider than needed.)
+constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
 #if LBM_TILE_STAMPS      // diagnostic builds (tile.h, scripts/tile_stamps.py): stamps of one block in the middle of the launch, lane 0
 #define LBM_MSTAMP(i) do { if (blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) g_tile_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -79,7 +88,7 @@ struct MultiGeom {
   static constexpr int TX = geom_tx(GEOM);                          // owned columns of a tile
   static constexpr int TY = multi_ty(K, GEOM);                      // owned rows of a tile
   static constexpr int LANES = multi_lanes(K, GEOM);                // block size
-  static constexpr int EY = K - 1, EX = 2 * (K - 1);                // growth of the first sub-step
+  static constexpr int EY = K - 1, EX = multi_ex(K - 1);            // growth of the first sub-step
   static constexpr int W = TX + 2 * EX, H = TY + 2 * EY;            // LDS frame
   static constexpr int cells = W * H;
   static constexpr size_t lds_bytes = sizeof(float) * 9 * cells + sizeof(double) * K * (LANES / 64) + (K >= 2 ? cells / 2 : 0);   // + a flag byte per x-pair
@@ -285,9 +294,9 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   // tile carries it).  The choice is block-uniform.
   auto k_substeps = [&](auto count_c) __attribute__((always_inline)) {
     constexpr bool COUNT = decltype(count_c)::value;
-    // ---- sub-step 1: pull from the source grid; region = owned tile grown by (ksteps-1) rows / 2(ksteps-1) columns
+    // ---- sub-step 1: pull from the source grid; region = owned tile grown by (ksteps-1) rows / multi_ex(ksteps-1) columns
     {
-      const int ey = ksteps - 1, ex = 2 * ey;
+      const int ey = ksteps - 1, ex = multi_ex(ey);
       const int wp = (TX + 2 * ex) / 2;                                 // pairs per region row
       const int np = wp * (TY + 2 * ey);
       // tiles whose frame (and its x -+ 1, y -+ 1 reads) lies inside the grid need none of the periodic
@@ -376,13 +385,13 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     if constexpr (K >= 2) {
       __syncthreads();
       LBM_MSTAMP(2);
-      // ---- sub-steps 2..ksteps: in place in the LDS frame, each on a region one row / two columns smaller.
+      // ---- sub-steps 2..ksteps: in place in the LDS frame, each on a region one row / zero or two columns smaller.
       // In place without holding a whole region in registers: sub-step j writes its row r where the
       // frame it read kept row r-1 (the frame creeps down one storage row per sub-step), and a region
       // of more than 512 pairs goes in passes of whole rows, bottom to top.  A pass reads, meets at a
       // barrier, then writes; what it overwrites (old rows up to its last row - 1) no later pass reads.
       auto in_lds_substep = [&](const int j) __attribute__((always_inline)) {
-        const int ey = ksteps - j, ex = 2 * ey;
+        const int ey = ksteps - j, ex = multi_ex(ey);
         const int wp = (TX + 2 * ex) / 2;                                // pairs per region row
         const int rows = TY + 2 * ey;
         const int rpp = kLanes / wp;                                       // whole rows per pass

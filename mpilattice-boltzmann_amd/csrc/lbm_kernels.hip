@@ -171,7 +171,7 @@ struct lbm_ctx {
   int n_prev_vecs = 1;       // ... and how many step vectors of that length the previous launch left (tile kernel: up to 8)
   int multi_K = 0;           // > 0: bandwidth-bound grid advanced K steps per launch by lbm_multi_kernel<K>
   int multi_tiles_x = 0;
-  int multi_geom = kGeomStd; // geometry of lbm_multi_kernel's launches (kernels/multi.h): standard, narrow (32-wide tiles), tall (K = 4 on 64 x 23)
+  int multi_geom = kGeomStd; // geometry of lbm_multi_kernel's launches (kernels/multi.h): standard, narrow (32-wide tiles), tall (K = 4 on 64 x 24)
   int multi_tx = kMTX;       // its tile width: 64, or 32 for partitions of one round of blocks
   bool multi_tail4 = true;   // lbm_run at K = 3: 4-step launches instead of a 1- or 2-step tail (LBM_TUNE_MULTI_TAIL4)
   int sweep_R = 0;           // > 0: lbm_run's 3-step launches are lbm_sweep_kernel<R> (streaming temporal blocking, kernels/sweep.h)
@@ -656,7 +656,7 @@ static int macro_group_for(int k, int ghost)
 // sub-steps: half the work per block, twice the blocks.  Measured us/step for 64 / 32 wide tiles (K = 3, one GPU):
 // 1024x128 3.22 / 2.53, 512x256 3.17 / 2.50, 512x512 3.42 / 3.44, 2048x256 4.94 / 5.05, 1024x1024 8.39 / 9.01.
 // LBM_TUNE_MULTI_TILE = 64 / 32 overrides the width; LBM_TUNE_MULTI_GEOM = 0 / 1 / 2 the whole choice.
-// The tall geometry (K = 4 on 64 x 23 tiles, 768-lane blocks, two per CU) from 2^20 cells up: where a launch is several rounds of
+// The tall geometry (K = 4 on 64 x 24 tiles, 768-lane blocks, two per CU) from 2^20 cells up: where a launch is several rounds of
 // blocks it is 4 - 10 % faster, at one round or less its 512 slots lose to 768 (kernels/multi.h).
 // Row partitions (interior + edge launch per macro-step) follow the same rule.  Measured one ring per PROCESS, as ranks run (two rings in
 // one process can share a hardware queue, which made the tall geometry look 20 % worse in a same-process A/B): standard / tall, us/step
@@ -1524,7 +1524,7 @@ int lbm_macro_next_launches(const lbm_ctx* c) { return (c && c->ghost > 0 && c->
 // `interior_rows` between them do not: the rows they need — their own, k below and k above — are owned rows.  (The last tile row
 // may hold fewer rows than a launch makes steps: the ring of the row below then reaches the ghost rows, and the top edge is two rows.)
 // (Tile ranks: the first `left_cols` and the last `right_cols` tile COLUMNS read exchanged columns as well — a tile's first sub-step reads
-// 2 (k - 1) + 1 columns beyond its own on each side; the interior is then the rectangle inside all four.)
+// multi_ex(k - 1) + 1 columns beyond its own on each side; the interior is then the rectangle inside all four.)
 struct MacroRows { int bottom_edge_rows, interior_rows, top_edge_rows, left_cols, right_cols; };
 static MacroRows macro_rows(const lbm_ctx* c, int k, int ext = 0)
 {
@@ -1540,7 +1540,7 @@ static MacroRows macro_rows(const lbm_ctx* c, int k, int ext = 0)
   }
   int l = 0, r = 0;
   if (c->ghost_x > 0) {
-    const int tx = c->multi_tx, ntx = c->multi_tiles_x, reach = 2 * (k - 1) + 1;
+    const int tx = c->multi_tx, ntx = c->multi_tiles_x, reach = multi_ex(k - 1) + 1;
     const int xlo = c->ghost_x, xhi = c->ghost_x + c->nxl;         // the owned columns [xlo, xhi)
     while (l < ntx && l * tx - reach < xlo) ++l;
     while (r < ntx - l && (ntx - r) * tx - 1 + reach >= xhi) ++r;
