@@ -123,8 +123,11 @@ int lbm_create_global(lbm_ctx** ctx, const lbm_params* p, int free_cells, const 
 typedef struct lbm_layout {
   int y0, ny_local;                 /* rows [y0, y0+ny_local) of the global grid belong to the rank */
   int macro_k;                      /* K of K-step mode for the whole run, or 0 */
-  int ghost;                        /* rows kept (and obstacle rows to supply) below and above the owned rows: 2 * macro_k (8 at macro_k = 3):
-                                       the launches between two halo exchanges make at most that many steps together (LBM_TUNE_MACRO_GHOST) */
+  int ghost;                        /* rows kept (and obstacle rows to supply) below and above the owned rows; the launches between two halo
+                                       exchanges make at most that many steps together.  One value for all ranks, from nx and the smallest /
+                                       largest rank's rows: 2 * macro_k (8 at macro_k = 3) by default; 16 (rounded down to a multiple of macro_k)
+                                       for ranks of < 2^21 cells with >= 128 rows each (macro_k, 4 at macro_k = 3, below 64 rows); 24 from 128
+                                       rows per rank and 32 from 256 where nx <= 2048 and nx * rows <= 2^19 on every rank (LBM_TUNE_MACRO_GHOST) */
   int group;                        /* most launches per halo exchange: ghost / macro_k (LBM_TUNE_MACRO_GROUP) */
 } lbm_layout;
 int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out);

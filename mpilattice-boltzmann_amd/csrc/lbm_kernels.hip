@@ -44,6 +44,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "lbm_d2q9.h"
@@ -152,6 +153,7 @@ struct lbm_ctx {
   double* sums = nullptr;
   int sums_cap = 0;
   double* sums_host = nullptr;   // pinned, sums_cap doubles
+  std::vector<std::pair<double*, double*>> sums_retired;   // (sums, sums_host) outgrown by a longer run: freed by lbm_destroy only (ensure_sums)
   int* counter = nullptr;
   bool counter_clean = false;   // the device counter is 0 (left so by the last fold of the previous run, enqueued on counter_clean_stream): a run that
   hipStream_t counter_clean_stream = nullptr;   // starts on THAT stream needs no memset; on another stream nothing would order its first fold behind the reset
@@ -224,22 +226,29 @@ void drop_graphs(lbm_ctx* c)
   }
 }
 
+// Room for n per-step sums.  Invariant: between the start of a partitioned run and its end nothing here calls hipFree, hipHostFree or
+// anything else that waits for the whole DEVICE — the neighbours may already spin in their wait kernels for this rank's rows, and where
+// several ranks of one process share a device such a wait dead-locks until the time-out (seen in the randomised tile cases: a second run
+// one step longer than the first).  create_impl sizes the buffers for max(max_iters, 4096) steps; a longer run allocates larger ones and
+// retires the old ones to sums_retired, which lbm_destroy frees.
 int ensure_sums(lbm_ctx* c, int n)
 {
   if (n <= c->sums_cap) return 0;
-  // room for the deck's own run length from the start: growing means hipFree, which waits for the whole DEVICE — harmless for one rank per
-  // device, a dead-lock until the time-out where several ranks of one process share a device and the others already wait for this one's
-  // rows (seen in the randomised tile cases: a second run one step longer than the first)
   n = std::max(n, std::max(c->p.max_iters, 4096));
-  drop_graphs(c);   // captured kernel arguments hold the old pointer
-  if (c->sums) HIP_TRY(hipFree(c->sums));
-  if (c->sums_host) HIP_TRY(hipHostFree(c->sums_host));
-  c->sums = nullptr;
-  c->sums_host = nullptr;
-  c->sums_cap = 0;
-  HIP_TRY(hipMalloc(&c->sums, sizeof(double) * static_cast<size_t>(n)));
+  double* dev = nullptr;
+  double* host = nullptr;
+  HIP_TRY(hipMalloc(&dev, sizeof(double) * static_cast<size_t>(n)));
   // pinned landing zone of lbm_run's one device-to-host copy per run (a pageable destination is staged: ~2x the time)
-  HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&c->sums_host), sizeof(double) * static_cast<size_t>(n), hipHostMallocDefault));
+  const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(double) * static_cast<size_t>(n), hipHostMallocDefault);
+  if (e != hipSuccess) {
+    c->sums_retired.emplace_back(dev, nullptr);
+    lbm_internal::set_error(std::string("hipHostMalloc (per-step sums): ") + hipGetErrorString(e));
+    return 1;
+  }
+  drop_graphs(c);   // captured kernel arguments hold the old pointer (whole grids only: partitions capture no graph)
+  if (c->sums || c->sums_host) c->sums_retired.emplace_back(c->sums, c->sums_host);
+  c->sums = dev;
+  c->sums_host = host;
   c->sums_cap = n;
   return 0;
 }
@@ -934,6 +943,7 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
   HIP_TRY_C(hipMalloc(&c->fold_scratch, sizeof(double) * kFoldSlices * 8));
   HIP_TRY_C(hipMalloc(&c->counter, sizeof(int)));
   HIP_TRY_C(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream));
+  if (ensure_sums(c, 1)) return fail();                   // max(max_iters, 4096) steps before any run starts (ensure_sums)
   // initial state (d2q9-bgk.c:880-902)
   {
     const float w0 = p->density * 4.0f / 9.0f, w1 = p->density / 9.0f, w2 = p->density / 36.0f;
@@ -1120,6 +1130,10 @@ int lbm_destroy(lbm_ctx* c)
   for (int i = 0; i < 2; ++i) if (c->partials[i]) (void)hipFree(c->partials[i]);
   if (c->sums) (void)hipFree(c->sums);
   if (c->sums_host) (void)hipHostFree(c->sums_host);
+  for (const auto& r : c->sums_retired) {
+    if (r.first) (void)hipFree(r.first);
+    if (r.second) (void)hipHostFree(r.second);
+  }
   if (c->fold_scratch) (void)hipFree(c->fold_scratch);
   if (c->counter) (void)hipFree(c->counter);
   if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
@@ -1507,11 +1521,9 @@ struct GroupPlan {
 static GroupPlan plan_group(const lbm_ctx* c, int left)
 {
   GroupPlan g;
-  while (left > 0 && g.n < c->group_max && g.n < kMaxGroup) {
-    const int k = next_multi_k(c, left);
-    if (g.n > 0 && g.total + k > c->ghost) break;
-    g.k[g.n++] = k; g.total += k; left -= k;
-  }
+  g.n = lbm_plan_group_for(c->multi_K, (c->self_periodic || c->ghost >= 4) ? 1 : 0, c->multi_tail4 ? 1 : 0, c->ghost,
+                           std::min(c->group_max, static_cast<int>(kMaxGroup)), left, g.k, kMaxGroup);   // next_multi_k's launches
+  for (int i = 0; i < g.n; ++i) g.total += g.k[i];
   return g;
 }
 static GroupPlan macro_group(const lbm_ctx* c) { return plan_group(c, c->run_steps - c->run_done); }

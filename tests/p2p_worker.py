@@ -10,7 +10,8 @@ Several cases per launch; rank 0 compares the gathered state with the oracle, bi
 case = {"nx", "ny", "K" (0 = library default), "schedule" ("edge" | "serial" | ""), "runs": [steps, ...], "p", "seed", "walls",
         "scatter" (only rank 0 holds the obstacle map), "exchange" ("p2p" | "rccl"), "step_allreduce",
         "ghost", "group" (LBM_TUNE_MACRO_GHOST / _GROUP: ghost rows kept and most launches per halo exchange; default 2 K rows, two launches),
-        "grid" ([px, py]: the tile (2-D) decomposition over px x py = N ranks instead of row blocks; peer-to-peer loop)}"""
+        "grid" ([px, py]: the tile (2-D) decomposition over px x py = N ranks instead of row blocks; peer-to-peer loop),
+        "want" ([ghost, group]: the layout every rank must run — the shape the case is named for)}"""
 import json
 import os
 import sys
@@ -60,6 +61,11 @@ def main() -> int:
             assert sim.describe()["rccl_nranks"] == size and sim.describe()["step_allreduce"] == bool(c.get("step_allreduce")), sim.describe()
         if c.get("K"):
             assert sim.partition.macro_steps == c["K"]
+        if c.get("want"):
+            assert [sim.layout["ghost"], sim.layout["group"]] == list(c["want"]), (rank, sim.layout, c)
+            if c["want"][0] > 0:                                   # ... and the context built from it runs that layout
+                info = sim.partition.tile_info()
+                assert [info["ghost"], info["group"]] == list(c["want"]), (rank, info, c)
         av = np.concatenate([sim.run(n) for n in c["runs"]])
         everyone = [None] * size
         dist.all_gather_object(everyone, av.tobytes())

@@ -666,9 +666,15 @@ def test_run_lengths_that_three_does_not_divide(lbm, oracle, digests, monkeypatc
 
 def _k_step_partitions_in_process(lbm, parts, steps, K):
     """Several K-step partitions of one grid on one GPU, ghost rows exchanged by device copies
-    (lbm_macro_exchange_local) in the order of the native loop; returns the summed per-step tot_u."""
+    (lbm_macro_exchange_local) in the order of the native loop; returns the summed per-step tot_u.
+    The groups the partitions make (steps and launches between two exchanges) must be the ones the public
+    lbm_plan_group gives for their layout: bench.py derives its launch counts from that one."""
     import torch
     size = len(parts)
+    lays = [part.tile_info() for part in parts]
+    assert all((l["macro_k"], l["ghost"], l["group"]) == (lays[0]["macro_k"], lays[0]["ghost"], lays[0]["group"]) for l in lays), lays
+    plan = lbm.plan_groups(lays[0]["macro_k"], lays[0]["ghost"], lays[0]["group"], steps)
+    seen = []
     tstream = torch.cuda.Stream(torch.device("cuda", 0))
     st = tstream.cuda_stream
     with torch.cuda.stream(tstream):
@@ -683,12 +689,15 @@ def _k_step_partitions_in_process(lbm, parts, steps, K):
                 part.macro_interior(st)
                 part.macro_edge(st)
             k = parts[0].macro_next                                              # steps until the next exchange; the same on every partition
-            assert 1 <= k <= 32 and all(part.macro_next == k for part in parts)
+            n = parts[0].macro_launches
+            assert 1 <= k <= 32 and all(part.macro_next == k and part.macro_launches == n for part in parts)
+            seen.append((k, n))
             for part in parts:
                 part.macro_finish(st)
             done += k
         sums = sum(part.step_collect(steps, st) for part in parts)
     tstream.synchronize()
+    assert seen == [(sum(g), len(g)) for g in plan], (seen, plan)
     return sums
 
 
@@ -911,7 +920,8 @@ def test_groups_of_launches_per_exchange_on_a_ring_of_one(lbm, oracle, monkeypat
 
 
 @pytest.mark.parametrize("ghost,group", GROUPINGS)
-@pytest.mark.parametrize("nx,ny,size,K", [(256, 200, 3, 4), (1000, 1000, 8, 4), (192, 99, 2, 3), (128, 260, 8, 4), (2048, 1100, 2, 4)])
+@pytest.mark.parametrize("nx,ny,size,K", [(256, 200, 3, 4), (1000, 1000, 8, 4), (192, 99, 2, 3), (128, 260, 8, 4), (2048, 1100, 2, 4),
+                                          (1024, 1024, 8, 4), (2048, 2048, 8, 4)])      # the driver's eight ranks: 24 / 6 and 32 / 8 by default
 def test_groups_of_launches_per_exchange_with_several_partitions(lbm, oracle, monkeypatch, nx, ny, size, K, ghost, group):
     """The same through the split-phase entry points (exchange of ALL ghost rows by device copies; lbm_macro_interior / _edge, then
     lbm_macro_finish, which makes the later launches of the group): uneven partitions, the tall geometry (2048 x 1100 on two ranks),
@@ -1116,10 +1126,21 @@ P2P_CASES = {
         dict(nx=512, ny=256, K=0, schedule="", runs=[20, 11], grid=[2, 2], scatter=True), dict(nx=1024, ny=64, K=0, schedule="", runs=[9, 8], grid=[4, 1]),
         dict(nx=384, ny=200, K=3, schedule="", runs=[31], grid=[2, 2], walls=True),
         dict(nx=1024, ny=512, K=0, schedule="edge", runs=[20, 11], grid=[2, 2], scatter=True)],
+    # the driver's eight row ranks (BASELINE configs 4 and 5) at each boundary of the ghost-row rule (lbm_kernels.hip macro_ghost_for):
+    # 128 rows per rank -> 24 rows, six launches per exchange; a rank below 128 rows -> every rank drops to 8 / 2; 256 rows at nx * rows =
+    # 2^19 -> 32 / 8; just below 256 rows -> 24 / 6; nx * rows above 2^19 -> 16 / 4.  "want" pins the shape each case is named for
+    8: [dict(nx=1024, ny=1024, K=0, schedule="", runs=[50, 23], want=[24, 6]),
+        dict(nx=1024, ny=1030, K=0, schedule="serial", runs=[50, 23], walls=True, want=[24, 6]),           # 129 x 6, 128 x 2 rows
+        dict(nx=1024, ny=1020, K=0, schedule="edge", runs=[50, 23], scatter=True, want=[8, 2]),           # 128 x 4, 127 x 4 rows
+        dict(nx=2048, ny=2048, K=0, schedule="edge", runs=[50, 23], p=0.01, want=[32, 8]),
+        dict(nx=2048, ny=2040, K=0, schedule="serial", runs=[50, 23], p=0.01, want=[24, 6]),              # 255 rows
+        dict(nx=2048, ny=2056, K=0, schedule="", runs=[50, 23], p=0.01, scatter=True, want=[16, 4]),      # 257 rows
+        # one-step mode: 4, 4, 4, 3, 3, 3, 3, 3 rows — the accelerate row in a 3-row last rank (d2q9-bgk.c:848-849)
+        dict(nx=64, ny=27, K=0, schedule="", runs=[25, 6], want=[0, 1])],
 }
 
 
-@pytest.mark.parametrize("ranks", [2, 3, 4])
+@pytest.mark.parametrize("ranks", [2, 3, 4, 8])
 def test_p2p_ranks_in_separate_processes_share_the_gpu(lbm, ranks):
     """The peer-to-peer loop as an N-GPU run executes it — one process per rank, each mapping its neighbours'
     grids with hipIpcOpenMemHandle — with the ranks sharing this box's one GPU (tests/p2p_worker.py).  Uneven row
@@ -1166,10 +1187,15 @@ MULTI_GPU_CASES = {
         dict(nx=256, ny=200, K=3, schedule="", runs=[20, 11], exchange="rccl", scatter=True),
         dict(nx=1000, ny=400, K=0, schedule="", runs=[16], walls=True, exchange="rccl", step_allreduce=True),
         dict(nx=37, ny=45, K=0, schedule="", runs=[19], scatter=True), dict(nx=37, ny=45, K=0, schedule="", runs=[19], exchange="rccl", step_allreduce=True)],
+    # the driver's eight ranks (BASELINE configs 4 and 5): 24 / 6 on 128 rows per rank, 16 / 4 on 257; RCCL with nranks = 8
+    8: [dict(nx=1024, ny=1024, K=0, schedule="", runs=[50, 23], want=[24, 6]),
+        dict(nx=2048, ny=2056, K=0, schedule="edge", runs=[50, 23], p=0.01, scatter=True, want=[16, 4]),
+        dict(nx=1024, ny=1024, K=0, schedule="", runs=[50, 23], walls=True, exchange="rccl", want=[24, 6]),
+        dict(nx=2048, ny=2056, K=0, schedule="", runs=[50, 23], p=0.01, exchange="rccl", step_allreduce=True, want=[16, 4])],
 }
 
 
-@pytest.mark.parametrize("ranks", [2, 3])
+@pytest.mark.parametrize("ranks", [2, 3, 8])
 def test_native_loops_with_one_gpu_per_rank(lbm, ranks):
     """Switches itself on when the box has at least `ranks` GPUs: the peer-to-peer loop and the RCCL loop (with and
     without one all-reduce per macro-step) as fresh rank processes, ONE DEVICE EACH — stores, flags and RCCL messages
@@ -1215,7 +1241,9 @@ def test_bench_on_two_gpus_harvests_every_part(lbm):
 
 @pytest.mark.parametrize("nx,ny,size,K,schedule", [(256, 200, 3, 3, "serial"), (130, 100, 2, 4, "serial"), (192, 99, 2, 3, "edge"),
                                                    # >= 2^20 cells per rank: several tall-geometry contexts (79 KB frames) in one process
-                                                   (2048, 1100, 2, 4, "serial")])
+                                                   (2048, 1100, 2, 4, "serial"),
+                                                   # the driver's eight row ranks: 24 ghost rows / six launches (128 rows each), 8 / 2 (127 rows)
+                                                   (1024, 1024, 8, 4, "serial"), (1024, 1020, 8, 4, "serial")])
 def test_p2p_partitions_in_one_process(lbm, nx, ny, size, K, schedule):
     """Several ranks of one run as contexts of ONE process (one host thread per rank, as a single-process
     multi-GPU host drives them), connected through plain pointers instead of IPC handles
@@ -1224,10 +1252,28 @@ def test_p2p_partitions_in_one_process(lbm, nx, ny, size, K, schedule):
     for), hence the fresh process with GPU_MAX_HW_QUEUES raised, as the C shim does for LBM_GPUS."""
     import sys
     from conftest import ROOT
-    env = dict(os.environ, GPU_MAX_HW_QUEUES="16", LBM_P2P_TIMEOUT_MS="10000")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "p2p_inprocess_worker.py"), str(nx), str(ny), str(size), str(K), schedule],
+    # a queue per rank plus torch's own: 2 * 8 + 4 = 20 for eight ranks, as the C shim sets it (at most 32)
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="20", LBM_P2P_TIMEOUT_MS="10000")
+    want = {(1024, 1024): ["want=24,6"], (1024, 1020): ["want=8,2"]}.get((nx, ny), [])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "p2p_inprocess_worker.py"), str(nx), str(ny), str(size), str(K), schedule, *want],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0 and "IN-PROCESS RING ok" in r.stdout, r.stderr[-3000:]
+
+
+@pytest.mark.parametrize("worker,args", [("p2p_inprocess_worker.py", ["256", "200", "3", "4", "serial", "runs=20,4200", "max_iters=31"]),
+                                         ("tile_inprocess_worker.py", ["512", "256", "2", "2", "4", "-", "-", "20,4200", "max_iters=31"])])
+def test_partitions_of_one_process_run_longer_than_their_deck(lbm, worker, args):
+    """Ranks of one process sharing the device, created for a 31-step deck, then a 20-step run and one of 4 200 steps — beyond the
+    4 096 steps the per-step sums buffers hold from the start.  Growing them must not wait for the device in the middle of the run
+    (a hipFree there blocks behind the neighbours' wait kernels until the loop's time-out): bit for bit against the oracle, the
+    per-step sums of every step, for row blocks and for a 2 x 2 tile grid."""
+    import sys
+    from conftest import ROOT
+    env = dict(os.environ, GPU_MAX_HW_QUEUES="20", LBM_P2P_TIMEOUT_MS="10000")
+    for k in ("LBM_TUNE_MACRO_K", "LBM_TUNE_MACRO_GHOST", "LBM_TUNE_MACRO_GROUP"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", worker), *args], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and ("IN-PROCESS RING ok" in r.stdout or "TILES ok" in r.stdout), (r.stdout[-500:], r.stderr[-3000:])
 
 
 TILE_CASES = [   # nx ny px py K ghost group runs [walls]
@@ -1413,7 +1459,43 @@ def test_bench_self_launch_two_ranks_on_one_gpu(lbm):
         assert small["parity_ok"] is True and small["reynolds_line_equals_reference"] is True and small["value"] > 0
 
 
-@pytest.mark.parametrize("gpus,name", [(2, "256x256_t1000"), (3, "1024x1024_t200"), (4, "128x256_t2000"), (4, "rand_64x48"), (3, "tall_8x256")])
+def test_bench_self_launch_eight_ranks_on_one_gpu(lbm):
+    """The driver's N = 8 call (BASELINE configs 4 and 5: eight row ranks), dry-run with all eight rank processes on this box's one GPU:
+    one JSON line, the peer-to-peer loop checked bit for bit against a single-GPU run, eight ranks' phases, the RCCL variants recorded
+    as not usable rather than crashing, and the shipped 1024 x 1024 deck on the same eight ranks (128 rows each: 24 ghost rows, six
+    launches per exchange) parity-checked."""
+    import json
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env.update(LBM_FORCE_DEVICE="0", LBM_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "20", "--warmup", "5", "--workload", "4096x4096",
+                        "--secondary-steps", "3000", "--full"], capture_output=True, text=True, timeout=1200, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 8 and out["steps"] == 20 and out["value"] > 0, lines[0][-3000:]
+    # Eight ranks time-sharing one GPU make every exchange wait for the others' time slices: the three small shipped decks, whole runs of
+    # 40 000 - 80 000 steps on the same ranks after everything else, do not fit the ranks' budget here (measured: not even in 395 s, where
+    # eight devices take seconds).  The line may be cut there — and only there: everything before them must have been banked.
+    assert out.get("truncated", "during: secondary: input_256x256").split("during: ")[1] in \
+        ("secondary: input_256x256", "secondary: input_128x256", "secondary: input_128x128"), out["truncated"]
+    assert out["config"]["loop"] == "p2p" and "ipc" in out["config"]["p2p"]
+    assert (out["config"]["ghost_rows"], out["config"]["launches_per_exchange"]) == (8, 2)         # 512 rows of 4096 cells: >= 2^21 per rank
+    assert out["parity_check"]["ok"] is True and out["exchange_attempts"][0] == {"exchange": "p2p", "ok": True}
+    assert len(out["phases"]["per_rank"]) == 8
+    for name in ("rccl", "rccl_step_allreduce"):
+        assert "ranks share a GPU" in out["variants"][name]["error"]
+    sec = out["secondary"]["input_1024x1024"]
+    assert sec["steps"] == 3000 and sec["p2p"]["parity_ok"] is True and sec["p2p"]["value"] > 0 and "ranks share a GPU" in sec["rccl"]["error"]
+    assert "ghost rows 24; launches per exchange 6" in sec["p2p"]["p2p"], sec["p2p"]["p2p"]          # config 4: 128 rows per rank
+
+
+@pytest.mark.parametrize("gpus,name", [(2, "256x256_t1000"), (3, "1024x1024_t200"), (4, "128x256_t2000"), (4, "rand_64x48"), (3, "tall_8x256"),
+                                       # the driver's eight ranks: 128 rows each (24 ghost rows, six launches per exchange), 32 rows each
+                                       # (K-step mode on 4 ghost rows, an exchange before every launch), 32 rows of 8 cells (one-step mode)
+                                       (8, "1024x1024_t200"), (8, "256x256_t1000"), (8, "tall_8x256")])
 def test_cli_drives_several_ranks_from_one_process(lbm, digests, tmp_path, gpus, name):
     """LBM_GPUS=N: the C shim as a single-process multi-GPU host — N ranks of the reference's decomposition, one
     host thread each, peer-to-peer halos.  Here all ranks sit on device 0 (LBM_DEVICES), the way a one-GPU box
@@ -1429,6 +1511,29 @@ def test_cli_drives_several_ranks_from_one_process(lbm, digests, tmp_path, gpus,
     assert sha256(tmp_path / "final_state.dat") == digests[name]["final_state_sha256"]
     av = lbm.checker.load_av_vels(str(tmp_path / "av_vels.dat"))
     assert np.allclose(av[np.asarray(digests[name]["av_sample_steps"])], digests[name]["av_sample_values"], rtol=5e-4)
+
+
+def test_cli_runs_the_shipped_1024_deck_on_eight_ranks_from_one_process(lbm, digests, tmp_path):
+    """BASELINE config 4 end to end: the whole shipped 1024 x 1024 deck (20 000 steps) on eight row ranks of the C shim — 128 rows
+    each, 24 ghost rows, six launches per exchange — all on device 0.  final_state.dat byte-identical to the reference binary's (as
+    test_cli_on_shipped_decks for one rank), the reference's Reynolds line, av_vels against the reference's samples."""
+    name = "1024x1024"
+    ppath, opath = deck_paths(name, digests)
+    env = dict(os.environ, LBM_GPUS="8", LBM_DEVICES=",".join(["0"] * 8), LBM_P2P_TIMEOUT_MS="20000")
+    env.pop("GPU_MAX_HW_QUEUES", None)          # the shim sets 2 * 8 + 4 = 20 for ranks that share a device
+    for k in ("LBM_TUNE_MACRO_K", "LBM_TUNE_MACRO_GHOST", "LBM_TUNE_MACRO_GROUP", "LBM_RANK_GRID"):
+        env.pop(k, None)
+    p = lbm.read_params(ppath)
+    assert {(l["macro_k"], l["ghost"], l["group"]) for l in (lbm.rank_layout(p, 8, r) for r in range(8))} == {(4, 24, 6)}
+    r = subprocess.run([lbm.CLI_PATH, ppath, opath], cwd=tmp_path, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr
+    out = r.stdout.splitlines()
+    assert out[0] == "==done==" and out[1] == digests[name]["reynolds_line"]
+    assert "(8 GPUs, peer-to-peer halos)" in out[5]
+    assert sha256(tmp_path / "final_state.dat") == digests[name]["final_state_sha256"]
+    av = lbm.checker.load_av_vels(str(tmp_path / "av_vels.dat"))
+    assert av.size == digests[name]["steps"]
+    assert np.allclose(av[np.asarray(digests[name]["av_sample_steps"])], digests[name]["av_sample_values"], rtol=4e-3)
 
 
 @pytest.mark.parametrize("gpus,grid,name", [(4, "2x2", "1024x1024_t200"), (2, "2x1", "256x256_t1000"), (2, "1x2", "256x256_t1000"), (8, "4x2", "1024x1024_t200"),

@@ -688,6 +688,28 @@ def test_groups_of_launches_between_exchanges(lbm, monkeypatch):
     assert lbm.rank_layout(p, 8, 3)["ghost"] == 32                                                  # kMaxGhost
 
 
+def test_eight_rank_gpu_cases_run_the_layouts_they_are_named_for(lbm, monkeypatch):
+    """The GPU suite's eight-rank cases pin the ghost rows / launches per exchange they are meant to exercise ("want"): here, on any
+    machine, every rank's lbm_rank_layout under the case's knobs must give exactly that, the same on all eight ranks — so that a case
+    cannot drift off the boundary of the ghost-row rule it is named for without a GPU noticing."""
+    from test_gpu_parity import MULTI_GPU_CASES, P2P_CASES
+    cases = [c for c in P2P_CASES[8] + MULTI_GPU_CASES[8] if "want" in c]
+    assert len(cases) == len(P2P_CASES[8]) + len(MULTI_GPU_CASES[8])
+    # every boundary of the rule is hit: 24 / 6, 8 / 2, 32 / 8, 16 / 4 and one-step mode
+    assert {tuple(c["want"]) for c in P2P_CASES[8]} == {(24, 6), (8, 2), (32, 8), (16, 4), (0, 1)}
+    for c in cases:
+        for key, val in (("LBM_TUNE_MACRO_K", c.get("K", 0)), ("LBM_TUNE_MACRO_GHOST", c.get("ghost", "")), ("LBM_TUNE_MACRO_GROUP", c.get("group", ""))):
+            if val:
+                monkeypatch.setenv(key, str(val))
+            else:
+                monkeypatch.delenv(key, raising=False)
+        p = lbm.Params(c["nx"], c["ny"], sum(c["runs"]), 4, 0.1, 0.01, 1.7)
+        lays = [lbm.rank_layout(p, 8, r) for r in range(8)]
+        assert all((l["macro_k"], l["ghost"], l["group"]) == (lays[0]["macro_k"], lays[0]["ghost"], lays[0]["group"]) for l in lays), (c, lays)
+        assert [lays[0]["ghost"], lays[0]["group"]] == c["want"], (c, lays[0])
+        assert sum(l["ny_local"] for l in lays) == c["ny"]
+
+
 def test_tile_layout_is_one_decision_for_all_ranks(lbm, monkeypatch):
     """The tile (2-D) decomposition (the reference's report discusses it, d2q9-bgk.c:834-862 splits rows only):
     rows by the reference's rule over py, columns in whole x-pairs over px; the blocks tile the grid exactly; K, ghost rows, ghost

@@ -1,9 +1,10 @@
 """The ranks of a px x py TILE (2-D) decomposition as contexts of ONE process, one host thread per rank (test helper, run as a
 fresh process by tests/test_gpu_parity.py with GPU_MAX_HW_QUEUES raised, as tests/p2p_inprocess_worker.py).  Every rank keeps ghost
 rows and ghost columns; per exchange the columns travel west / east first, then whole storage rows south / north.
-argv: nx ny px py K ghost group runs(comma separated) [walls] [flags=<lbm_create flags>] [sched=edge|serial] [yghost]
+argv: nx ny px py K ghost group runs(comma separated) [walls] [flags=<lbm_create flags>] [sched=edge|serial] [yghost] [max_iters=<n>]
 (yghost: LBM_TUNE_TILE_GHOST_ROWS=1 — column blocks (py = 1) keep ghost rows and push rows onto themselves instead of wrapping in the launch;
-ranks of one process on one device run the serial schedule whatever is asked for; a 1 x 1 grid takes the edge-stream schedule when asked)"""
+ranks of one process on one device run the serial schedule whatever is asked for; a 1 x 1 grid takes the edge-stream schedule when asked;
+max_iters: the deck's step count the contexts are created with — below the longest run, the per-step sums buffers grow between runs)"""
 import os
 import sys
 
@@ -24,6 +25,7 @@ def main() -> int:
     if "yghost" in sys.argv[9:]:
         os.environ["LBM_TUNE_TILE_GHOST_ROWS"] = "1"
     sched = next((a.split("=")[1] for a in sys.argv[9:] if a.startswith("sched=")), "")
+    max_iters = next((int(a.split("=")[1]) for a in sys.argv[9:] if a.startswith("max_iters=")), sum(runs))
     os.environ.pop("LBM_P2P_SCHEDULE", None)
     if sched:
         os.environ["LBM_P2P_SCHEDULE"] = sched
@@ -37,7 +39,7 @@ def main() -> int:
     import oracle_lib
     steps = sum(runs)
     size = px * py
-    p = lbm.Params(nx, ny, steps, 4, 0.1, 0.01, 1.7)
+    p = lbm.Params(nx, ny, max_iters, 4, 0.1, 0.01, 1.7)
     obst = lbm.synthetic_obstacles(nx, ny, 0.03, nx * 5 + ny, walls)
     free = lbm.count_free_cells(obst)
     lays = [lbm.tile_layout(p, px, py, r, flags) for r in range(size)]
@@ -69,6 +71,7 @@ def main() -> int:
     ref_cells, _, ref_exact = oracle_lib.run(p, obst, steps, nthreads=4)
     assert np.array_equal(cells.view(np.uint32), ref_cells.view(np.uint32)), "populations differ from the oracle"
     av = np.concatenate([o[0] for o in out]) * np.float64(np.float32(1.0) / np.float32(free))
+    assert av.shape == (steps,)
     tol = 2e-6 if flags & lbm._capi.FLAG_FAST_AVVELS else 1e-12          # (float terms: an ulp of the float av_vels is)
     assert np.max(np.abs(av - ref_exact) / ref_exact) < tol, np.max(np.abs(av - ref_exact) / ref_exact)
     # the same state on one context: digests add up, observables and the velocity sum agree
