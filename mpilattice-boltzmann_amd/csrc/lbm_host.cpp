@@ -16,6 +16,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_internal.h"
+#include "lbm_knobs.h"
 
 namespace {
 thread_local std::string g_error;
@@ -281,8 +282,8 @@ int write_final_state_impl(const char* path, const lbm_params* p, const int* obs
 
   // blocks of rows (~4 MB of text each), `workers` of them formatted concurrently, written in order
   const int rows_per_block = std::max(1, static_cast<int>((4u << 20) / (static_cast<size_t>(nx) * 90 + 1)));
-  unsigned workers = std::thread::hardware_concurrency();
-  if (const char* e = std::getenv("LBM_WRITE_THREADS")) workers = static_cast<unsigned>(std::atoi(e));
+  const int want = knobs_from_env().write_threads;
+  unsigned workers = want != kKnobUnset ? static_cast<unsigned>(want) : std::thread::hardware_concurrency();
   workers = std::max(1u, std::min(workers, 16u));
   std::vector<std::string> text(workers);
   bool ok = true;

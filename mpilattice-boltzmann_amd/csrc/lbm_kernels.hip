@@ -36,7 +36,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -49,6 +48,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_internal.h"
+#include "lbm_knobs.h"
 #include "kernels/common.h"
 #include "kernels/step.h"
 #include "kernels/tile.h"
@@ -82,13 +82,7 @@ size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 // Plane stride: rows*nx floats + guard for the dword-shifted loads at both ends, rounded to 256 B,
 // then skewed by an odd number of 256-B units so the 9 planes (and the two grids) do not all start
 // on the same HBM channel when rows*nx is a large power of two.
-int tune_env(const char* name, int dflt)
-{
-  const char* v = std::getenv(name);
-  return (v && *v) ? std::atoi(v) : dflt;
-}
-
-size_t plane_stride_floats(size_t ncells)
+size_t plane_stride_floats(size_t ncells, int skew)
 {
   size_t s = round_up(ncells + 64, 64);
   if ((s / 64) % 2 == 0) s += 64;
@@ -98,13 +92,14 @@ size_t plane_stride_floats(size_t ncells)
   // 285.1 / 286.6; K = 3 (the tails) 384.6 & 329.5 / 341.1 / 324.0 / 317.9 / 339.8 / 339.7 & 348.5 / 323.5 / 335.4 / 333.7 — 33 and 34 are the
   // two bad values for the tall tiles, 24 is best for both; other sizes (4096 x 4096 ... 16384 x 4096, partitions) do not care
   // (profiles/r03/ab_skew_scan.txt, ab_skew_sizes.txt).
-  if (ncells >= (1u << 20)) s += 64 * static_cast<size_t>(tune_env("LBM_TUNE_SKEW", 24));
+  if (ncells >= (1u << 20)) s += 64 * static_cast<size_t>(skew);
   return s;
 }
 
 }  // namespace
 
 struct lbm_ctx {
+  Knobs knobs;                       // the environment knobs as lbm_create* read them (lbm_knobs.h)
   lbm_params p{};
   int free_cells = 0;
   float free_cells_inv = 0.f;
@@ -194,11 +189,11 @@ struct lbm_ctx {
 
 namespace {
 
-int pick_iters(long long quads)
+// max_blocks (LBM_TUNE_MAXBLOCKS): measured on 8192x8192, 16384 blocks x 4 chunks ~7 % faster than 4096 x 16
+int pick_iters(long long quads, int max_blocks)
 {
   // keep the grid at <= ~4096 blocks (16 per CU): fewer, longer blocks and a short partial vector
   long long chunks = (quads + kBlock - 1) / kBlock;
-  const int max_blocks = tune_env("LBM_TUNE_MAXBLOCKS", 16384);   // measured on 8192x8192: 16384 blocks x 4 chunks ~7 % faster than 4096 x 16
   int iters = 1;
   while (chunks / iters > max_blocks && iters < 1024) iters *= 2;
   return iters;
@@ -398,9 +393,9 @@ void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int 
     for (int i = 0; i < nrect; ++i) { a.rect[i] = rects[i]; blocks += rects[i].count; }
   }
   // measured on 8192x8192, K=2: 515 us/step with the XCD-contiguous tile order, 549 without
-  a.xcd_remap = (tune_env("LBM_TUNE_MULTI_REMAP", 1) && blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
+  a.xcd_remap = (c->knobs.multi_remap && blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
   a.nblocks = blocks;
-  if (c->ghost_x > 0 && tune_env("LBM_TUNE_MULTI_REMAP", 1) && blocks >= 64 && blocks % 8 != 0 && tune_env("LBM_TUNE_TILE_PAD_GRID", 1)) {
+  if (c->ghost_x > 0 && c->knobs.multi_remap && blocks >= 64 && blocks % 8 != 0 && c->knobs.tile_pad_grid) {
     blocks = (blocks + 7) / 8 * 8;                              // tile ranks: pad the grid (the form drops the extra blocks) and keep the XCD-contiguous order
     a.xcd_remap = 1;
   }
@@ -518,7 +513,7 @@ int fold_last(lbm_ctx* c, hipStream_t s, bool final = false)
   const double* part = c->partials[c->parity ^ 1];
   // one block folds 23 K partials (4 vectors of an 8192 x 1024-row rank's 5760 tiles) in 31 us — at the end of EVERY run, on the critical
   // path of a 20-step region; sliced over 64 blocks per vector and folded again it is two launches of a few us (threshold was 8192)
-  if (c->n_prev >= tune_env("LBM_TUNE_FOLD_SLICED_MIN", 1024)) {
+  if (c->n_prev >= c->knobs.fold_sliced_min) {
     hipLaunchKernelGGL(lbm_fold_slices_kernel, dim3(kFoldSlices, c->n_prev_vecs), dim3(kBlock), 0, s, part, c->n_prev, c->fold_scratch);
     hipLaunchKernelGGL(lbm_fold_kernel, dim3(1), dim3(kBlock), 0, s, c->fold_scratch, kFoldSlices, c->n_prev_vecs, c->sums, c->counter, final ? 1 : 0);
   } else {
@@ -530,25 +525,6 @@ int fold_last(lbm_ctx* c, hipStream_t s, bool final = false)
   c->counter_clean = final;
   c->counter_clean_stream = s;
   return 0;
-}
-
-// Wait for the stream's work: hipStreamSynchronize, optionally preceded by LBM_SPIN_WAIT_US microseconds of polling
-// (hipStreamQuery).  A blocked host thread is woken some microseconds after the last kernel ends, which a 1 ms run of 20
-// steps could notice; measured in one process on a 1-rank ring of 8192 x 1024 rows (scripts/ab_ring.py, 60 rounds of
-// 20-step runs): 52.70 us/step blocking, 52.63 polling — no difference, so the default is 0 (no core kept spinning).
-hipError_t stream_wait(hipStream_t s)
-{
-  const int spin_us = tune_env("LBM_SPIN_WAIT_US", 0);          // read per call: scripts/ab_ring.py alternates it in one process
-  if (spin_us > 0) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (;;) {
-      const hipError_t e = hipStreamQuery(s);
-      if (e != hipErrorNotReady) return e;
-      if (std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(spin_us)) break;
-    }
-    (void)hipGetLastError();             // hipErrorNotReady is not an error
-  }
-  return hipStreamSynchronize(s);
 }
 
 // Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
@@ -610,16 +586,15 @@ static bool macro_eligible(const lbm_params* p, int rows, unsigned flags)
   return !(flags & LBM_FLAG_ONE_STEP) && rows >= 2 * kMTY && fits_u32 && p->nx < (1 << 23) && (p->nx % kMTX == 0 || (p->nx % 2 == 0 && p->nx >= 2 * kMTX));
 }
 
-// K for partitions of at most `max_cells` cells.  Measured on a 1-rank ring with the packed exchange,
+// K of the K-step partitions, whatever their size (LBM_TUNE_MACRO_K overrides).  Measured on a 1-rank ring with the packed exchange,
 // us/step for K = 2 / 3 / 4 (one-step loop):
 //   8192x4096 rows 243 / 182 / 199   8192x2048 rows 122 / 92.6 / 103   8192x1024 rows 66.2 / 52.5 / 55.9 (116)
 //   1024x128 rows 26.1 / 18.8 / 14.7 (37)
 // Round 3: with the 4-step launch on 64 x 13 tiles (three blocks per CU, kernels/multi.h) K = 4 wins at every size — 1-rank
 // p2p rings, us/step for K = 3 / K = 4: 8192x4096 178.9 / 166.2, 8192x1024 51.3 / 48.5, 1024x128 4.40 / 4.04.
-static int macro_k_for(size_t max_cells)
+static int macro_k_for(const Knobs& knobs)
 {
-  (void)max_cells;
-  return std::min(std::max(tune_env("LBM_TUNE_MACRO_K", 4), 0), kMaxMultiSteps);
+  return std::min(std::max(knobs.macro_k, 0), kMaxMultiSteps);
 }
 
 // Ghost rows kept on each side of a K-step partition, and with them how often it exchanges: the launches between two exchanges (a
@@ -637,7 +612,7 @@ static int macro_k_for(size_t max_cells)
 // One answer for all ranks: from nx and the smallest / largest row count of the run.  LBM_TUNE_MACRO_GHOST overrides (0 or anything
 // below K: K rows, one launch per exchange).  The exchange moves the rows the NEXT group needs (peer-to-peer loop) or all `ghost`
 // rows (RCCL loop).
-static int macro_ghost_for(int k, int nx, int rows_min, int rows_max, bool row_blocks = true)
+static int macro_ghost_for(const Knobs& knobs, int k, int nx, int rows_min, int rows_max, bool row_blocks = true)
 {
   if (k <= 0) return 0;
   const int classic = k == 3 ? 4 : k, two = k == 3 ? 8 : 2 * k;
@@ -650,14 +625,14 @@ static int macro_ghost_for(int k, int nx, int rows_min, int rows_max, bool row_b
   // for ranks of at most 2^19 cells in rows of at most 2048 cells
   if (row_blocks && nx <= 2048 && static_cast<size_t>(nx) * rows_max <= (size_t(1) << 19) && rows_min >= 128)     // (tile ranks: lbm_tile_layout_of has its own rule)
     by_size = std::max(by_size, std::min((rows_min >= 256 ? 32 : 24) / k * k, static_cast<int>(kMaxGhost)));
-  return std::min(std::max(tune_env("LBM_TUNE_MACRO_GHOST", by_size), k), kMaxGhost);
+  return std::min(std::max(knob_or(knobs.macro_ghost, by_size), k), kMaxGhost);
 }
 
 // Most launches per exchange: what the ghost rows allow (LBM_TUNE_MACRO_GROUP caps it; 1 = rounds 1-3's loop on any number of ghost rows).
-static int macro_group_for(int k, int ghost)
+static int macro_group_for(const Knobs& knobs, int k, int ghost)
 {
   if (k <= 0) return 1;
-  return std::min(std::max(tune_env("LBM_TUNE_MACRO_GROUP", std::max(ghost / k, 1)), 1), kMaxGroup);
+  return std::min(std::max(knob_or(knobs.macro_group, std::max(ghost / k, 1)), 1), kMaxGroup);
 }
 
 // Geometry of lbm_multi_kernel's launches by partition size.  Width: 64 x 16 tiles for the bandwidth-bound grids; 32 x 16 where 64 x 16
@@ -671,13 +646,12 @@ static int macro_group_for(int k, int ghost)
 // one process can share a hardware queue, which made the tall geometry look 20 % worse in a same-process A/B): standard / tall, us/step
 // at 200 and 20 steps per run: 8192 x 1024 rows 46.5 / 45.5 and 48.2 / 48.1, 8192 x 2048 rows 86.9 / 82.4 and 88.9 / 84.2
 // (profiles/r03/ab_fused_schedule.txt).
-static int pick_geom(size_t ncells)
+static int pick_geom(const Knobs& knobs, size_t ncells)
 {
-  const int by_size = ncells <= static_cast<size_t>(tune_env("LBM_TUNE_NARROW_TILE_MAX", 1 << 17)) ? kMTXNarrow : kMTX;
-  const int t = tune_env("LBM_TUNE_MULTI_TILE", by_size);
-  int g = t == kMTXNarrow ? kGeomNarrow : ncells >= static_cast<size_t>(tune_env("LBM_TUNE_TALL_TILE_MIN", 1 << 20)) ? kGeomTall : kGeomStd;
-  const int forced = tune_env("LBM_TUNE_MULTI_GEOM", -1);
-  if (forced >= kGeomStd && forced <= kGeomTall) g = forced;
+  const int by_size = ncells <= static_cast<size_t>(knobs.narrow_tile_max) ? kMTXNarrow : kMTX;
+  const int t = knob_or(knobs.multi_tile, by_size);
+  int g = t == kMTXNarrow ? kGeomNarrow : ncells >= static_cast<size_t>(knobs.tall_tile_min) ? kGeomTall : kGeomStd;
+  if (knobs.multi_geom >= kGeomStd && knobs.multi_geom <= kGeomTall) g = knobs.multi_geom;
   return g;
 }
 
@@ -719,7 +693,7 @@ static void pack_obstacle_bits(std::vector<uint32_t>& bits, int rows, int nx, Ro
 // (lbm_create_global); >= 0: decided by the caller for the whole run (lbm_rank_layout).
 struct TileSpec { int px, py, rx, ry, x0, nxl, ghost_x, nx_global, ghost_rows; };    // lbm_create_tile: `p->nx` is then the storage row width nxl + 2 ghost_x
 
-static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const int* obstacles_rows,
+static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, int free_cells, const int* obstacles_rows,
                        const int* obstacles_global, const int* obstacles_window, int forced_k, int forced_ghost, int y0, int ny_local,
                        int device, unsigned flags, const TileSpec* tile = nullptr)
 {
@@ -741,6 +715,7 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
 
   HIP_TRY(hipSetDevice(device));
   lbm_ctx* c = new lbm_ctx();
+  c->knobs = knobs;
   c->p = *p;
   c->free_cells = free_cells;
   c->free_cells_inv = 1.0f / free_cells;                                    // d2q9-bgk.c:950
@@ -754,7 +729,7 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
   c->fast_avvels = (flags & LBM_FLAG_FAST_AVVELS) != 0;
   c->multi_terms = c->fast_avvels ? kTermsFloat : (flags & LBM_FLAG_EXACT_AVVELS) ? kTermsDouble : kTermsCompensated;
   {
-    const int t = tune_env("LBM_TUNE_TERMS", -1);            // 0 double, 1 float, 2 compensated (A/B runs of the DEFAULT form:
+    const int t = knobs.terms;                                // 0 double, 1 float, 2 compensated (A/B runs of the DEFAULT form:
     if (t >= 0 && t <= 2 && !(flags & (LBM_FLAG_EXACT_AVVELS | LBM_FLAG_FAST_AVVELS))) c->multi_terms = t;   // a form asked for by flag stays)
   }
   c->accel_row = accel_row;
@@ -773,14 +748,14 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
     }
     c->multi_K = forced_k; c->ghost = forced_ghost;
     c->ghost_rows = (tile && !tile->ghost_rows) ? 0 : forced_ghost;
-    c->group_max = macro_group_for(forced_k, forced_ghost);
+    c->group_max = macro_group_for(knobs, forced_k, forced_ghost);
   } else if (forced_k < 0 && !self_periodic && obstacles_global && macro_eligible(p, ny_local, flags)) {
-    const int k = macro_k_for(c->ncells);
-    if (k > 0) { c->multi_K = k; c->ghost = c->ghost_rows = macro_ghost_for(k, p->nx, ny_local, ny_local); c->group_max = macro_group_for(k, c->ghost); }
+    const int k = macro_k_for(knobs);
+    if (k > 0) { c->multi_K = k; c->ghost = c->ghost_rows = macro_ghost_for(knobs, k, p->nx, ny_local, ny_local); c->group_max = macro_group_for(knobs, k, c->ghost); }
   }
-  c->multi_tail4 = tune_env("LBM_TUNE_MULTI_TAIL4", 1) != 0;
+  c->multi_tail4 = knobs.multi_tail4 != 0;
   c->ncells_storage = static_cast<size_t>(p->nx) * (ny_local + 2 * c->ghost_rows);
-  c->ps = plane_stride_floats(c->ncells_storage);
+  c->ps = plane_stride_floats(c->ncells_storage, knobs.skew);
   c->grid_floats = 9 * c->ps + 128;
   // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache
   const size_t state_bytes = 2 * 9 * c->ncells * sizeof(float);
@@ -789,7 +764,7 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
   if (flags & LBM_FLAG_NO_NT_STORES) c->nt_stores = false;
   // narrow form for latency-bound grids (measured cross-over) and for nx % 4 != 0
   // (128x128: 3.5 vs 4.4 us/step, 256x256: 4.1 vs 4.6, 512x512: 7.3 vs 6.2 -> cross-over at 64 K cells)
-  const size_t narrow_max = static_cast<size_t>(tune_env("LBM_TUNE_NARROW_MAX", 65536));
+  const size_t narrow_max = static_cast<size_t>(knobs.narrow_max);
   c->lane_cells = (p->nx % kCellsPerLane != 0 || c->ncells <= narrow_max) ? 1 : kCellsPerLane;
 #if LBM_EXPERIMENTS
   c->lds_kernel = (flags & LBM_FLAG_KERNEL_LDS) != 0 && c->lane_cells == kCellsPerLane;
@@ -823,7 +798,7 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
     HIP_TRY_C(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(float) * c->grid_floats, c->stream));
     c->grid[g] = c->grid_alloc[g] + 64;
   }
-  if (tune_env("LBM_DEBUG_ADDR", 0))      // placement experiments (scripts/experiments/alloc_order.py)
+  if (knobs.debug_addr)      // placement experiments (scripts/experiments/alloc_order.py)
     std::fprintf(stderr, "lbm_create: grids at %p %p (%zu bytes each, plane stride %zu floats)\n", static_cast<void*>(c->grid_alloc[0]),
                  static_cast<void*>(c->grid_alloc[1]), sizeof(float) * c->grid_floats, c->ps);
   // obstacle bitfield
@@ -853,10 +828,10 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
   // launch geometry + partial buffers
   const long long qrow = p->nx / c->lane_cells;
   const long long qfull = qrow * ny_local;
-  c->iters_full = pick_iters(qfull);
+  c->iters_full = pick_iters(qfull, knobs.maxblocks);
   c->n_part_full = blocks_for(qfull, c->iters_full);
   const long long qint = ny_local > 2 ? qrow * (ny_local - 2) : 0;
-  c->iters_interior = pick_iters(qint > 0 ? qint : 1);
+  c->iters_interior = pick_iters(qint > 0 ? qint : 1, knobs.maxblocks);
   c->n_part_interior = qint > 0 ? blocks_for(qint, c->iters_interior) : 0;
   c->n_part_boundary = blocks_for(ny_local > 1 ? 2 * qrow : qrow, 1);
   c->partials_cap = std::max(c->n_part_full, c->n_part_interior + c->n_part_boundary) + 1;
@@ -866,22 +841,22 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
     // geometry by size, measured on MI355X (us/step for <8,4> / <8,8> / <16,4> / <16,8>; one-step kernels
     // 3.4 / 3.5 / 4.0):  128x128 1.7 / 1.4 / 1.8 / 1.6 | 128x256 2.2 / 1.8 / 1.9 / 1.7 | 256x256 3.4 / 3.0 / 2.2 / 1.9
     const int by_size = c->ncells <= 16384 ? 88 : 168;
-    const int geom = tune_env("LBM_TUNE_TILE_GEOM", by_size);   // T*10 + H
+    const int geom = knob_or(knobs.tile_geom, by_size);   // T*10 + H
     c->tile_T = geom / 10; c->tile_H = geom % 10;
     if (!((c->tile_T == 16 || c->tile_T == 8) && (c->tile_H == 8 || c->tile_H == 4))) { c->tile_T = 16; c->tile_H = 4; }
   }
   // measured whole-deck times (s) for 0 / 256 / 512: 128x128 0.0648 / 0.0576 / 0.0565, 128x256 0.0746 / 0.0747 / 0.0712,
   // 256x256 0.1598 / 0.1570 / 0.1532
-  c->tile_single_max = tune_env("LBM_TUNE_TILE_SINGLE_MAX", 512);
+  c->tile_single_max = knobs.tile_single_max;
   c->n_tiles = (p->nx % c->tile_T == 0 && ny_local % c->tile_T == 0) ? (p->nx / c->tile_T) * (ny_local / c->tile_T) : 0;
   c->tile_kernel = self_periodic && c->n_tiles > 0 &&
-                   c->ncells <= static_cast<size_t>(tune_env("LBM_TUNE_TILE_MAX", 131072));  // us/step here vs lbm_multi_kernel<3>: 256x256 1.9 / 3.1, 512x256 2.8 / 3.2, 384x384 3.6 / 3.2, 512x512 4.5 / 3.3
+                   c->ncells <= static_cast<size_t>(knobs.tile_max);  // us/step here vs lbm_multi_kernel<3>: 256x256 1.9 / 3.1, 512x256 2.8 / 3.2, 384x384 3.6 / 3.2, 512x512 4.5 / 3.3
   if (c->ghost > 0) {
     const size_t pack_floats = static_cast<size_t>(2) * 9 * std::max(c->ghost_rows, 1) * p->nx;
     for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack[i], sizeof(float) * pack_floats));
     c->tile_kernel = false;
-    c->multi_geom = pick_geom(c->ncells);
-    if (tile && c->ghost_rows == 0 && c->multi_geom == kGeomTall && tune_env("LBM_TUNE_MULTI_GEOM", -1) < 0) {
+    c->multi_geom = pick_geom(knobs, c->ncells);
+    if (tile && c->ghost_rows == 0 && c->multi_geom == kGeomTall && knobs.multi_geom < 0) {
       // A column block's launches all cover exactly its ny rows: where 23-row tiles fit them badly the last tile row is mostly waste — 256 rows: 12
       // tile rows cover 276 (7.8 % over) against 260 on 13-row tiles; 128 rows: 138 against 130 — and the standard geometry wins by 10 % (us/step
       // tall / standard: 4096 x 256 8.96 / 8.11, 8192 x 128 9.40 / 8.37; 512 and 1024 rows fit: 2048 x 512 7.82 / 8.25, 1024 x 1024 8.20 / 8.60, 2048 x 1024
@@ -904,8 +879,8 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
     // round 3, 4-step launch on 64 x 13 tiles: K = 3 / K = 4 8192x8192 346.6 / 324.0, 4096x4096 87.2 / 78.4, 2048x2048 24.0 / 21.6,
     // 1536x1536 14.2 / 13.8, 1024x1024 8.16 / 7.07, 768x768 5.39 / 4.63, 1024x512 4.51 / 4.72, 512x1024 4.39 / 4.62, 640x640 4.01 / 4.13,
     // 512x512 3.11 / 3.45 -> K = 4 from 768 x 768 cells up (profiles/r03/ab_k3_k4.txt, ab_k3_k4_threshold.txt)
-    c->multi_K = std::min(std::max(tune_env("LBM_TUNE_MULTI_K", c->ncells >= size_t(768) * 768 ? 4 : 3), 0), kMaxMultiSteps);
-    c->multi_geom = pick_geom(c->ncells);
+    c->multi_K = std::min(std::max(knob_or(knobs.multi_k, c->ncells >= size_t(768) * 768 ? 4 : 3), 0), kMaxMultiSteps);
+    c->multi_geom = pick_geom(knobs, c->ncells);
     c->multi_tx = geom_tx(c->multi_geom);
     HIP_TRY_C(raise_multi_lds_limits_for(c->multi_geom));
     c->multi_tiles_x = (p->nx + c->multi_tx - 1) / c->multi_tx;
@@ -914,12 +889,12 @@ static int create_impl(lbm_ctx** out, const lbm_params* p, int free_cells, const
     // streaming form of the 3-step launch (kernels/sweep.h): strips of 64 columns, segments of rows so that the launch is
     // about one round of two blocks per CU (8192 x 8192: 128 strips x 4 segments of 2048 rows = 512 blocks).
     // LBM_TUNE_SWEEP = R (rows per tick: 4 or 5); 0 = off (the default: measured 10-20 % slower than lbm_multi_kernel<3>)
-    const int want = tune_env("LBM_TUNE_SWEEP", 0);
+    const int want = knobs.sweep;
     if (want > 0 && c->multi_K >= 3 && p->nx % kSTX == 0 && ny_local >= 64) {
       c->multi_K = 3;                                        // the sweep makes 3-step launches; tails are lbm_multi_kernel's
       const int strips = p->nx / kSTX;
-      c->sweep_mode = std::min(std::max(tune_env("LBM_TUNE_SWEEP_MODE", 2), 0), 2);
-      const int target_blocks = tune_env("LBM_TUNE_SWEEP_BLOCKS", c->sweep_mode == 0 ? 512 : 768);
+      c->sweep_mode = std::min(std::max(knobs.sweep_mode, 0), 2);
+      const int target_blocks = knob_or(knobs.sweep_blocks, c->sweep_mode == 0 ? 512 : 768);
       int nseg = std::max(1, (target_blocks + strips / 2) / strips);
       int seg_rows = (ny_local + nseg - 1) / nseg;
       seg_rows = std::max(seg_rows, 32);
@@ -967,18 +942,18 @@ extern "C" {
 int lbm_create(lbm_ctx** out, const lbm_params* p, int free_cells, const int* obstacles_rows, int y0,
                int ny_local, int device, unsigned flags)
 {
-  return create_impl(out, p, free_cells, obstacles_rows, nullptr, nullptr, 0, 0, y0, ny_local, device, flags);
+  return create_impl(out, knobs_from_env(), p, free_cells, obstacles_rows, nullptr, nullptr, 0, 0, y0, ny_local, device, flags);
 }
 
 int lbm_create_global(lbm_ctx** out, const lbm_params* p, int free_cells, const int* obstacles_all, int y0,
                       int ny_local, int device, unsigned flags)
 {
   if (!obstacles_all || !p || y0 < 0) { lbm_internal::set_error("lbm_create_global: bad argument"); return 1; }
-  return create_impl(out, p, free_cells, obstacles_all + static_cast<size_t>(y0) * p->nx, obstacles_all, nullptr, -1, 0, y0, ny_local, device, flags);
+  return create_impl(out, knobs_from_env(), p, free_cells, obstacles_all + static_cast<size_t>(y0) * p->nx, obstacles_all, nullptr, -1, 0, y0, ny_local, device, flags);
 }
 
 // One mode and one K for every rank of a run, from global quantities only (see the header).
-int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
+static int rank_layout(const Knobs& knobs, const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
 {
   if (!p || !out || nranks < 1 || rank < 0 || rank >= nranks) { lbm_internal::set_error("lbm_rank_layout: bad argument"); return 1; }
   if (p->nx < 1 || p->ny < 3 || p->ny < nranks) { lbm_internal::set_error("lbm_rank_layout: grid too small for this many ranks"); return 1; }
@@ -991,10 +966,15 @@ int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, l
   out->macro_k = 0;
   const bool partitioned = nranks > 1 || (flags & LBM_FLAG_FORCE_HALO);
   if (partitioned && macro_eligible(p, lo, flags) && macro_eligible(p, hi, flags))
-    out->macro_k = macro_k_for(static_cast<size_t>(p->nx) * hi);
-  out->ghost = macro_ghost_for(out->macro_k, p->nx, lo, hi);
-  out->group = macro_group_for(out->macro_k, out->ghost);
+    out->macro_k = macro_k_for(knobs);
+  out->ghost = macro_ghost_for(knobs, out->macro_k, p->nx, lo, hi);
+  out->group = macro_group_for(knobs, out->macro_k, out->ghost);
   return 0;
+}
+
+int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
+{
+  return rank_layout(knobs_from_env(), p, nranks, rank, flags, out);
 }
 
 int lbm_create_rank(lbm_ctx** out, const lbm_params* p, int free_cells, const int* obstacle_window, int nranks,
@@ -1002,15 +982,16 @@ int lbm_create_rank(lbm_ctx** out, const lbm_params* p, int free_cells, const in
 {
   lbm_layout lay;
   if (!obstacle_window) { lbm_internal::set_error("lbm_create_rank: null argument"); return 1; }
-  if (lbm_rank_layout(p, nranks, rank, flags, &lay)) return 1;
+  const Knobs knobs = knobs_from_env();
+  if (rank_layout(knobs, p, nranks, rank, flags, &lay)) return 1;
   const int* rows = obstacle_window + static_cast<size_t>(lay.ghost) * p->nx;          // the owned rows inside the window
-  return create_impl(out, p, free_cells, rows, nullptr, obstacle_window, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, device, flags);
+  return create_impl(out, knobs, p, free_cells, rows, nullptr, obstacle_window, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, device, flags);
 }
 
 // ---- tile (2-D) decomposition: px x py ranks, rank = ry * px + rx ------------------------------------------------------------
 // Rows by the reference's rule over py (d2q9-bgk.c:834-862), columns by lbm_decompose_columns over px.  Always K-step mode: ghost rows
 // as a row partition of the same cells would keep, ghost columns the same number rounded up to even (x-pairs).
-int lbm_tile_layout_of(const lbm_params* p, int px, int py, int rank, unsigned flags, lbm_tile_layout* out)
+static int tile_layout_of(const Knobs& knobs, const lbm_params* p, int px, int py, int rank, unsigned flags, lbm_tile_layout* out)
 {
   if (!p || !out || px < 1 || py < 1 || rank < 0 || rank >= px * py) { lbm_internal::set_error("lbm_tile_layout_of: bad argument"); return 1; }
   if (p->nx < 1 || p->ny < 3 || p->ny < py) { lbm_internal::set_error("lbm_tile_layout_of: grid too small for this many ranks"); return 1; }
@@ -1024,16 +1005,16 @@ int lbm_tile_layout_of(const lbm_params* p, int px, int py, int rank, unsigned f
   out->px = px; out->py = py; out->rx = rank % px; out->ry = rank / px;
   out->x0 = xdis[out->rx]; out->nx_local = nxl[out->rx];
   out->y0 = ydis[out->ry]; out->ny_local = nyl[out->ry];
-  const int k = macro_k_for(static_cast<size_t>(chi) * rhi);
-  int ghost = macro_ghost_for(k, chi, rlo, rhi, /*row_blocks=*/false);
+  const int k = macro_k_for(knobs);
+  int ghost = macro_ghost_for(knobs, k, chi, rlo, rhi, /*row_blocks=*/false);
   // Column blocks (py = 1) below the edge-stream size: 32 ghost columns, eight launches per exchange.  Their ghost depth costs columns only (no
   // launch advances ghost rows), and their launches are bound by latency, not by the cells they compute: us/step for 16 / 24 / 32 ghost columns
   // 2048 x 512 8.05 / 8.00 / 7.85, 4096 x 256 8.40 / 8.21 / 8.18, 8192 x 128 8.77 / 8.58 / 8.46, 512 x 512 4.06 / 3.96 / 3.87, 256 x 512 3.32 / 3.20 / 3.14
   // (profiles/r04/ab_column_block_ghost_depth.txt).  LBM_TUNE_MACRO_GHOST still overrides.
-  if (k > 0 && py == 1 && clo >= 256 && !tune_env("LBM_TUNE_TILE_GHOST_ROWS", 0) && static_cast<size_t>(chi) * rhi < (size_t(1) << 21) && tune_env("LBM_TUNE_MACRO_GHOST", -1) < 0)   // (blocks of >= 256 columns: the measured range)
+  if (k > 0 && py == 1 && clo >= 256 && !knobs.tile_ghost_rows && static_cast<size_t>(chi) * rhi < (size_t(1) << 21) && knobs.macro_ghost < 0)   // (blocks of >= 256 columns: the measured range)
     ghost = std::max(ghost, std::min(32 / k * k, static_cast<int>(kMaxGhost)));
   int ghost_x = (ghost + 1) & ~1;
-  ghost_x = std::min(std::max(tune_env("LBM_TUNE_TILE_GHOST_X", ghost_x) & ~1, ghost_x), kMaxGhost);
+  ghost_x = std::min(std::max(knob_or(knobs.tile_ghost_x, ghost_x) & ~1, ghost_x), kMaxGhost);
   // every rank's storage rows (owned + ghost columns) must be ones the K-step kernels take, and its own columns at least the ghost
   // columns its neighbours need from it
   lbm_params narrow = *p, wide = *p;
@@ -1045,12 +1026,17 @@ int lbm_tile_layout_of(const lbm_params* p, int px, int py, int rank, unsigned f
     return 1;
   }
   out->macro_k = k; out->ghost = ghost; out->ghost_x = ghost_x;
-  out->group = macro_group_for(k, ghost);
+  out->group = macro_group_for(knobs, k, ghost);
   // column blocks (py = 1: every rank owns all rows) keep no ghost rows: their launches wrap in y like a whole grid's, and an exchange is the
   // column push alone.  LBM_TUNE_TILE_GHOST_ROWS=1 keeps them (a 1 x 1 ring then stands for a block of ANY tiling: the rank is its own south
   // and north neighbour through the row push, as it is its own west and east one)
-  out->ghost_y = (py == 1 && !tune_env("LBM_TUNE_TILE_GHOST_ROWS", 0)) ? 0 : ghost;
+  out->ghost_y = (py == 1 && !knobs.tile_ghost_rows) ? 0 : ghost;
   return 0;
+}
+
+int lbm_tile_layout_of(const lbm_params* p, int px, int py, int rank, unsigned flags, lbm_tile_layout* out)
+{
+  return tile_layout_of(knobs_from_env(), p, px, py, rank, flags, out);
 }
 
 // Row blocks or tiles, and which tiles, for `nranks` ranks: the decomposition whose ranks recompute the smallest share of cells they do not own.
@@ -1071,8 +1057,9 @@ int lbm_choose_rank_grid(const lbm_params* p, int nranks, unsigned flags, int* p
 {
   if (!p || !px || !py || nranks < 1) { lbm_internal::set_error("lbm_choose_rank_grid: bad argument"); return 1; }
   *px = 1; *py = nranks;
+  const Knobs knobs = knobs_from_env();
   lbm_layout rows;
-  if (lbm_rank_layout(p, nranks, nranks - 1, flags, &rows)) return 1;
+  if (rank_layout(knobs, p, nranks, nranks - 1, flags, &rows)) return 1;
   if (nranks == 1) return 0;
   std::vector<int> nyl(nranks), dis(nranks);
   if (lbm_decompose(p->ny, nranks, nyl.data(), dis.data())) return 1;
@@ -1082,7 +1069,7 @@ int lbm_choose_rank_grid(const lbm_params* p, int nranks, unsigned flags, int* p
   for (int qx = 2; qx <= nranks; ++qx) {
     if (nranks % qx != 0) continue;
     lbm_tile_layout t;
-    if (lbm_tile_layout_of(p, qx, nranks / qx, nranks - 1, flags, &t)) continue;      // a rank would fall out of K-step mode: not a candidate
+    if (tile_layout_of(knobs, p, qx, nranks / qx, nranks - 1, flags, &t)) continue;      // a rank would fall out of K-step mode: not a candidate
     // (the last rank holds the smallest column block and, by the reference's rule, not the largest row block)
     // (a column block's 32 ghost columns count as 16 here: the rule was measured at 16, and the deeper halo only made the column blocks faster)
     const double cost = t.ghost_y > 0 ? 0.75 * t.ghost_y / t.ny_local + 2.0 * t.ghost_x / t.nx_local + 0.05 + thin(t.ny_local)
@@ -1097,12 +1084,13 @@ int lbm_create_tile(lbm_ctx** out, const lbm_params* p, int free_cells, const in
 {
   lbm_tile_layout lay;
   if (!obstacle_window) { lbm_internal::set_error("lbm_create_tile: null argument"); return 1; }
-  if (lbm_tile_layout_of(p, px, py, rank, flags, &lay)) return 1;
+  const Knobs knobs = knobs_from_env();
+  if (tile_layout_of(knobs, p, px, py, rank, flags, &lay)) return 1;
   lbm_params local = *p;
   local.nx = lay.nx_local + 2 * lay.ghost_x;                                           // the storage row: what every kernel works on
   const TileSpec tile{px, py, lay.rx, lay.ry, lay.x0, lay.nx_local, lay.ghost_x, p->nx, lay.ghost_y};
   const int* rows = obstacle_window + static_cast<size_t>(lay.ghost_y) * local.nx;    // the owned rows inside the window
-  return create_impl(out, &local, free_cells, rows, nullptr, obstacle_window, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, device,
+  return create_impl(out, knobs, &local, free_cells, rows, nullptr, obstacle_window, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, device,
                      flags | LBM_FLAG_FORCE_HALO, &tile);
 }
 
@@ -1231,14 +1219,16 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
   c->ev_valid = true;
   if (fold_last(c, s, /*final=*/true)) return 1;
   c->run_done = n_steps;
+  // blocking waits: polling hipStreamQuery first measured no faster on 20-step runs of a 1-rank ring of 8192 x 1024 rows
+  // (52.70 us/step blocking, 52.63 polling; profiles/r03/ab_ring_spin_8192x1024_s20.txt)
   if (av_vels) {
     const double* host = c->sums_host;
     HIP_TRY(hipMemcpyAsync(c->sums_host, c->sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s));
-    HIP_TRY(stream_wait(s));
+    HIP_TRY(hipStreamSynchronize(s));
     const double inv = static_cast<double>(c->free_cells_inv);
     for (int t = 0; t < n_steps; ++t) av_vels[t] = static_cast<float>(host[t] * inv);   // d2q9-bgk.c:367
   } else {
-    HIP_TRY(stream_wait(s));
+    HIP_TRY(hipStreamSynchronize(s));
   }
   return 0;
 }
@@ -1288,7 +1278,7 @@ int lbm_get_observables(lbm_ctx* c, float* obs)
   // row blocks of at most 16 M cells through a 256 MB device buffer: no second copy of the state
   // (whole rows per block, so that a block of a tile rank's column window starts on a row)
   const size_t total = owned_cells(c);
-  const size_t chunk = std::min<size_t>(total, std::max<size_t>(1, static_cast<size_t>(tune_env("LBM_TUNE_OBS_CHUNK_CELLS", 16 << 20)) / c->nxl) * c->nxl);
+  const size_t chunk = std::min<size_t>(total, std::max<size_t>(1, static_cast<size_t>(c->knobs.obs_chunk_cells) / c->nxl) * c->nxl);
   float* tmp = nullptr;
   HIP_TRY(hipMalloc(&tmp, sizeof(float) * 4 * chunk));
   hipError_t e = hipSuccess;
@@ -1705,7 +1695,7 @@ int lbm_step_collect(lbm_ctx* c, void* stream, double* tot_u_per_step, int n_ste
   if (!c || !tot_u_per_step || n_steps > c->run_done) { lbm_internal::set_error("lbm_step_collect: bad argument"); return 1; }
   hipStream_t s = pick_stream(c, stream);
   HIP_TRY(hipMemcpyAsync(tot_u_per_step, c->sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s));
-  HIP_TRY(stream_wait(s));
+  HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }
 

@@ -204,7 +204,7 @@ int p2p_push_cols(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s)
   };
   const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
   const int work = 18 * c->nyl * (k / per);
-  const dim3 grid(std::max(1, std::min(std::max(1, tune_env("LBM_P2P_PUSH_BLOCKS_SERIAL", kP2PPushBlocks)), (work + 1023) / 1024)));
+  const dim3 grid(std::max(1, std::min(kP2PPushBlocks, (work + 1023) / 1024)));
   if (per == 4) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f4>, grid, dim3(256), 0, s, a);
   else if (per == 2) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<float>, grid, dim3(256), 0, s, a);
@@ -250,10 +250,10 @@ int p2p_push(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s, bool ex
   // (`exposed`: the push before the first macro-step of a run in the serial schedule, which nothing overlaps)
   // (pushes of more than four rows, round 4: twice the blocks — 8 rows beside the interior launch of 8192 x 1024 rows, us/step at 20 / 200
   // steps per run for 16 / 32 / 64 / 128 blocks: 51.9 / 49.4, 46.9 / 43.5, 47.0 / 43.1, 48.6 / 44.0; profiles/r04/ring_push_blocks.txt)
-  const int max_blocks = (t->edge_stream && !exposed) ? t->push_blocks_edge * (k > 4 ? 2 : 1) : std::max(1, tune_env("LBM_P2P_PUSH_BLOCKS_SERIAL", kP2PPushBlocks));
+  const int max_blocks = (t->edge_stream && !exposed) ? t->push_blocks_edge * (k > 4 ? 2 : 1) : kP2PPushBlocks;
   // (exposed push of a 1024 x 128-row rank, 16 rows: us/step at 200 steps for 32 / 64 / 72 blocks of 1024 vectors 3.59 / 3.50 - 3.55 / 3.51, 144 blocks of
   // 512 vectors 3.61, 288 of 256 3.90 — the block count is not the lever; profiles/r04/ring_push_blocks_serial.txt)
-  const int per_block = std::max(256, tune_env("LBM_P2P_PUSH_WORK_PER_BLOCK", 1024));
+  const int per_block = 1024;
   const dim3 grid(std::max(1, std::min(max_blocks, (work + per_block - 1) / per_block)));
   if (wide) hipLaunchKernelGGL(lbm_p2p_push_kernel<f4>, grid, dim3(256), 0, s, a, nx);
   else hipLaunchKernelGGL(lbm_p2p_push_kernel<f2>, grid, dim3(256), 0, s, a, nx);
@@ -284,7 +284,7 @@ int p2p_reduce(lbm_p2p* t, int n_steps, double* tot_u_per_step)
     hipLaunchKernelGGL(lbm_p2p_allreduce_kernel, dim3(t->nranks), dim3(256), 0, cs, a);
     HIP_TRY(hipGetLastError());
     t->ev_reduce_end = p2p_stamp(t, cs);
-    HIP_TRY(stream_wait(cs));
+    HIP_TRY(hipStreamSynchronize(cs));
     std::memcpy(tot_u_per_step + t0, t->reduce_out, sizeof(double) * n);     // host-mapped: the kernel wrote it in place
   }
   return 0;
@@ -399,7 +399,8 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   }
   t->compute = ctx->stream;
   t->peers.resize(nranks);
-  t->timeout_ticks = static_cast<long long>(tune_env("LBM_P2P_TIMEOUT_MS", 30000)) * 100000LL;   // wall_clock64: 100 MHz
+  const Knobs knobs = knobs_from_env();
+  t->timeout_ticks = static_cast<long long>(knobs.p2p_timeout_ms) * 100000LL;   // wall_clock64: 100 MHz
   // default by size, as the RCCL loop: an own stream for the edge rows pays once the interior launch is long
   // enough to cover two cross-queue waits
   t->edge_stream = ctx->ncells >= (size_t(1) << 21);
@@ -408,16 +409,13 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   // exchange it hides is short (31 us per 8 steps): 1-rank rings, us/step serial / edge stream: 2048 x 4096 45.5 / 46.5, 4096 x 4096 82.0 / 82.4,
   // 4096 x 8192 158.0 / 155.5 (profiles/r04/tile_ring_*_{serial,edge_stream}.json) — from 2^25 cells up
   if (t->tiles) t->edge_stream = ctx->ncells >= (size_t(1) << 25);
-  if (const char* sched = std::getenv("LBM_P2P_SCHEDULE")) {
-    if (std::string(sched) == "serial") t->edge_stream = false;
-    if (std::string(sched) == "edge") t->edge_stream = true;
-  }
+  if (knobs.p2p_schedule != kKnobUnset) t->edge_stream = knobs.p2p_schedule == kScheduleEdge;
   // beside the interior launch the push has a whole macro-step to finish, and every block of it takes a CU slot and
   // an L2 write-back away from that launch: us/step on a 1-rank ring of 8192 x 1024 rows for 8 / 12 / 16 / 32 / 64
   // blocks 60.1 / 52.8 / 51.7 / 52.1 / 53.6 (8192 x 2048: 94.8 / - / 95.2 / 95.1 / 96.7)
   // 32, not the 16 that measure best on a self-ring: there the push kernel takes ~110 of the ~147 us it has, and a
   // real link is slower than local memory — a push that outlasts the interior launch would be the critical path
-  t->push_blocks_edge = std::max(1, tune_env("LBM_P2P_PUSH_BLOCKS", 32));
+  t->push_blocks_edge = std::max(1, knobs.p2p_push_blocks);
   auto fail = [&]() { lbm_p2p_destroy(t); return 1; };
 #define P2P_TRY(expr)                                                                        \
   do {                                                                                       \
@@ -442,7 +440,7 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   // transport is NOT created and the caller falls back to the RCCL loop.  LBM_P2P_WINDOW=2 asks for the coarse
   // window explicitly (experiments on one GPU only).
   void* w = nullptr;
-  const int want = tune_env("LBM_P2P_WINDOW", 0);
+  const int want = knobs.p2p_window;
   if (want <= 0 && hipExtMallocWithFlags(&w, t->window_bytes, hipDeviceMallocUncached) == hipSuccess) t->window_kind = "uncached";
   else if (want <= 1 && hipExtMallocWithFlags(&w, t->window_bytes, hipDeviceMallocFinegrained) == hipSuccess) t->window_kind = "fine-grained";
   else if (want >= 2) { (void)hipGetLastError(); P2P_TRY(hipMalloc(&w, t->window_bytes)); t->window_kind = "coarse"; }

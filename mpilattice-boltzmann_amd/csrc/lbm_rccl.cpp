@@ -28,6 +28,7 @@
 
 #include "lbm_d2q9_rccl.h"
 #include "lbm_internal.h"
+#include "lbm_knobs.h"
 
 struct lbm_comm {
   lbm_ctx* ctx = nullptr;
@@ -123,21 +124,15 @@ int lbm_comm_create(lbm_comm** out, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTE
       return fail();
     }
   }
-  const char* sched = std::getenv("LBM_RCCL_SCHEDULE");
   // default by size: three queues pay once the interior kernel is long enough to cover two extra
   // cross-queue waits (measured on MI355X: 8192x1024 rows 120 vs 133 us/step; 1024x128 rows 55 vs 34)
+  const int sched = knobs_from_env().rccl_schedule;
   long long cells = 0;
   (void)lbm_describe(ctx, nullptr, 0, &cells, nullptr);
-  c->three_queues = cells >= (1LL << 21);
-  if (sched && std::string(sched) == "serial") c->three_queues = false;
-  if (sched && std::string(sched) == "edge") c->three_queues = true;
-  // LBM_RCCL_PRIORITY=1: side/edge streams at the highest stream priority (measured: slower)
-  const char* prio = std::getenv("LBM_RCCL_PRIORITY");
-  int prio_low = 0, prio_high = 0;
-  (void)hipDeviceGetStreamPriorityRange(&prio_low, &prio_high);   // numerically lower = higher priority
-  const int use_prio = (prio && prio[0] == '1') ? prio_high : 0;   // 0 = the normal priority of hipStreamCreate
-  if (hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, use_prio) != hipSuccess ||
-      hipStreamCreateWithPriority(&c->edge, hipStreamNonBlocking, use_prio) != hipSuccess ||
+  c->three_queues = sched != kKnobUnset ? sched == kScheduleEdge : cells >= (1LL << 21);
+  // side / edge streams at the normal priority: the highest one measured 2x slower
+  if (hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, 0) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->edge, hipStreamNonBlocking, 0) != hipSuccess ||
       hipEventCreateWithFlags(&c->halo, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->edge_done, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&c->interior_done, hipEventDisableTiming) != hipSuccess) {
@@ -181,15 +176,13 @@ int lbm_comm_destroy(lbm_comm* c)
 // K-step mode (contexts from lbm_create_rank / lbm_create_global, lbm_macro_steps() = K > 0): one exchange of the partition's ghost
 // rows (`ghost` whole rows of each of the 9 planes: 2 K) per GROUP of launches (lbm_macro_next_launches(): two 4-step launches by
 // default), same three-queue schedule for the first launch of the group; the later ones — launches over all tiles that read no
-// exchanged row — are made by lbm_macro_finish on the compute stream.  By default the 18 row blocks of a direction pair are packed into
-// one message per direction by a small kernel on the exchange stream (fewer, larger messages); LBM_RCCL_PACK=0 sends them straight
-// from the edge rows into the neighbour's ghost rows as 18 + 18 messages.
+// exchanged row — are made by lbm_macro_finish on the compute stream.  The 18 row blocks of a direction pair are packed into one
+// message per direction by a small kernel on the exchange stream: fewer, larger messages (18 + 18 direct ones measured 25 against
+// 14 us/step, DESIGN_APPENDIX.md).
 static int run_macro(lbm_comm* c, int n_steps, double* tot_u_per_step)
 {
   lbm_ctx* ctx = c->ctx;
-  const size_t n = lbm_macro_halo_floats(ctx), np = lbm_macro_pack_floats(ctx);
-  const char* pk = std::getenv("LBM_RCCL_PACK");
-  const bool packed = !(pk && pk[0] == '0');              // default: 2 + 2 packed messages; 0 = 18 + 18 direct ones
+  const size_t np = lbm_macro_pack_floats(ctx);
   const bool three_queues = c->three_queues;
   hipStream_t edge_stream = c->edge;
   // small ranks (one-queue schedule): the exchange goes to the compute stream as well — every hand-off between queues costs 6 - 8 us of idle
@@ -208,26 +201,15 @@ static int run_macro(lbm_comm* c, int n_steps, double* tot_u_per_step)
       HIP_TRY(hipStreamWaitEvent(c->side, c->edge_done, 0));
       HIP_TRY(hipStreamWaitEvent(c->side, c->interior_done, 0));
     }
-    if (packed) {
-      // gather the 9 planes' rows into one message per direction, exchange 2 + 2 messages, scatter
-      LBM_TRY(lbm_macro_pack(ctx, xs));
-      NCCL_TRY(ncclGroupStart());                            // order as in the one-step loop: sends [S, N], receives [N, S]
-      NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 0, 0), np, ncclFloat, c->south, c->nccl, xs));
-      NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 1, 0), np, ncclFloat, c->north, c->nccl, xs));
-      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 1, 1), np, ncclFloat, c->north, c->nccl, xs));
-      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 0, 1), np, ncclFloat, c->south, c->nccl, xs));
-      NCCL_TRY(ncclGroupEnd());
-      LBM_TRY(lbm_macro_unpack(ctx, xs));
-    } else {
-      NCCL_TRY(ncclGroupStart());
-      for (int q = 0; q < LBM_NSPEEDS; ++q) {                // rows straight into the neighbour's ghost rows
-        NCCL_TRY(ncclSend(lbm_macro_send_ptr(ctx, 0, q), n, ncclFloat, c->south, c->nccl, xs));
-        NCCL_TRY(ncclSend(lbm_macro_send_ptr(ctx, 1, q), n, ncclFloat, c->north, c->nccl, xs));
-        NCCL_TRY(ncclRecv(lbm_macro_recv_ptr(ctx, 1, q), n, ncclFloat, c->north, c->nccl, xs));
-        NCCL_TRY(ncclRecv(lbm_macro_recv_ptr(ctx, 0, q), n, ncclFloat, c->south, c->nccl, xs));
-      }
-      NCCL_TRY(ncclGroupEnd());
-    }
+    // gather the 9 planes' rows into one message per direction, exchange 2 + 2 messages, scatter
+    LBM_TRY(lbm_macro_pack(ctx, xs));
+    NCCL_TRY(ncclGroupStart());                            // order as in the one-step loop: sends [S, N], receives [N, S]
+    NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 0, 0), np, ncclFloat, c->south, c->nccl, xs));
+    NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 1, 0), np, ncclFloat, c->north, c->nccl, xs));
+    NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 1, 1), np, ncclFloat, c->north, c->nccl, xs));
+    NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 0, 1), np, ncclFloat, c->south, c->nccl, xs));
+    NCCL_TRY(ncclGroupEnd());
+    LBM_TRY(lbm_macro_unpack(ctx, xs));
     if (three_queues) HIP_TRY(hipEventRecord(c->halo, c->side));
     if (three_queues) {
       if (prev_launches == 1) HIP_TRY(hipStreamWaitEvent(c->compute, c->edge_done, 0));

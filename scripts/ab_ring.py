@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Same-process A/B of run-boundary settings on a 1-rank peer-to-peer ring (box-to-box spread exceeds what a
-per-run overhead of 10-20 us is worth): one ring, short runs, settings alternated round-robin, wall time of
-`run(steps)` + device synchronise per run as bench.py times it.
+"""A/B of library knobs on a 1-rank peer-to-peer ring (box-to-box spread exceeds what a per-run overhead of 10-20 us is
+worth): one ring per setting in one process, short runs, rings alternated round-robin, wall time of `run(steps)` + device
+synchronise per run as bench.py times it.
 
-    python scripts/ab_ring.py --grid 8192x1024 --steps 20 --rounds 40 LBM_SPIN_WAIT_US=0 LBM_SPIN_WAIT_US=4000
+    python scripts/ab_ring.py --grid 8192x1024 --steps 20 --rounds 40 - LBM_TUNE_MACRO_GHOST=16
 
-Each positional argument is one setting: comma-separated KEY=VALUE pairs put into the environment before the run
-(only knobs the library reads per call take effect: LBM_SPIN_WAIT_US).  With --per-context every setting gets its OWN ring,
-created with the setting in the environment (knobs read at lbm_create: LBM_TUNE_MULTI_GEOM, LBM_TUNE_MACRO_K ...); a setting "-"
-is the default environment; --single runs the grid as one periodic launch per macro-step instead of a ring."""
+Each positional argument is one setting: comma-separated KEY=VALUE pairs put into the environment while its ring is created
+(the library reads its knobs when it creates a context or a transport: csrc/lbm_knobs.h); a setting "-" is the default
+environment.  --per-context is the only mode and is accepted for old command lines; --single runs the grid as one periodic
+launch per macro-step instead of a ring."""
 import argparse
 import os
 import statistics
@@ -25,7 +25,7 @@ ap.add_argument("--grid", default="8192x1024")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=40)
 ap.add_argument("--exchange", default="p2p")
-ap.add_argument("--per-context", action="store_true")
+ap.add_argument("--per-context", action="store_true", help="the only mode (every setting gets its own ring)")
 ap.add_argument("--single", action="store_true")
 ap.add_argument("settings", nargs="+")
 a = ap.parse_args()
@@ -49,22 +49,15 @@ def make():
 
 
 sims = {}
-if a.per_context:
-    for s in a.settings:
-        keys = apply(s)
-        sims[s] = make()
-        for k in keys:
-            os.environ.pop(k, None)
-        sims[s].run(a.steps)
-else:
-    one = make()
-    one.run(a.steps)
-    sims = {s: one for s in a.settings}
+for s in a.settings:
+    keys = apply(s)
+    sims[s] = make()
+    for k in keys:
+        os.environ.pop(k, None)
+    sims[s].run(a.steps)
 res = {s: [] for s in a.settings}
 for r in range(a.rounds):
     for s in a.settings:
-        if not a.per_context:
-            apply(s)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         sims[s].run(a.steps)
@@ -73,5 +66,5 @@ for r in range(a.rounds):
 for s in a.settings:
     v = res[s][2:]
     print(f"{s:40s} min {min(v):7.2f}  med {statistics.median(v):7.2f}  max {max(v):7.2f} us/step", flush=True)
-for sim in set(sims.values()):
+for sim in sims.values():
     sim.close()

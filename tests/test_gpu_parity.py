@@ -1341,9 +1341,12 @@ def test_tile_context_moves_and_digests_its_block_through_a_column_window(lbm, o
     whole.set_cells(state)
     obs = part.get_observables()
     assert np.array_equal(obs.view(np.uint32), whole.get_observables()[ys, xs].view(np.uint32))
-    monkeypatch.setenv("LBM_TUNE_OBS_CHUNK_CELLS", str(37 * lay["nx_local"] + 5))      # 37 rows per fetch
-    assert np.array_equal(part.get_observables().view(np.uint32), obs.view(np.uint32))
+    monkeypatch.setenv("LBM_TUNE_OBS_CHUNK_CELLS", str(37 * lay["nx_local"] + 5))      # 37 rows per fetch (read when a context is created)
+    chunked = lbm.Partition(p, free, lbm.obstacle_window(obst, lay), tile_of=(3, 2, 2))
     monkeypatch.delenv("LBM_TUNE_OBS_CHUNK_CELLS")
+    chunked.set_cells(state[ys, xs])
+    assert np.array_equal(chunked.get_observables().view(np.uint32), obs.view(np.uint32))
+    chunked.close()
     y0, y1 = lay["y0"], lay["y0"] + lay["ny_local"]
     mid = y0 + 51
     assert (part.checksum(y0, mid) + part.checksum(mid, y1)) % (1 << 64) == part.checksum() and part.checksum(mid, mid) == 0

@@ -831,3 +831,37 @@ def test_shipped_library_carries_no_experiment_kernels(lbm):
     blob = open(lbm.LIB_PATH, "rb").read()
     assert b"lbm_multi_kernel" in blob and b"lbm_tile_kernel" in blob and b"lbm_step_kernel" in blob
     assert b"lbm_sweep_kernel" not in blob and b"lbm_step_kernel_lds" not in blob
+
+
+REMOVED_KNOBS = {"LBM_SPIN_WAIT_US", "LBM_RCCL_PRIORITY", "LBM_RCCL_PACK", "LBM_P2P_PUSH_BLOCKS_SERIAL", "LBM_P2P_PUSH_WORK_PER_BLOCK"}
+
+
+def test_every_library_knob_is_a_row_of_one_table_and_documented():
+    """csrc/lbm_knobs.h lists every LBM_* environment knob of the two libraries, its reader is their only getenv, every LBM_* name
+    in a string of their sources is a row of it (or a macro of the ABI), scripts/README.md's knob table has exactly one row per knob,
+    and the knobs whose variants were measured and dropped are gone from all three."""
+    csrc = os.path.join(ROOT, "mpilattice-boltzmann_amd", "csrc")
+    table = open(os.path.join(csrc, "lbm_knobs.h")).read()
+    rows = re.findall(r"^\s*X\((LBM_[A-Z0-9_]+),", table, re.M)
+    assert len(rows) == len(set(rows)) > 20
+    sources = {f: open(os.path.join(csrc, f)).read() for f in os.listdir(csrc) if f.endswith((".hip", ".cpp")) or f == "lbm_p2p_impl.h"}
+    assert {"lbm_kernels.hip", "lbm_host.cpp", "lbm_rccl.cpp", "lbm_p2p_impl.h"} <= set(sources)
+    macros = set()
+    for d in (os.path.join(ROOT, "include"), csrc):
+        for f in os.listdir(d):
+            if f.endswith((".h", ".hip", ".cpp")):
+                macros |= set(re.findall(r"#\s*define\s+(LBM_[A-Z0-9_]+)", open(os.path.join(d, f)).read()))
+    for name, text in sources.items():
+        assert "getenv" not in text, name
+        for lit in re.findall(r'"(?:[^"\\\n]|\\.)*"', text):
+            for knob in re.findall(r"\bLBM_[A-Z0-9_]+", lit):
+                assert knob in rows or knob in macros or knob.startswith("LBM_FLAG_"), (name, knob)
+    assert table.count("getenv") == 1 + table.count("only getenv")
+    readme = open(os.path.join(ROOT, "scripts", "README.md")).read()
+    section = readme[readme.index("\nTuning knobs"):] + "\n\n"
+    section = section[:section.index("\n\n", section.index("\n|"))]
+    documented = re.findall(r"^\| `(LBM_[A-Z0-9_]+)` \|", section, re.M)
+    assert len(documented) == len(re.findall(r"^\| `LBM_", section, re.M)) and len(documented) == len(set(documented))
+    assert sorted(documented) == sorted(rows)
+    assert not REMOVED_KNOBS & (set(rows) | set(documented))
+    assert not any(k in text for k in REMOVED_KNOBS for text in list(sources.values()) + [table])
