@@ -19,6 +19,13 @@ namespace {
 // the one-step kernel.  HBM traffic per K steps: (64+2K)(16+2K)/1024 x 36 B read + 36 B written
 // (K = 2: 84 B instead of 144 B; K = 4: 97 B instead of 288 B).
 //
+// Dealing of lanes.  k_substeps deals each region's pairs row after row over the block, in passes of
+// whole rows (sub-steps 1 - 3 of the tall K = 4 launch take two passes each), every pair with the
+// sum|u| term code and a flag byte in LDS.  The tall K = 4 instantiation, whose 64 x 24 tile has one
+// x-pair per lane, runs owned_substeps instead: each lane keeps its owned pair for the whole launch
+// (flags and population 0 in registers), and the ring pairs are extra, term-free items on the first
+// lanes, one per lane and sub-step, so that each in-LDS sub-step is a single read / barrier / write.
+//
 // Rows outside the partition: `y_periodic` wraps (self-contained domain); otherwise the storage has
 // `ghost` extra rows below and above the owned rows, filled by the neighbours before the launch.
 // ------------------------------------------------------------------------------------------------
@@ -95,6 +102,10 @@ struct MultiGeom {
   // waves per SIMD the kernel is compiled for: what its LDS frame lets a CU hold, LBM_MWAVES at most
   static constexpr int blocks_per_cu = lds_bytes * 8 <= 160 * 1024 ? 8 : static_cast<int>(160 * 1024 / lds_bytes);
   static constexpr int waves_per_simd = blocks_per_cu * (LANES / 64) / 4 < LBM_MWAVES ? (blocks_per_cu * (LANES / 64) / 4 < 1 ? 1 : blocks_per_cu * (LANES / 64) / 4) : LBM_MWAVES;
+  // lanes dealt one owned x-pair each for the whole launch (the tall K = 4 geometry: 32 x 24 pairs on 768 lanes; see owned_substeps)
+  static constexpr bool owned_lanes = K == 4 && GEOM == kGeomTall;
+  // x-pairs of sub-step j's region outside the owned tile: ey rows below and above it, multi_ex(ey) / 2 pairs on each side of its rows
+  static constexpr int ring_pairs(int j) { return 2 * (K - j) * (TX / 2 + multi_ex(K - j)) + TY * multi_ex(K - j); }
 };
 
 struct MultiArgs {
@@ -162,6 +173,19 @@ __device__ __forceinline__ void store_pair(float* plane, int k, int row, int fx,
   } else {
     plane[row + (fx >> 1)] = v.y;
     plane[row + (fx >> 1) + W / 2] = v.x;
+  }
+}
+
+// finish_pair_lo's accelerate_flow (d2q9-bgk.c:457-469) on the pair's vector elements directly.  owned_substeps relaxes with
+// tile_accel = false and applies this after: the same arithmetic, but no float[9] copy of each cell, which hipcc turned into
+// strided vector loads of the result array and then kept that array in scratch.
+__device__ __forceinline__ void accelerate_pair(f2 (&out)[9], uint32_t mbits, bool accel, float w1, float w2)
+{
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const bool go = accel && !((mbits >> j) & 1u) && out[3][j] - w1 > 0.0f && out[6][j] - w2 > 0.0f && out[7][j] - w2 > 0.0f;
+    out[1][j] = go ? out[1][j] + w1 : out[1][j]; out[5][j] = go ? out[5][j] + w2 : out[5][j]; out[8][j] = go ? out[8][j] + w2 : out[8][j];
+    out[3][j] = go ? out[3][j] - w1 : out[3][j]; out[6][j] = go ? out[6][j] - w2 : out[6][j]; out[7][j] = go ? out[7][j] - w2 : out[7][j];
   }
 }
 
@@ -288,6 +312,11 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     return g == a.accel_row;
   };
 
+  // tiles whose frame (and its x -+ 1, y -+ 1 reads) lies inside the grid need none of the periodic
+  // wraps and none of the partial-tile tests in sub-step 1: block-uniform fast path for all but the edge tiles
+  const bool inner = x0 - EX >= 2 && x0 + TX + EX + 2 <= nx && sy0 - EY >= 1 && sy0 + TY + EY + 1 <= rows_storage &&
+                     sy0 + TY <= a.row_first + a.rows_compute;
+
   // The K sub-steps, in two forms: COUNT = the tile holds rows that are computed but not counted (a launch that also advances ghost rows:
   // its first and last tile rows) — every pair then carries a `counted` bit beside `owned`; all other tiles, and every tile of the other
   // launches, take the form without it, whose schedule is the one rounds 1 - 3 measured (see PART above: the test costs 2 - 3 % when every
@@ -299,10 +328,6 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       const int ey = ksteps - 1, ex = multi_ex(ey);
       const int wp = (TX + 2 * ex) / 2;                                 // pairs per region row
       const int np = wp * (TY + 2 * ey);
-      // tiles whose frame (and its x -+ 1, y -+ 1 reads) lies inside the grid need none of the periodic
-      // wraps and none of the partial-tile tests: block-uniform fast path for all but the edge tiles
-      const bool inner = x0 - EX >= 2 && x0 + TX + EX + 2 <= nx && sy0 - EY >= 1 && sy0 + TY + EY + 1 <= rows_storage &&
-                         sy0 + TY <= a.row_first + a.rows_compute;
   #pragma unroll 1
       for (int i = tid; i < np; i += kLanes) {
         const int ry = i / wp, rp = i - ry * wp;
@@ -462,18 +487,205 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     }
 
   };
+
+  // The same K sub-steps with the lanes dealt ONE OWNED x-pair each for the whole launch (G::owned_lanes: a tile of exactly as many
+  // x-pairs as the block has lanes).  Lane t keeps pair (t mod TX/2, t / (TX/2)) of the tile: its flag bits (as pair_flags) and its
+  // population 0, which never streams, live in registers, and its frame address is fixed — each sub-step moves it by a constant row.
+  // The ring of each region (312 / 184 / 116 pairs at K = 4) is extra, term-free work on the first lanes: sub-step 1 runs one ring
+  // item after the owned pass; sub-step j < K relaxes the owned pair and, on those lanes, reads one ring pair, meets at ONE barrier,
+  // then relaxes the ring pair and writes both (the dealing above takes two passes for each of sub-steps 1 - 3, every pair with the
+  // term code).  Each lane adds exactly one
+  // pair's term per sub-step: acc[j-1] is that term, its compensated low part already added.  Plane 0 and the flag byte are kept in
+  // LDS for ring pairs only.
+  auto owned_substeps = [&](auto count_c) __attribute__((always_inline)) {
+    constexpr bool COUNT = decltype(count_c)::value;
+    constexpr int TP = TX / 2;                                         // owned pairs per tile row
+    static_assert(TP * TY == kLanes && G::ring_pairs(1) <= kLanes, "one owned pair and at most one ring pair per lane and sub-step");
+    // ring pair i of sub-step j: the ey region rows below the tile, the ey above it, then per tile row the ex / 2 pairs on each side
+    auto ring_pos = [&](auto jc, const int i, int& fx, int& fy) __attribute__((always_inline)) {
+      constexpr int ey = K - decltype(jc)::value, ex = multi_ex(ey), ep = ex / 2, wp = TP + ep * 2, band = ey * wp;
+      if (i < 2 * band) {
+        const bool top = i >= band;
+        const int q = top ? i - band : i, ry = q / wp, rp = q - ry * wp;
+        fy = top ? EY + TY + ry : EY - ey + ry;
+        fx = EX - ex + 2 * rp;
+      } else {
+        const int q = i - 2 * band, ry = q / (2 * ep), c = q - ry * (2 * ep);
+        fy = EY + ry;
+        fx = EX - ex + 2 * (c < ep ? c : c + TP);
+      }
+    };
+    // relaxation, bounce-back and accelerate_flow of one pair; returns its sum|u| term (0 where skip = 3)
+    auto relax = [&](const f2 (&p)[9], const uint32_t mbits, const bool accel, const uint32_t skip, f2 (&out)[9]) __attribute__((always_inline)) {
+      const double term = finish_pair<TERMS>(p, mbits, a.omega, false, false, a.accel_w1, a.accel_w2, skip, out);
+      if (tile_accel) accelerate_pair(out, mbits, accel, a.accel_w1, a.accel_w2);
+      return term;
+    };
+    // sub-step 1's sources of frame pair (fx, fy), as k_substeps pulls them; false: a row past the storage (a row partition
+    // whose rows the tile height does not divide), outside every owned cell's dependency cone and not computed
+    auto pull = [&](const int fx, const int fy, f2 (&p)[9], uint32_t& mbits, int& sr) __attribute__((always_inline)) -> bool {
+      int gx = x0 + fx - EX;
+      sr = sy0 + fy - EY;
+      int cell = tile_row_base + __mul24(fy - EY, nx) + gx;
+      int d_south = -nx, d_north = nx;
+      if (!inner) {
+        if (gx < 0) { gx += nx; cell += nx; } else if (gx >= nx) { gx -= nx; cell -= nx; }      // periodic (:527-529)
+        if (!a.y_periodic && sr + 1 >= rows_storage) return false;
+        if (a.y_periodic) {                                                               // periodic (:245-247)
+          if (sr < 0) { sr += rows_storage; cell += grid_cells; } else if (sr >= rows_storage) { sr -= rows_storage; cell -= grid_cells; }
+          if (sr == 0) d_south = grid_cells - nx;
+          if (sr + 1 >= rows_storage) d_north = nx - grid_cells;
+        }
+      }
+      const uint32_t o_here = 4u * static_cast<uint32_t>(cell);
+      const uint32_t o_south = 4u * static_cast<uint32_t>(cell + d_south);
+      const uint32_t o_north = 4u * static_cast<uint32_t>(cell + d_north);
+      p[0] = at_byte<f2>(a.srck[0], o_here);                                           // :530-538
+      p[2] = at_byte<f2>(a.srck[2], o_south);
+      p[4] = at_byte<f2>(a.srck[4], o_north);
+      p[1] = at_byte<f2u>(a.srck[1] - 1, o_here);
+      p[5] = at_byte<f2u>(a.srck[5] - 1, o_south);
+      p[8] = at_byte<f2u>(a.srck[8] - 1, o_north);
+      p[3] = at_byte<f2u>(a.srck[3] + 1, o_here);
+      p[6] = at_byte<f2u>(a.srck[6] + 1, o_south);
+      p[7] = at_byte<f2u>(a.srck[7] + 1, o_north);
+      if (!inner) {
+        if (gx == 0) {
+          p[1].x = at_byte<float>(a.srck[1] + nx - 1, o_here); p[5].x = at_byte<float>(a.srck[5] + nx - 1, o_south);
+          p[8].x = at_byte<float>(a.srck[8] + nx - 1, o_north);
+        }
+        if (gx == nx - 2) {
+          p[3].y = at_byte<float>(a.srck[3] + 2 - nx, o_here); p[6].y = at_byte<float>(a.srck[6] + 2 - nx, o_south);
+          p[7].y = at_byte<float>(a.srck[7] + 2 - nx, o_north);
+        }
+      }
+      mbits = (at_byte<uint32_t>(a.mask, 4u * (static_cast<uint32_t>(cell) >> 5)) >> (cell & 31)) & 3u;
+      return true;
+    };
+    const int py = tid / TP, ofx = EX + 2 * (tid - py * TP), ofy = EY + py;
+    f2 own0 = f2{0.0f, 0.0f};                                          // population 0 of the owned pair
+    uint32_t ofl = 0;                                                  // its flag bits; 0: not computed
+    // ---- sub-step 1: item 0 = the owned pair, item 1 = a ring pair (the first G::ring_pairs(1) lanes)
+  #pragma unroll 1
+    for (int item = 0; item < 2; ++item) {
+      const bool own = item == 0;
+      if (!own && tid >= G::ring_pairs(1)) break;
+      int fx = ofx, fy = ofy;
+      if (!own) ring_pos(std::integral_constant<int, 1>{}, tid, fx, fy);
+      f2 p[9];
+      uint32_t mbits = 0, fl = 0;
+      int sr = 0;
+      if (pull(fx, fy, p, mbits, sr)) {
+        // kept = an owned pair inside the grid (the last tile column / row may stick out of a grid whose edges are not multiples of the tile)
+        const int srow = sy0 + fy - EY;                                // storage row before any periodic wrap
+        const bool kept_rows = own && (inner || (x0 + fx - EX < nx && srow < a.row_first + a.rows_compute));
+        const bool counted_rows = COUNT ? (kept_rows && srow >= a.count_first && srow < a.count_end) : kept_rows;
+        bool kept = kept_rows, counted = counted_rows;
+        if constexpr (XR && COUNT) {
+          const int gxo = x0 + fx - EX;
+          kept = kept_rows && gxo >= a.keep_x0 && gxo < a.keep_x1;
+          counted = counted_rows && kept && gxo >= a.cx0 && gxo < a.cx1;
+        }
+        bool accel_row_here = false;
+        if (tile_accel) accel_row_here = on_accel_row(sr);
+        f2 out[9];
+        const double term = relax(p, mbits, accel_row_here, counted ? mbits : 3u, out);
+  #pragma unroll
+        for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
+        fl = mbits | (kept ? 4u : 0u) | (accel_row_here ? 8u : 0u) | 16u | ((COUNT && counted) ? 32u : 0u);
+        if (own) {
+          acc[0] = term;
+          own0 = out[0];
+        } else {
+          store_pair<W>(lds, 0, fy * W, fx, out[0]);
+        }
+      }
+      if (own) ofl = fl;
+      else pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(fl);
+    }
+    LBM_MSTAMP(1);
+    __syncthreads();
+    LBM_MSTAMP(2);
+    // ---- sub-steps 2..K in place, the frame creeping down one row per sub-step as in k_substeps
+    auto in_lds_substep = [&](auto jc) __attribute__((always_inline)) {
+      constexpr int j = decltype(jc)::value;
+      constexpr bool last = j == K;
+      constexpr int rd = (j - 2) * W, wr = (j - 1) * W;                // storage shift of the frame read / written
+      // populations 1 - 8 of pair (fx, fy), from the frame layout k_substeps describes
+      auto read_pair = [&](const int fx, const int fy, f2 (&p)[9]) __attribute__((always_inline)) {
+        const int ci = fy * W + fx - rd, cs = fy * W + (fx >> 1) - rd;
+        p[2] = *reinterpret_cast<const f2*>(lds + 2 * kCells + ci - W);
+        p[4] = *reinterpret_cast<const f2*>(lds + 4 * kCells + ci + W);
+        p[1] = f2{lds[1 * kCells + cs - 1], lds[1 * kCells + cs + WH]};
+        p[5] = f2{lds[5 * kCells + cs - W - 1], lds[5 * kCells + cs - W + WH]};
+        p[8] = f2{lds[8 * kCells + cs + W - 1], lds[8 * kCells + cs + W + WH]};
+        p[3] = f2{lds[3 * kCells + cs], lds[3 * kCells + cs + WH + 1]};
+        p[6] = f2{lds[6 * kCells + cs - W], lds[6 * kCells + cs - W + WH + 1]};
+        p[7] = f2{lds[7 * kCells + cs + W], lds[7 * kCells + cs + W + WH + 1]};
+      };
+      f2 p[9], outs[9];
+      read_pair(ofx, ofy, p);
+      p[0] = own0;
+      const uint32_t mbits = ofl & 3u;
+      const bool counted = COUNT ? (ofl & 32u) != 0u : (ofl & 4u) != 0u;
+      acc[j - 1] = relax(p, mbits, (!last || a.accel_last) && (ofl & 8u), counted ? mbits : 3u, outs);
+      own0 = outs[0];
+      if constexpr (!last) {
+        // the ring pair's populations are READ before the barrier and relaxed after it, once the owned results are stored: a lane
+        // never holds the results of one pair while it computes the other
+        f2 q[9];
+        int rfx = 0, rfy = 0;
+        uint32_t rfl = 0;
+        const bool ring = tid < G::ring_pairs(j);
+        if (ring) {
+          ring_pos(jc, tid, rfx, rfy);
+          rfl = pair_flags[(rfy * W + rfx) >> 1];
+          read_pair(rfx, rfy, q);
+          q[0] = *reinterpret_cast<const f2*>(lds + rfy * W + rfx - rd);
+        }
+        __syncthreads();                       // every lane has read its neighbours
+        if (ofl & 16u) {
+  #pragma unroll
+          for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, ofy * W - wr, ofx, outs[k]);
+        }
+        if (ring) {
+          f2 routs[9];
+          relax(q, rfl & 3u, (rfl & 8u) != 0u, 3u, routs);
+          if (rfl & 16u) {
+  #pragma unroll
+            for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, rfy * W - wr, rfx, routs[k]);
+          }
+        }
+        __syncthreads();
+      } else if (ofl & 4u) {
+        // a kept pair lies inside the grid: its cell index needs no periodic wrap
+        const uint32_t o = 4u * static_cast<uint32_t>(tile_row_base + __mul24(py, nx) + x0 + ofx - EX);
+  #pragma unroll
+        for (int k = 0; k < 9; ++k) __builtin_nontemporal_store(outs[k], &at_byte<f2>(a.dstk[k], o));
+      }
+      LBM_MSTAMP(1 + j);
+    };
+    in_lds_substep(std::integral_constant<int, 2>{});
+    if constexpr (K >= 3) in_lds_substep(std::integral_constant<int, K >= 3 ? 3 : 2>{});
+    if constexpr (K >= 4) in_lds_substep(std::integral_constant<int, K >= 4 ? 4 : 2>{});
+  };
+  auto substeps = [&](auto count_c) __attribute__((always_inline)) {
+    if constexpr (G::owned_lanes) owned_substeps(count_c);
+    else k_substeps(count_c);
+  };
+
   if constexpr (PART == kPartGhost) {
-    if (sy0 >= a.count_first && sy0 + TY <= a.count_end) k_substeps(std::false_type{});       // every row of the tile counts
-    else k_substeps(std::true_type{});
+    if (sy0 >= a.count_first && sy0 + TY <= a.count_end) substeps(std::false_type{});       // every row of the tile counts
+    else substeps(std::true_type{});
   } else if constexpr (PART == kPartTile) {
-    if (sy0 >= a.count_first && sy0 + TY <= a.count_end && x0 >= a.cx0 && x0 + TX <= a.cx1) k_substeps(std::false_type{});   // ... and every column
-    else k_substeps(std::true_type{});
+    if (sy0 >= a.count_first && sy0 + TY <= a.count_end && x0 >= a.cx0 && x0 + TX <= a.cx1) substeps(std::false_type{});   // ... and every column
+    else substeps(std::true_type{});
   } else {
-    k_substeps(std::false_type{});
+    substeps(std::false_type{});
   }
 
   // per-step sums over the owned cells of this tile
-  if constexpr (TERMS == kTermsCompensated) {
+  if constexpr (TERMS == kTermsCompensated && !G::owned_lanes) {
 #pragma unroll
     for (int i = 0; i < K; ++i) acc[i] += static_cast<double>(acc_lo[i]);
   }
