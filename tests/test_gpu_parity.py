@@ -13,6 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import readout_ref
 from conftest import GOLDEN, deck_paths
 
 pytestmark = pytest.mark.gpu
@@ -256,6 +257,8 @@ def test_device_av_velocity_matches_host(lbm, digests):
     host = lbm.av_velocity_host(p, cells, obst)
     dev = s.partition.av_velocity_sum()
     assert abs(dev - host) / host < 1e-5
+    exact = readout_ref.velocity_sum(cells, obst)             # exactly rounded: what is left is the device's summation order
+    assert abs(dev - exact) <= readout_ref.velocity_sum_bound(p.nx * p.ny) * exact
     s.close()
 
 
@@ -343,6 +346,7 @@ def test_full_size_8192_properties_and_short_parity(lbm, oracle):
         if digest is None:
             assert np.array_equal(bits(ring.local_cells()), bits(ref_cells))
             digest = ring.partition.checksum()
+            assert digest == readout_ref.digest_rows(ref_cells, chunk_rows=256)      # the host restatement of the documented formula: here the digest is the only witness
             half = ring.partition.checksum(0, n // 2) + ring.partition.checksum(n // 2, n)
             assert half % (1 << 64) == digest                      # additive over disjoint row ranges
         else:
@@ -1645,10 +1649,13 @@ def test_av_velocity_sum_on_a_k_step_partition_with_unaligned_ghost_rows(lbm, mo
     sim = lbm.Simulation(p, obst, flags=lbm._capi.FLAG_FORCE_HALO, exchange="p2p", strict=True)
     assert sim.partition.macro_steps == 3
     sim.run(30)
-    host = lbm.av_velocity_host(p, sim.local_cells(), obst)
+    cells = sim.local_cells()
+    host = lbm.av_velocity_host(p, cells, obst)
     dev = sim.partition.av_velocity_sum()
     sim.close()
     assert abs(dev - host) / host < 1e-5
+    exact = readout_ref.velocity_sum(cells, obst)             # exactly rounded: what is left is the device's summation order
+    assert abs(dev - exact) <= readout_ref.velocity_sum_bound(p.nx * p.ny) * exact
 
 
 @pytest.mark.parametrize("K", [0, 3])
