@@ -9,15 +9,16 @@ namespace {
 // K steps per pass over HBM for bandwidth-bound grids: lbm_multi_kernel<K>.
 //
 // The one-step kernel moves 72 B per cell-step and sits at ~90 % of what HBM delivers; the only way
-// further up is to touch memory less often.  Here a 512-lane block owns a 64x16 tile and advances it
-// by up to K steps per launch: sub-step 1 pulls straight from the source grid (as the one-step kernel
+// further up is to touch memory less often.  Here a block owns a TX x TY tile (MultiGeom below: 64 x 16 on
+// 512 lanes for K <= 3; 64 x 13, 32 x 13 or, on 768 lanes, 64 x 24 for K = 4) and advances it
+// by K steps per launch: sub-step 1 pulls straight from the source grid (as the one-step kernel
 // does) for the tile plus a (K-1)-cell ring and keeps the result in LDS; sub-steps 2..K update that
 // LDS frame in place (neighbours read into registers, barrier, results written back), each on a
 // region one cell smaller; the last sub-step covers exactly the owned tile and writes the
 // destination grid.  The ring is recomputed redundantly by the neighbouring blocks with the same
 // arithmetic, so no block ever waits for another, and the results are bit-identical to K launches of
-// the one-step kernel.  HBM traffic per K steps: (64+2K)(16+2K)/1024 x 36 B read + 36 B written
-// (K = 2: 84 B instead of 144 B; K = 4: 97 B instead of 288 B).
+// the one-step kernel.  HBM traffic per K steps, on 64 x 16 tiles: (64+2K)(16+2K)/1024 x 36 B read + 36 B
+// written (K = 2: 84 B instead of 144 B; K = 4: 97 B instead of 288 B).
 //
 // Dealing of lanes.  k_substeps deals each region's pairs row after row over the block, in passes of
 // whole rows (sub-steps 1 - 3 of the tall K = 4 launch take two passes each), every pair with the
@@ -25,6 +26,8 @@ namespace {
 // x-pair per lane, runs owned_substeps instead: each lane keeps its owned pair for the whole launch
 // (flags and population 0 in registers), and the ring pairs are extra, term-free items on the first
 // lanes, one per lane and sub-step, so that each in-LDS sub-step is a single read / barrier / write.
+// What is not the dealing itself — the source pull, the kept / counted tests, the flag byte, the frame read,
+// the destination index — is written once at kernel scope (pull, classify, pair_flag_bits, read_pair, kept_cell).
 //
 // Rows outside the partition: `y_periodic` wraps (self-contained domain); otherwise the storage has
 // `ghost` extra rows below and above the owned rows, filled by the neighbours before the launch.
@@ -49,26 +52,13 @@ constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY
               kMaxGroup = 8;       // most launches of such a group
 constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall) : (kMTY4 < kMTY4Tall ? kMTY4 : kMTY4Tall);
 // Geometry of a launch: tile width, and by steps per launch tile height and block size.
-//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4 on the same tiles
-//                (rounds 1-2) needed a 76 x 22 frame = 60 KB, two blocks per CU: 353 - 363 us/step at 8192 x 8192 against 341 - 347 for
-//                K = 3.  On 64 x 13 tiles (round 3) its frame is 72 x 19 = 49.0 KB (76 x 19 = 52.0 KB until round 4), three blocks per CU again: a tile recomputes 1.36 x
-//                its cells per step instead of 1.31 x but the launch moves 21.5 B per cell-step instead of 26.9 — 8192 x 8192 346.6
-//                (K = 3) -> 324.0, 4096 x 4096 87.2 -> 78.4, 1024 x 1024 8.16 -> 7.07, 8192 x 1024 53.0 -> 43.5 (profiles/r03/ab_k3_k4.txt).
-//   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24
-//                waves): 60 wave-passes per tile.  Until round 4 the columns grew by 2 (K - j) (multi_ex below) and the tiles were 64 x 23:
-//                76 x 29 frame = 79.3 KB (64 x 24 did not fit two blocks), ring work 1.24 x, 60 wave-passes for 1.77 x the cells of 37.
-//                The even-rounded growth and the 24th row, 8192 x 8192 in one process, us/step min of two interleaved runs each: 64 x 23 with
-//                the old growth 284.4 / 282.9, with the new 277.7 / 278.8, 64 x 24 269.6 / 272.0 (SQ_INSTS_VALU per launch 557.9 M ->
-//                535.9 M -> 529.3 M, FETCH_SIZE equal or lower: profiles/r05/).  Round 4, on 76-wide frames: with double-precision sum|u| terms
-//                this was a draw (310.8 against 311.9 - 317.3, ab_k4_big_blocks_8192.txt); the launch runs at the socket power limit, and with
-//                the compensated float terms the form that does less work per cell wins wherever a launch is rounds of blocks — us/step
-//                64 x 13 / 64 x 21 / 64 x 22 / 64 x 23 (768 lanes): 8192 x 8192 315.0 & 324.7 / 304.6 / 307.7 / 303.9, 4096 x 4096 81.0 & 85.4 /
-//                77.5 / 75.6 / 74.0, 8192 x 1024 43.6 & 44.1 / 40.5 / 40.2 / 39.9, 2048 x 2048 22.3 & 22.8 / 22.3 / 21.5 / 21.6, 1024 x 1024
-//                6.98 & 7.25 / 7.58 / 6.93 / 6.81 (ab_big_blocks_matrix.txt; 832-, 896- and 1024-lane blocks spill: 500 us/step) — and
-//                loses where it is one round or less (512 slots instead of 768): 768 x 768 4.91 against 4.56, 1024 x 768 6.20 / 5.57,
-//                1536 x 1536 13.1 / 13.1 (ab_k3_k4_threshold_768lanes.txt): the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.
+//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4: 64 x 13 (72 x 19 frame,
+//                49.0 KB, three blocks per CU).
+//   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24 waves);
+//                the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.
 //   kGeomNarrow  32-wide tiles, heights as kGeomStd: partitions so small that a launch is one round of blocks (twice the tiles, each
 //                with half the dependent work — a 1024 x 128-row partition keeps 256 CUs busy instead of 128).
+// The measurements behind each choice, round by round: DESIGN_APPENDIX.md R8.1.
 constexpr int kGeomStd = 0, kGeomNarrow = 1, kGeomTall = 2;
 constexpr int geom_tx(int g) { return g == kGeomNarrow ? kMTXNarrow : kMTX; }
 constexpr int multi_ty(int k, int g) { return k >= 4 ? (g == kGeomTall ? kMTY4Tall : kMTY4) : kMTY; }
@@ -206,6 +196,19 @@ __device__ __forceinline__ void accelerate_pair(f2 (&out)[9], uint32_t mbits, bo
 // of a rank of the 2-D decomposition: ghost rows AND ghost columns — the counted and kept tests in x as well, in the tiles on the rim of
 // the owned block only — and four ready words; the forms above do not change for it).
 constexpr int kPartPlain = 0, kPartGhost = 1, kPartReady = 2, kPartTile = 3;
+
+// The flag byte of an x-pair of the frame, written by sub-step 1 and read by the in-LDS sub-steps (which then need no grid
+// coordinates at all); bits 0-1 are the pair's obstacle bits.  0: the pair was not computed.
+constexpr uint32_t kPairObstacles = 3u,
+                   kPairKept = 4u,       // inside the owned tile and the grid: the last sub-step writes it to the destination grid
+                   kPairAccelRow = 8u,   // on the global accelerate row ny - 2
+                   kPairComputed = 16u,
+                   kPairCounted = 32u;   // owned by this partition: enters the per-step sums (set in the COUNT form only: elsewhere kept pairs count)
+__device__ __forceinline__ uint32_t pair_flag_bits(uint32_t mbits, bool kept, bool accel_row, bool counted)
+{
+  return mbits | (kept ? kPairKept : 0u) | (accel_row ? kPairAccelRow : 0u) | kPairComputed | (counted ? kPairCounted : 0u);
+}
+
 template <int K, int TERMS, int GEOM, int PART>   // TERMS: form of the sum|u| terms (kTermsCompensated by default), see finish_pair_lo; GEOM: kGeomStd / Narrow / Tall
 __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEOM>::waves_per_simd)) lbm_multi_kernel(const MultiArgs a)
 {
@@ -213,22 +216,15 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   constexpr int TX = G::TX, EX = G::EX, EY = G::EY, W = G::W, WH = G::W / 2, kCells = G::cells, kLanes = G::LANES, kWaves = kLanes / 64, TY = G::TY;
   extern __shared__ __attribute__((aligned(16))) float lds[];      // [9][kCells], then [K][kWaves] doubles
   double* red = reinterpret_cast<double*>(lds + 9 * kCells);
-  // per x-pair of the frame, written by sub-step 1 and read by the in-LDS sub-steps (which then need no
-  // grid coordinates at all): bits 0-1 obstacle bits, 2 owned (kept: written to the destination grid), 3 on the accelerate row,
-  // 4 computed, 5 counted (owned by this partition: enters the per-step sums)
-  uint8_t* pair_flags = reinterpret_cast<uint8_t*>(red + K * kWaves);
+  uint8_t* pair_flags = reinterpret_cast<uint8_t*>(red + K * kWaves);   // a flag byte (kPair*) per x-pair of the frame
   const int tid = threadIdx.x;
 
   if (blockIdx.x == 0) {
-    if constexpr (PART == kPartReady) {
+    constexpr int kReadyWords = PART == kPartTile ? 4 : PART == kPartReady ? 2 : 0;   // south, north (a.ready), west, east (a.ready_x)
+    if constexpr (kReadyWords > 0) {
       if (a.ready_epoch != 0ull && tid == 0) {
-        for (int d = 0; d < 2; ++d) __hip_atomic_store(a.ready[d], a.ready_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    }
-    if constexpr (PART == kPartTile) {
-      if (a.ready_epoch != 0ull && tid == 0) {
-        for (int d = 0; d < 2; ++d) __hip_atomic_store(a.ready[d], a.ready_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        for (int d = 0; d < 2; ++d) __hip_atomic_store(a.ready_x[d], a.ready_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#pragma unroll
+        for (int d = 0; d < kReadyWords; ++d) __hip_atomic_store(d < 2 ? a.ready[d] : a.ready_x[d - 2], a.ready_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
     // fold block: the previous launch's per-tile sums, one vector per step, into sums[counter..]
@@ -247,11 +243,8 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     }
     __syncthreads();
     if (tid == 0 && a.n_prev_vecs > 0) *a.counter += a.n_prev_vecs;
-    if constexpr (PART == kPartReady) {
-      if (a.wait_ready && tid == 0) p2p_wait_flags(a.wait_ready, nullptr, 2, a.ready_epoch, 0ull, a.timeout_ticks, a.err, /*acquire=*/false);
-    }
-    if constexpr (PART == kPartTile) {
-      if (a.wait_ready && tid == 0) p2p_wait_flags(a.wait_ready, nullptr, 4, a.ready_epoch, 0ull, a.timeout_ticks, a.err, /*acquire=*/false);
+    if constexpr (kReadyWords > 0) {
+      if (a.wait_ready && tid == 0) p2p_wait_flags(a.wait_ready, nullptr, kReadyWords, a.ready_epoch, 0ull, a.timeout_ticks, a.err, /*acquire=*/false);
     }
     return;
   }
@@ -289,7 +282,6 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   const int nx = a.nx;
   constexpr bool XR = PART == kPartTile;            // ghost columns: kept / counted column ranges
   const int rows_storage = (PART == kPartGhost || PART == kPartTile) ? a.rows_storage : a.rows_compute + 2 * a.row_first;   // (owned rows only: row_first ghost rows on each side)
-  [[maybe_unused]] const int row_end = a.row_first + a.rows_compute;   // first storage row past the rows this launch computes
   const int tile_row_base = sy0 * nx;               // block-uniform: a scalar multiply
   const int grid_cells = rows_storage * nx;
   constexpr int ksteps = K;
@@ -305,8 +297,9 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     if (d < 0) d += a.ny_global;
     tile_accel = d < G::H || a.ny_global < G::H;
   }
-  // storage row -> does it hold the global accelerate row ny-2 ?
-  auto on_accel_row = [&](int sr) {
+  // storage row (after any periodic wrap) -> does it hold the global accelerate row ny-2 ?
+  auto on_accel_row = [&](int sr) __attribute__((always_inline)) {
+    if (!tile_accel) return false;
     int g = a.y0_global + sr - a.row_first;
     if (g < 0) g += a.ny_global; else if (g >= a.ny_global) g -= a.ny_global;
     return g == a.accel_row;
@@ -317,8 +310,97 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   const bool inner = x0 - EX >= 2 && x0 + TX + EX + 2 <= nx && sy0 - EY >= 1 && sy0 + TY + EY + 1 <= rows_storage &&
                      sy0 + TY <= a.row_first + a.rows_compute;
 
+  // ---- what both dealings of the lanes (k_substeps, owned_substeps below) share: the pair at frame position (fx, fy), fx even
+
+  // Sub-step 1's sources of the pair, pulled from the source grid: its nine populations, obstacle bits, storage row `sr` (after
+  // any periodic wrap) and byte offset `o_here` within a plane.  false: a row past the storage (a row partition whose rows the
+  // tile height does not divide: the last tile row sticks out past the ghost rows), outside every owned cell's dependency cone
+  // and not computed.
+  auto pull = [&](const int fx, const int fy, f2 (&p)[9], uint32_t& mbits, int& sr, uint32_t& o_here) __attribute__((always_inline)) -> bool {
+    int gx = x0 + fx - EX;
+    sr = sy0 + fy - EY;
+    // One multiply per pair, and a 24-bit one (v_mul_lo_u32 and v_mad_u64_u32 issue at quarter rate: the three
+    // products sr * nx, ys * nx, yn * nx were 48 cycles of a pass): the tile's first row is a scalar product, the row
+    // inside the frame a small factor (nx < 2^23 is part of the kernel's eligibility), the rows above and below and
+    // the periodic wraps are additions.
+    int cell = tile_row_base + __mul24(fy - EY, nx) + gx;
+    int d_south = -nx, d_north = nx;
+    if (!inner) {
+      if (gx < 0) { gx += nx; cell += nx; } else if (gx >= nx) { gx -= nx; cell -= nx; }      // periodic (:527-529)
+      if (!a.y_periodic && sr + 1 >= rows_storage) return false;
+      if (a.y_periodic) {                                                               // periodic (:245-247)
+        if (sr < 0) { sr += rows_storage; cell += grid_cells; } else if (sr >= rows_storage) { sr -= rows_storage; cell -= grid_cells; }
+        if (sr == 0) d_south = grid_cells - nx;
+        if (sr + 1 >= rows_storage) d_north = nx - grid_cells;
+      }
+    }
+    // three 32-bit byte offsets per lane on block-uniform plane bases (scalar base + vector offset
+    // addressing: no 64-bit address arithmetic in the vector unit; the x -+ 1 shifts live in the bases)
+    o_here = 4u * static_cast<uint32_t>(cell);
+    const uint32_t o_south = 4u * static_cast<uint32_t>(cell + d_south);
+    const uint32_t o_north = 4u * static_cast<uint32_t>(cell + d_north);
+    p[0] = at_byte<f2>(a.srck[0], o_here);                                           // :530-538
+    p[2] = at_byte<f2>(a.srck[2], o_south);
+    p[4] = at_byte<f2>(a.srck[4], o_north);
+    p[1] = at_byte<f2u>(a.srck[1] - 1, o_here);
+    p[5] = at_byte<f2u>(a.srck[5] - 1, o_south);
+    p[8] = at_byte<f2u>(a.srck[8] - 1, o_north);
+    p[3] = at_byte<f2u>(a.srck[3] + 1, o_here);
+    p[6] = at_byte<f2u>(a.srck[6] + 1, o_south);
+    p[7] = at_byte<f2u>(a.srck[7] + 1, o_north);
+    if (!inner) {
+      if (gx == 0) {                        // x_w wraps to nx-1 (:529)
+        p[1].x = at_byte<float>(a.srck[1] + nx - 1, o_here); p[5].x = at_byte<float>(a.srck[5] + nx - 1, o_south);
+        p[8].x = at_byte<float>(a.srck[8] + nx - 1, o_north);
+      }
+      if (gx == nx - 2) {                   // x_e wraps to 0 (:527-528)
+        p[3].y = at_byte<float>(a.srck[3] + 2 - nx, o_here); p[6].y = at_byte<float>(a.srck[6] + 2 - nx, o_south);
+        p[7].y = at_byte<float>(a.srck[7] + 2 - nx, o_north);
+      }
+    }
+    mbits = (at_byte<uint32_t>(a.mask, 4u * (static_cast<uint32_t>(cell) >> 5)) >> (cell & 31)) & 3u;
+    return true;
+  };
+  // Is the pair kept (written to the destination grid) and counted (in the per-step sums) ?  kept = inside the owned tile (`own`)
+  // AND inside the grid (the last tile column / row may stick out of a grid whose edges are not multiples of the tile: those
+  // cells are periodic images, computed but not kept).  COUNT (see the forms below): the tile holds rows or columns that are
+  // computed but not counted.  (The grid test behind `if (!inner)`: as one && chain it cost the K = 2 and K = 3 ghost-row
+  // instantiations a 63rd VGPR.)
+  auto classify = [&](auto count_c, const int fx, const int fy, const bool own, bool& kept, bool& counted) __attribute__((always_inline)) {
+    constexpr bool COUNT = decltype(count_c)::value;
+    const int srow = sy0 + fy - EY, gxo = x0 + fx - EX;               // the pair's storage row and column before any periodic wrap
+    kept = own;
+    if (!inner) kept = kept && gxo < nx && srow < a.row_first + a.rows_compute;
+    counted = COUNT ? (kept && srow >= a.count_first && srow < a.count_end) : kept;
+    if constexpr (XR && COUNT) {                                      // ghost columns: kept and counted column ranges (even bounds: whole pairs)
+      kept = kept && gxo >= a.keep_x0 && gxo < a.keep_x1;
+      counted = counted && kept && gxo >= a.cx0 && gxo < a.cx1;
+    }
+  };
+  // Populations 1 - 8 of the pair from the frame as the in-LDS sub-step that reads it finds it: stored `rd` dwords lower.
+  // Frame layout, per population: the three that are pulled without an x shift (0, 2, 4) keep their rows
+  // interleaved — a pair is one aligned ds_read_b64.  The six that are pulled from x -+ 1 have their rows stored
+  // DE-INTERLEAVED, odd-x cells first: a row is O[0..WH), E[0..WH) (WH = W/2).  For a pair (x, x+1), x = 2i, the
+  // west pulls are O[i-1], E[i] and the east pulls O[i], E[i+1]: one ds_read2_b32 each, ascending addresses in
+  // lane order (no register swap), lanes on consecutive dwords (interleaved, they were dword pairs at odd
+  // addresses with lane stride 2, two-way bank conflicts in both passes of the instruction).
+  auto read_pair = [&](const int rd, const int fx, const int fy, f2 (&p)[9]) __attribute__((always_inline)) {
+    const int ci = fy * W + fx - rd;                                   // interleaved planes: cell (fx, fy)
+    const int cs = fy * W + (fx >> 1) - rd;                            // split planes: O[i] of row fy; E[i] is WH further
+    p[2] = *reinterpret_cast<const f2*>(lds + 2 * kCells + ci - W);
+    p[4] = *reinterpret_cast<const f2*>(lds + 4 * kCells + ci + W);
+    p[1] = f2{lds[1 * kCells + cs - 1], lds[1 * kCells + cs + WH]};
+    p[5] = f2{lds[5 * kCells + cs - W - 1], lds[5 * kCells + cs - W + WH]};
+    p[8] = f2{lds[8 * kCells + cs + W - 1], lds[8 * kCells + cs + W + WH]};
+    p[3] = f2{lds[3 * kCells + cs], lds[3 * kCells + cs + WH + 1]};
+    p[6] = f2{lds[6 * kCells + cs - W], lds[6 * kCells + cs - W + WH + 1]};
+    p[7] = f2{lds[7 * kCells + cs + W], lds[7 * kCells + cs + W + WH + 1]};
+  };
+  // Cell index of a kept pair in the destination grid: it lies inside the grid, so its index needs no periodic wrap.
+  auto kept_cell = [&](const int fx, const int fy) __attribute__((always_inline)) { return tile_row_base + __mul24(fy - EY, nx) + x0 + fx - EX; };
+
   // The K sub-steps, in two forms: COUNT = the tile holds rows that are computed but not counted (a launch that also advances ghost rows:
-  // its first and last tile rows) — every pair then carries a `counted` bit beside `owned`; all other tiles, and every tile of the other
+  // its first and last tile rows) — every pair then carries a `counted` bit beside `kept`; all other tiles, and every tile of the other
   // launches, take the form without it, whose schedule is the one rounds 1 - 3 measured (see PART above: the test costs 2 - 3 % when every
   // tile carries it).  The choice is block-uniform.
   auto k_substeps = [&](auto count_c) __attribute__((always_inline)) {
@@ -332,75 +414,22 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       for (int i = tid; i < np; i += kLanes) {
         const int ry = i / wp, rp = i - ry * wp;
         const int fx = EX - ex + 2 * rp, fy = EY - ey + ry;               // LDS frame coordinates (fx even)
-        int gx = x0 + fx - EX;
-        int sr = sy0 + fy - EY;
-        // One multiply per pair, and a 24-bit one (v_mul_lo_u32 and v_mad_u64_u32 issue at quarter rate: the three
-        // products sr * nx, ys * nx, yn * nx were 48 cycles of a pass): the tile's first row is a scalar product, the row
-        // inside the frame a small factor (nx < 2^23 is part of the kernel's eligibility), the rows above and below and
-        // the periodic wraps are additions.
-        int cell = tile_row_base + __mul24(fy - EY, nx) + gx;
-        int d_south = -nx, d_north = nx;
-        if (!inner) {
-          if (gx < 0) { gx += nx; cell += nx; } else if (gx >= nx) { gx -= nx; cell -= nx; }      // periodic (:527-529)
-          // row partition whose rows the tile height does not divide: the last tile row sticks out past the
-          // ghost rows; those cells lie outside every owned cell's dependency cone and are skipped
-          if (!a.y_periodic && sr + 1 >= rows_storage) {
-            if (ksteps > 1) pair_flags[(fy * W + fx) >> 1] = 0;
-            continue;
-          }
-          if (a.y_periodic) {                                                               // periodic (:245-247)
-            if (sr < 0) { sr += rows_storage; cell += grid_cells; } else if (sr >= rows_storage) { sr -= rows_storage; cell -= grid_cells; }
-            if (sr == 0) d_south = grid_cells - nx;
-            if (sr + 1 >= rows_storage) d_north = nx - grid_cells;
-          }
+        f2 p[9], out[9];
+        uint32_t mbits = 0, o_here = 0;
+        int sr = 0;
+        if (!pull(fx, fy, p, mbits, sr, o_here)) {
+          if (ksteps > 1) pair_flags[(fy * W + fx) >> 1] = 0;
+          continue;
         }
-        // three 32-bit byte offsets per lane on block-uniform plane bases (scalar base + vector offset
-        // addressing: no 64-bit address arithmetic in the vector unit; the x -+ 1 shifts live in the bases)
-        const uint32_t o_here = 4u * static_cast<uint32_t>(cell);
-        const uint32_t o_south = 4u * static_cast<uint32_t>(cell + d_south);
-        const uint32_t o_north = 4u * static_cast<uint32_t>(cell + d_north);
-        f2 p[9];
-        p[0] = at_byte<f2>(a.srck[0], o_here);                                                   // :530
-        p[2] = at_byte<f2>(a.srck[2], o_south);                                         // :532
-        p[4] = at_byte<f2>(a.srck[4], o_north);                                         // :534
-        p[1] = at_byte<f2u>(a.srck[1] - 1, o_here);                                         // :531
-        p[5] = at_byte<f2u>(a.srck[5] - 1, o_south);                                    // :535
-        p[8] = at_byte<f2u>(a.srck[8] - 1, o_north);                                    // :538
-        p[3] = at_byte<f2u>(a.srck[3] + 1, o_here);                                     // :533
-        p[6] = at_byte<f2u>(a.srck[6] + 1, o_south);                                    // :536
-        p[7] = at_byte<f2u>(a.srck[7] + 1, o_north);                                    // :537
-        if (!inner) {
-          if (gx == 0) {                        // x_w wraps to nx-1 (:529)
-            p[1].x = at_byte<float>(a.srck[1] + nx - 1, o_here); p[5].x = at_byte<float>(a.srck[5] + nx - 1, o_south);
-            p[8].x = at_byte<float>(a.srck[8] + nx - 1, o_north);
-          }
-          if (gx == nx - 2) {                   // x_e wraps to 0 (:527-528)
-            p[3].y = at_byte<float>(a.srck[3] + 2 - nx, o_here); p[6].y = at_byte<float>(a.srck[6] + 2 - nx, o_south);
-            p[7].y = at_byte<float>(a.srck[7] + 2 - nx, o_north);
-          }
-        }
-        const uint32_t mbits = (at_byte<uint32_t>(a.mask, 4u * (static_cast<uint32_t>(cell) >> 5)) >> (cell & 31)) & 3u;
-        f2 out[9];
-        // owned = inside the tile AND inside the grid (the last tile column / row may stick out of a grid
-        // whose edges are not multiples of the tile: those cells are periodic images, computed but not kept)
-        const int srow = sy0 + fy - EY;                                   // the pair's storage row before any periodic wrap
-        const bool owned_rows = fx >= EX && fx < EX + TX && fy >= EY && fy < EY + TY &&
-                                (inner || (x0 + fx - EX < nx && sy0 + fy - EY < a.row_first + a.rows_compute));
-        const bool counted_rows = COUNT ? (owned_rows && srow >= a.count_first && srow < a.count_end) : owned_rows;
-        bool owned = owned_rows, counted = counted_rows;
-        if constexpr (XR && COUNT) {                                      // ghost columns: kept and counted column ranges (even bounds: whole pairs)
-          const int gxo = x0 + fx - EX;                                   // the pair's storage column before any periodic wrap
-          owned = owned_rows && gxo >= a.keep_x0 && gxo < a.keep_x1;
-          counted = counted_rows && owned && gxo >= a.cx0 && gxo < a.cx1;
-        }
-        bool accel_row_here = false;
-        if (tile_accel) accel_row_here = on_accel_row(sr);
+        bool kept, counted;
+        classify(count_c, fx, fy, fx >= EX && fx < EX + TX && fy >= EY && fy < EY + TY, kept, counted);
+        const bool accel_row_here = on_accel_row(sr);
         acc[0] += finish_pair_lo<TERMS>(p, mbits, a.omega, tile_accel, (ksteps > 1 || a.accel_last) && accel_row_here, a.accel_w1, a.accel_w2, counted ? mbits : 3u, out, acc_lo[0]);
         if (ksteps > 1) {
   #pragma unroll
           for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
-          pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(mbits | (owned ? 4u : 0u) | (accel_row_here ? 8u : 0u) | 16u | ((COUNT && counted) ? 32u : 0u));
-        } else if (owned) {
+          pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(pair_flag_bits(mbits, kept, accel_row_here, COUNT && counted));
+        } else if (kept) {
   #pragma unroll
           for (int k = 0; k < 9; ++k) __builtin_nontemporal_store(out[k], &at_byte<f2>(a.dstk[k], o_here));
         }
@@ -435,37 +464,20 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
           // region's first row) and only the write is predicated: no per-lane state to merge at the barrier
           if (__builtin_amdgcn_ballot_w64(in_region) != 0ull) {
             const int fy = EY - ey + (in_region ? r0 + ry : 0);
-            const int cf = fy * W + fx;                                    // frame position; stored rd (read) / wr (written) lower
-            const uint32_t fl = pair_flags[cf >> 1];
-            const bool lane_on = in_region && (fl & 16u);
-            // Frame layout, per population: the three that are pulled without an x shift (0, 2, 4) keep their rows
-            // interleaved — a pair is one aligned ds_read_b64.  The six that are pulled from x -+ 1 have their rows stored
-            // DE-INTERLEAVED, odd-x cells first: a row is O[0..WH), E[0..WH) (WH = W/2).  For a pair (x, x+1), x = 2i, the
-            // west pulls are O[i-1], E[i] and the east pulls O[i], E[i+1]: one ds_read2_b32 each, ascending addresses in
-            // lane order (no register swap), lanes on consecutive dwords (interleaved, they were dword pairs at odd
-            // addresses with lane stride 2, two-way bank conflicts in both passes of the instruction).
-            const int ci = cf - rd;                                        // interleaved planes: cell (fx, fy)
-            const int cs = fy * W + (fx >> 1) - rd;                        // split planes: O[i] of row fy; E[i] is WH further
+            const uint32_t fl = pair_flags[(fy * W + fx) >> 1];
+            const bool lane_on = in_region && (fl & kPairComputed);
             f2 p[9];
-            p[0] = *reinterpret_cast<const f2*>(lds + 0 * kCells + ci);
-            p[2] = *reinterpret_cast<const f2*>(lds + 2 * kCells + ci - W);
-            p[4] = *reinterpret_cast<const f2*>(lds + 4 * kCells + ci + W);
-            p[1] = f2{lds[1 * kCells + cs - 1], lds[1 * kCells + cs + WH]};
-            p[5] = f2{lds[5 * kCells + cs - W - 1], lds[5 * kCells + cs - W + WH]};
-            p[8] = f2{lds[8 * kCells + cs + W - 1], lds[8 * kCells + cs + W + WH]};
-            p[3] = f2{lds[3 * kCells + cs], lds[3 * kCells + cs + WH + 1]};
-            p[6] = f2{lds[6 * kCells + cs - W], lds[6 * kCells + cs - W + WH + 1]};
-            p[7] = f2{lds[7 * kCells + cs + W], lds[7 * kCells + cs + W + WH + 1]};
-            const bool owned = lane_on && (fl & 4u);
-            const bool counted = COUNT ? (lane_on && (fl & 32u)) : owned;
+            p[0] = *reinterpret_cast<const f2*>(lds + fy * W + fx - rd);
+            read_pair(rd, fx, fy, p);
+            const bool kept = lane_on && (fl & kPairKept);
+            const bool counted = COUNT ? (lane_on && (fl & kPairCounted)) : kept;
             float term_lo = 0.0f;
-            const double term = finish_pair_lo<TERMS>(p, fl & 3u, a.omega, tile_accel, (!last || a.accel_last) && (fl & 8u), a.accel_w1, a.accel_w2,
-                                                      counted ? (fl & 3u) : 3u, outs, term_lo);
+            const double term = finish_pair_lo<TERMS>(p, fl & kPairObstacles, a.omega, tile_accel, (!last || a.accel_last) && (fl & kPairAccelRow), a.accel_w1, a.accel_w2,
+                                                      counted ? (fl & kPairObstacles) : 3u, outs, term_lo);
   #pragma unroll
             for (int m = 1; m < K; ++m)
               if (m == j - 1) { acc[m] += term; acc_lo[m] += term_lo; }
-            // an owned pair lies inside the grid: its cell index needs no periodic wrap
-            slot = !lane_on ? -1 : last ? (owned ? tile_row_base + __mul24(fy - EY, nx) + x0 + fx - EX : -1) : fy * W - wr;   // in LDS: the row; fx is added below
+            slot = !lane_on ? -1 : last ? (kept ? kept_cell(fx, fy) : -1) : fy * W - wr;   // in LDS: the row; fx is added below
           }
           if (!last) {
             __syncthreads();                     // every lane of the pass has read its neighbours
@@ -494,9 +506,8 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   // The ring of each region (312 / 184 / 116 pairs at K = 4) is extra, term-free work on the first lanes: sub-step 1 runs one ring
   // item after the owned pass; sub-step j < K relaxes the owned pair and, on those lanes, reads one ring pair, meets at ONE barrier,
   // then relaxes the ring pair and writes both (the dealing above takes two passes for each of sub-steps 1 - 3, every pair with the
-  // term code).  Each lane adds exactly one
-  // pair's term per sub-step: acc[j-1] is that term, its compensated low part already added.  Plane 0 and the flag byte are kept in
-  // LDS for ring pairs only.
+  // term code).  Each lane adds exactly one pair's term per sub-step: acc[j-1] is that term, its compensated low part already added.
+  // Plane 0 and the flag byte are kept in LDS for ring pairs only.
   auto owned_substeps = [&](auto count_c) __attribute__((always_inline)) {
     constexpr bool COUNT = decltype(count_c)::value;
     constexpr int TP = TX / 2;                                         // owned pairs per tile row
@@ -521,47 +532,6 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       if (tile_accel) accelerate_pair(out, mbits, accel, a.accel_w1, a.accel_w2);
       return term;
     };
-    // sub-step 1's sources of frame pair (fx, fy), as k_substeps pulls them; false: a row past the storage (a row partition
-    // whose rows the tile height does not divide), outside every owned cell's dependency cone and not computed
-    auto pull = [&](const int fx, const int fy, f2 (&p)[9], uint32_t& mbits, int& sr) __attribute__((always_inline)) -> bool {
-      int gx = x0 + fx - EX;
-      sr = sy0 + fy - EY;
-      int cell = tile_row_base + __mul24(fy - EY, nx) + gx;
-      int d_south = -nx, d_north = nx;
-      if (!inner) {
-        if (gx < 0) { gx += nx; cell += nx; } else if (gx >= nx) { gx -= nx; cell -= nx; }      // periodic (:527-529)
-        if (!a.y_periodic && sr + 1 >= rows_storage) return false;
-        if (a.y_periodic) {                                                               // periodic (:245-247)
-          if (sr < 0) { sr += rows_storage; cell += grid_cells; } else if (sr >= rows_storage) { sr -= rows_storage; cell -= grid_cells; }
-          if (sr == 0) d_south = grid_cells - nx;
-          if (sr + 1 >= rows_storage) d_north = nx - grid_cells;
-        }
-      }
-      const uint32_t o_here = 4u * static_cast<uint32_t>(cell);
-      const uint32_t o_south = 4u * static_cast<uint32_t>(cell + d_south);
-      const uint32_t o_north = 4u * static_cast<uint32_t>(cell + d_north);
-      p[0] = at_byte<f2>(a.srck[0], o_here);                                           // :530-538
-      p[2] = at_byte<f2>(a.srck[2], o_south);
-      p[4] = at_byte<f2>(a.srck[4], o_north);
-      p[1] = at_byte<f2u>(a.srck[1] - 1, o_here);
-      p[5] = at_byte<f2u>(a.srck[5] - 1, o_south);
-      p[8] = at_byte<f2u>(a.srck[8] - 1, o_north);
-      p[3] = at_byte<f2u>(a.srck[3] + 1, o_here);
-      p[6] = at_byte<f2u>(a.srck[6] + 1, o_south);
-      p[7] = at_byte<f2u>(a.srck[7] + 1, o_north);
-      if (!inner) {
-        if (gx == 0) {
-          p[1].x = at_byte<float>(a.srck[1] + nx - 1, o_here); p[5].x = at_byte<float>(a.srck[5] + nx - 1, o_south);
-          p[8].x = at_byte<float>(a.srck[8] + nx - 1, o_north);
-        }
-        if (gx == nx - 2) {
-          p[3].y = at_byte<float>(a.srck[3] + 2 - nx, o_here); p[6].y = at_byte<float>(a.srck[6] + 2 - nx, o_south);
-          p[7].y = at_byte<float>(a.srck[7] + 2 - nx, o_north);
-        }
-      }
-      mbits = (at_byte<uint32_t>(a.mask, 4u * (static_cast<uint32_t>(cell) >> 5)) >> (cell & 31)) & 3u;
-      return true;
-    };
     const int py = tid / TP, ofx = EX + 2 * (tid - py * TP), ofy = EY + py;
     f2 own0 = f2{0.0f, 0.0f};                                          // population 0 of the owned pair
     uint32_t ofl = 0;                                                  // its flag bits; 0: not computed
@@ -573,26 +543,17 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       int fx = ofx, fy = ofy;
       if (!own) ring_pos(std::integral_constant<int, 1>{}, tid, fx, fy);
       f2 p[9];
-      uint32_t mbits = 0, fl = 0;
+      uint32_t mbits = 0, fl = 0, o_here = 0;
       int sr = 0;
-      if (pull(fx, fy, p, mbits, sr)) {
-        // kept = an owned pair inside the grid (the last tile column / row may stick out of a grid whose edges are not multiples of the tile)
-        const int srow = sy0 + fy - EY;                                // storage row before any periodic wrap
-        const bool kept_rows = own && (inner || (x0 + fx - EX < nx && srow < a.row_first + a.rows_compute));
-        const bool counted_rows = COUNT ? (kept_rows && srow >= a.count_first && srow < a.count_end) : kept_rows;
-        bool kept = kept_rows, counted = counted_rows;
-        if constexpr (XR && COUNT) {
-          const int gxo = x0 + fx - EX;
-          kept = kept_rows && gxo >= a.keep_x0 && gxo < a.keep_x1;
-          counted = counted_rows && kept && gxo >= a.cx0 && gxo < a.cx1;
-        }
-        bool accel_row_here = false;
-        if (tile_accel) accel_row_here = on_accel_row(sr);
+      if (pull(fx, fy, p, mbits, sr, o_here)) {
+        bool kept, counted;
+        classify(count_c, fx, fy, own, kept, counted);
+        const bool accel_row_here = on_accel_row(sr);
         f2 out[9];
         const double term = relax(p, mbits, accel_row_here, counted ? mbits : 3u, out);
   #pragma unroll
         for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
-        fl = mbits | (kept ? 4u : 0u) | (accel_row_here ? 8u : 0u) | 16u | ((COUNT && counted) ? 32u : 0u);
+        fl = pair_flag_bits(mbits, kept, accel_row_here, COUNT && counted);
         if (own) {
           acc[0] = term;
           own0 = out[0];
@@ -611,24 +572,12 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       constexpr int j = decltype(jc)::value;
       constexpr bool last = j == K;
       constexpr int rd = (j - 2) * W, wr = (j - 1) * W;                // storage shift of the frame read / written
-      // populations 1 - 8 of pair (fx, fy), from the frame layout k_substeps describes
-      auto read_pair = [&](const int fx, const int fy, f2 (&p)[9]) __attribute__((always_inline)) {
-        const int ci = fy * W + fx - rd, cs = fy * W + (fx >> 1) - rd;
-        p[2] = *reinterpret_cast<const f2*>(lds + 2 * kCells + ci - W);
-        p[4] = *reinterpret_cast<const f2*>(lds + 4 * kCells + ci + W);
-        p[1] = f2{lds[1 * kCells + cs - 1], lds[1 * kCells + cs + WH]};
-        p[5] = f2{lds[5 * kCells + cs - W - 1], lds[5 * kCells + cs - W + WH]};
-        p[8] = f2{lds[8 * kCells + cs + W - 1], lds[8 * kCells + cs + W + WH]};
-        p[3] = f2{lds[3 * kCells + cs], lds[3 * kCells + cs + WH + 1]};
-        p[6] = f2{lds[6 * kCells + cs - W], lds[6 * kCells + cs - W + WH + 1]};
-        p[7] = f2{lds[7 * kCells + cs + W], lds[7 * kCells + cs + W + WH + 1]};
-      };
       f2 p[9], outs[9];
-      read_pair(ofx, ofy, p);
+      read_pair(rd, ofx, ofy, p);
       p[0] = own0;
-      const uint32_t mbits = ofl & 3u;
-      const bool counted = COUNT ? (ofl & 32u) != 0u : (ofl & 4u) != 0u;
-      acc[j - 1] = relax(p, mbits, (!last || a.accel_last) && (ofl & 8u), counted ? mbits : 3u, outs);
+      const uint32_t mbits = ofl & kPairObstacles;
+      const bool counted = (ofl & (COUNT ? kPairCounted : kPairKept)) != 0u;
+      acc[j - 1] = relax(p, mbits, (!last || a.accel_last) && (ofl & kPairAccelRow), counted ? mbits : 3u, outs);
       own0 = outs[0];
       if constexpr (!last) {
         // the ring pair's populations are READ before the barrier and relaxed after it, once the owned results are stored: a lane
@@ -640,26 +589,25 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         if (ring) {
           ring_pos(jc, tid, rfx, rfy);
           rfl = pair_flags[(rfy * W + rfx) >> 1];
-          read_pair(rfx, rfy, q);
+          read_pair(rd, rfx, rfy, q);
           q[0] = *reinterpret_cast<const f2*>(lds + rfy * W + rfx - rd);
         }
         __syncthreads();                       // every lane has read its neighbours
-        if (ofl & 16u) {
+        if (ofl & kPairComputed) {
   #pragma unroll
           for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, ofy * W - wr, ofx, outs[k]);
         }
         if (ring) {
           f2 routs[9];
-          relax(q, rfl & 3u, (rfl & 8u) != 0u, 3u, routs);
-          if (rfl & 16u) {
+          relax(q, rfl & kPairObstacles, (rfl & kPairAccelRow) != 0u, 3u, routs);
+          if (rfl & kPairComputed) {
   #pragma unroll
             for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, rfy * W - wr, rfx, routs[k]);
           }
         }
         __syncthreads();
-      } else if (ofl & 4u) {
-        // a kept pair lies inside the grid: its cell index needs no periodic wrap
-        const uint32_t o = 4u * static_cast<uint32_t>(tile_row_base + __mul24(py, nx) + x0 + ofx - EX);
+      } else if (ofl & kPairKept) {
+        const uint32_t o = 4u * static_cast<uint32_t>(kept_cell(ofx, ofy));
   #pragma unroll
         for (int k = 0; k < 9; ++k) __builtin_nontemporal_store(outs[k], &at_byte<f2>(a.dstk[k], o));
       }

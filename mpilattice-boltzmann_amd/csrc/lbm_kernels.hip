@@ -13,7 +13,7 @@
 //   av_vels[tt-1]          d2q9-bgk.c:367          block 0 of the next launch folds the partials
 //
 // Kernels (all produce the same bits; lbm_run / the partitioned loops pick by grid):
-//   kernels/multi.h  lbm_multi_kernel<K>                K steps per pass over HBM, 64x16 tiles, intermediate
+//   kernels/multi.h  lbm_multi_kernel<K>                K steps per pass over HBM, 64x16 / 64x13 / 64x24 tiles, intermediate
 //                                                       states in LDS — large grids and K-step row partitions
 //   kernels/tile.h   lbm_tile_kernel<T,H>               up to H steps per launch, launch-latency-bound small grids
 //   kernels/step.h   lbm_step_kernel / _narrow / _lds   one step per launch (4 cells or 1 cell per lane; the
@@ -36,6 +36,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -285,70 +286,35 @@ void launch_step(lbm_ctx* c, const StepArgs& a, int blocks, hipStream_t s)
   }
 }
 
-template <int K, int GEOM, int TERMS>
-void launch_multi_kgt(int blocks, hipStream_t s, const MultiArgs& a, int part)
+// Every instantiation of lbm_multi_kernel a context may launch, one row per (geometry, steps, terms, launch form) with what a launch
+// of it needs.  Rows of the tall geometry with K < 4 name the standard kernels (geom_for): no instantiation of their own.
+struct MultiKernel { void (*fn)(MultiArgs); int lanes; size_t lds_bytes; };
+constexpr int kMultiTerms = 3, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
+static_assert(kTermsDouble == 0 && kTermsFloat == 1 && kTermsCompensated == 2 && kPartPlain == 0 && kPartTile == 3 && kGeomTall == 2, "the values index the table");
+constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
+template <int ROW>
+constexpr MultiKernel multi_kernel_row()
 {
-  using G = MultiGeom<K, GEOM>;
-  if (part == kPartGhost) lbm_multi_kernel<K, TERMS, GEOM, kPartGhost><<<dim3(blocks + 1), dim3(G::LANES), G::lds_bytes, s>>>(a);
-  else if (part == kPartReady) lbm_multi_kernel<K, TERMS, GEOM, kPartReady><<<dim3(blocks + 1), dim3(G::LANES), G::lds_bytes, s>>>(a);
-  else if (part == kPartTile) lbm_multi_kernel<K, TERMS, GEOM, kPartTile><<<dim3(blocks + 1), dim3(G::LANES), G::lds_bytes, s>>>(a);
-  else lbm_multi_kernel<K, TERMS, GEOM, kPartPlain><<<dim3(blocks + 1), dim3(G::LANES), G::lds_bytes, s>>>(a);
+  constexpr int PART = ROW % kMultiParts, TERMS = ROW / kMultiParts % kMultiTerms, K = ROW / (kMultiParts * kMultiTerms) % kMaxMultiSteps + 1,
+                GEOM = geom_for(K, ROW / kMultiRowsPerGeom);
+  static_assert(multi_row(K, ROW / kMultiRowsPerGeom, TERMS, PART) == ROW, "multi_row and its inverse");
+  return {&lbm_multi_kernel<K, TERMS, GEOM, PART>, MultiGeom<K, GEOM>::LANES, MultiGeom<K, GEOM>::lds_bytes};
 }
+template <size_t... ROW>
+constexpr std::array<MultiKernel, sizeof...(ROW)> multi_kernel_rows(std::index_sequence<ROW...>) { return {{multi_kernel_row<static_cast<int>(ROW)>()...}}; }
+constexpr auto kMultiKernels = multi_kernel_rows(std::make_index_sequence<kMultiGeoms * kMultiRowsPerGeom>{});
 
 // Frames above the default limit of dynamic LDS (the tall geometry: 79 KB) need the limit raised — per DEVICE (a function attribute
 // belongs to the device's copy of the code object): called from lbm_create on the context's device, not from the first launch of a process.
-template <int K, int GEOM>
-hipError_t raise_multi_lds_limit()
-{
-  using G = MultiGeom<K, GEOM>;
-  if constexpr (G::lds_bytes > 65536) {
-    const void* fns[12] = {reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsDouble, GEOM, kPartPlain>), reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsFloat, GEOM, kPartPlain>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsCompensated, GEOM, kPartPlain>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsDouble, GEOM, kPartGhost>), reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsFloat, GEOM, kPartGhost>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsCompensated, GEOM, kPartGhost>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsDouble, GEOM, kPartReady>), reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsFloat, GEOM, kPartReady>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsCompensated, GEOM, kPartReady>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsDouble, GEOM, kPartTile>), reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsFloat, GEOM, kPartTile>),
-                          reinterpret_cast<const void*>(&lbm_multi_kernel<K, kTermsCompensated, GEOM, kPartTile>)};
-    for (const void* f : fns) {
-      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G::lds_bytes));
-      if (e != hipSuccess) return e;
-    }
-  }
-  return hipSuccess;
-}
-
-template <int K, int GEOM>
-void launch_multi_kg(int blocks, hipStream_t s, const MultiArgs& a, int terms, int part)
-{
-  if (terms == kTermsFloat) launch_multi_kgt<K, GEOM, kTermsFloat>(blocks, s, a, part);
-  else if (terms == kTermsDouble) launch_multi_kgt<K, GEOM, kTermsDouble>(blocks, s, a, part);
-  else launch_multi_kgt<K, GEOM, kTermsCompensated>(blocks, s, a, part);
-}
-
-template <int GEOM>
-hipError_t raise_multi_lds_limits()
-{
-  hipError_t e = raise_multi_lds_limit<1, GEOM>();
-  if (e == hipSuccess) e = raise_multi_lds_limit<2, GEOM>();
-  if (e == hipSuccess) e = raise_multi_lds_limit<3, GEOM>();
-  if (e == hipSuccess) e = raise_multi_lds_limit<4, GEOM>();
-  return e;
-}
 hipError_t raise_multi_lds_limits_for(int geom)          // every instantiation a context of this geometry may launch (K = 3 tails of the tall one: standard)
 {
-  if (geom == kGeomNarrow) return raise_multi_lds_limits<kGeomNarrow>();
-  hipError_t e = raise_multi_lds_limits<kGeomStd>();
-  if (e == hipSuccess && geom == kGeomTall) e = raise_multi_lds_limit<4, kGeomTall>();
-  return e;
-}
-
-template <int K>
-void launch_multi_k(int blocks, hipStream_t s, const MultiArgs& a, int terms, int geom, int part)
-{
-  if (geom == kGeomNarrow) launch_multi_kg<K, kGeomNarrow>(blocks, s, a, terms, part);
-  else if (geom_for(K, geom) == kGeomTall) launch_multi_kg<K, geom_for(K, kGeomTall)>(blocks, s, a, terms, part);
-  else launch_multi_kg<K, kGeomStd>(blocks, s, a, terms, part);
+  for (int r = geom * kMultiRowsPerGeom; r < (geom + 1) * kMultiRowsPerGeom; ++r) {
+    const MultiKernel& k = kMultiKernels[r];
+    if (k.lds_bytes <= 65536) continue;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k.lds_bytes));
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 // Tiles of a launch that makes `k` steps on the owned rows and `ext` more rows on each side (ext > 0: a launch of a partitioned
@@ -404,12 +370,8 @@ void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int 
   // the instantiation (kernels/multi.h PART): ghost rows computed too -> the counted test; ready words to say -> the fold block carries them
   // (a rank of the tile decomposition: ghost columns in every launch)
   const int part = c->ghost_x > 0 ? kPartTile : ext > 0 ? kPartGhost : a.ready_epoch != 0ull ? kPartReady : kPartPlain;
-  switch (ksteps) {                                            // <= multi_K, or 4 in the tail of a K = 3 run (lbm_run)
-    case 1: launch_multi_k<1>(blocks, s, a, c->multi_terms, c->multi_geom, part); break;
-    case 2: launch_multi_k<2>(blocks, s, a, c->multi_terms, c->multi_geom, part); break;
-    case 3: launch_multi_k<3>(blocks, s, a, c->multi_terms, c->multi_geom, part); break;
-    default: launch_multi_k<4>(blocks, s, a, c->multi_terms, c->multi_geom, part); break;
-  }
+  const MultiKernel& k = kMultiKernels[multi_row(std::min(ksteps, kMaxMultiSteps), c->multi_geom, c->multi_terms, part)];   // ksteps <= multi_K, or 4 in the tail of a K = 3 run (lbm_run)
+  k.fn<<<dim3(blocks + 1), dim3(k.lanes), k.lds_bytes, s>>>(a);
 }
 
 #if LBM_EXPERIMENTS

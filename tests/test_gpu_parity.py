@@ -630,7 +630,7 @@ def test_run_lengths_that_four_does_not_divide(lbm, oracle, digests, monkeypatch
 @pytest.mark.parametrize("geom,nx,ny,steps", [(None, 1346, 811, 11), (None, 1024, 1030, 9), ("2", 322, 140, 14), ("2", 128, 57, 10), ("0", 1154, 930, 7),
                                               ("1", 1346, 811, 6)])
 def test_multi_kernel_geometries_on_ragged_grids(lbm, oracle, monkeypatch, geom, nx, ny, steps):
-    """The three launch geometries of lbm_multi_kernel<4> (kernels/multi.h: standard 64 x 13 / 512 lanes, narrow 32 x 13, tall 64 x 23 /
+    """The three launch geometries of lbm_multi_kernel<4> (kernels/multi.h: standard 64 x 13 / 512 lanes, narrow 32 x 13, tall 64 x 24 /
     768 lanes — the library's choice from 2^20 cells up) on grids that no tile size divides: last tile column and row stick out of
     the grid, step counts that 4 does not divide mix in the K = 3 launch (64 x 16), the run is cut in two.  Against the oracle."""
     monkeypatch.setenv("LBM_TUNE_TILE_MAX", "0")
@@ -1586,7 +1586,7 @@ def test_cli_chooses_tiles_for_a_grid_much_wider_than_tall(lbm, tmp_path):
 @pytest.mark.parametrize("devices", ["0,0", "0,1"])
 def test_cli_ranks_of_one_process_on_the_tall_geometry(lbm, tmp_path, devices):
     """The single-process multi-device host (LBM_GPUS=N, one context per rank in ONE process: the reference's `mpirun -np N`,
-    mpi_submit:63) on a deck with >= 2^20 cells per rank, so that every context launches lbm_multi_kernel<4> on 64 x 23 tiles — 79 KB of
+    mpi_submit:63) on a deck with >= 2^20 cells per rank, so that every context launches lbm_multi_kernel<4> on 64 x 24 tiles — 79 KB of
     dynamic LDS, a limit that is raised per DEVICE by lbm_create (a per-process flag once left the second device of such a host at
     the default).  "0,0": both ranks on this box's GPU.  "0,1": one device per rank — switches itself on with two GPUs.  Against a
     one-rank run of the same binary: same bytes in final_state.dat and av_vels.dat within the float's own rounding."""
