@@ -65,7 +65,8 @@ def main(argv) -> int:
         return 1
     # p2p: direct peer-to-peer halo stores (default); rccl: RCCL send/recv; torch: torch.distributed P2P ops
     exchange = os.environ.get("LBM_EXCHANGE", "auto" if backend == "nccl" or world == 1 else "p2p")
-    # the contract path forms every sum|u| term as the reference does (double precision, d2q9-bgk.c:667); LBM_FLAGS=0: the library's default
+    # the contract path forms every sum|u| term as the reference does (double precision, d2q9-bgk.c:667); LBM_FLAGS=0: the library's default;
+    # LBM_FLAGS=256 (FLAG_FUSED_ARITH): the fused arithmetic of the cell update — inside check.py's 1 %, not the reference's bits
     flags = int(os.environ.get("LBM_FLAGS", lbm._capi.FLAG_EXACT_AVVELS))
     # LBM_RANK_GRID=PXxPY (PX * PY = the ranks): the tile (2-D) decomposition instead of the reference's row blocks (peer-to-peer loop)
     rank_grid = None

@@ -56,6 +56,22 @@ typedef struct lbm_ctx lbm_ctx;     /* opaque: device state of one partition */
                                        lbm_tile_kernel always do) instead of as compensated float sums of relative error ~2^-44 (its
                                        default: av_vels, a float, comes out the same; the launch runs at the socket power limit and the
                                        double-precision instructions cost 1-2.5 % of clock) */
+#define LBM_FLAG_FUSED_ARITH 256u   /* the cell update in its FUSED arithmetic: a fixed sequence of correctly rounded fused multiply-adds
+                                       (kernels/common.h relax_core_fused; 28 float operations per cell fewer), not what a compiler
+                                       contracts.  Contract: populations are no longer bit-identical to the reference's, check/check.py's
+                                       1 % rule still holds on all four shipped decks (full-length runs of bin/d2q9-bgk with LBM_FLAGS=256:
+                                       profiles/r05/check_fused_decks.txt; the suite runs the 128 x 128 deck), and the bits are the same whichever kernel family,
+                                       step split or decomposition advances the state (tests/fused_ref.c restates them on a CPU).
+                                       Measured deviation from the exact form: populations 1.95e-4, av_vels 3.6e-4 relative (largest over the full 128 x 128 deck, 40 000 steps; check.py allows 1e-2).
+                                       Measured time against the default (one MI355X, one session, the two contexts alternating run by run,
+                                       device time per step; profiles/r05/ab_fused_arith.txt): 8192 x 8192 253.3 against 266.4 us (ratio 0.951)
+                                       over 200-step runs and 248.5 against 262.4 us (0.947) sustained over 3 x 2000 steps, both forms at
+                                       1386 - 1388 W of the 1400 W socket limit and 2261 - 2271 MHz; 1024 x 1024 6.554 against 6.617 us (0.991);
+                                       128 x 128 0.965 against 1.012 us (0.953).
+                                       May be combined with LBM_FLAG_GRAPH (the captured launches are the fused ones).
+                                       Refused together with LBM_FLAG_FAST_AVVELS / LBM_FLAG_EXACT_AVVELS (each kernel family carries its
+                                       default form of the sum|u| terms only) and by a library built with -DLBM_EXPERIMENTS=1.  Every rank
+                                       of a partitioned run must pass it or none (not checked, as for every flag). */
 #define LBM_FLAG_FORCE_HALO    8u   /* treat a whole-grid partition like any other rank: edge rows read the halo
                                        buffers (a 1-rank run that exchanges with itself, d2q9-bgk.c:245-247) */
 

@@ -18,6 +18,7 @@ ABI_VERSION = 5
 NSPEEDS = 9
 
 FLAG_DEFAULT, FLAG_NT_STORES, FLAG_NO_NT_STORES, FLAG_KERNEL_LDS, FLAG_FORCE_HALO, FLAG_GRAPH, FLAG_ONE_STEP, FLAG_FAST_AVVELS, FLAG_EXACT_AVVELS = 0, 1, 2, 4, 8, 16, 32, 64, 128
+FLAG_FUSED_ARITH = 256     # the fused arithmetic of the cell update (include/lbm_d2q9.h): within check.py's 1 %, not the reference's bits
 
 
 class LbmError(RuntimeError):

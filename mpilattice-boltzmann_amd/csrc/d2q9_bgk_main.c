@@ -9,7 +9,9 @@
  * Environment (optional): LBM_DEVICE=<hip ordinal>, LBM_NO_OUTPUT=1 (like the reference's -DPROFILE build, :419-421),
  * LBM_FLAGS=<lbm_create flags> (default LBM_FLAG_EXACT_AVVELS: the contract path forms every sum|u| term as the reference does,
  * sqrt((double)u_sq) * densinv in double precision, d2q9-bgk.c:667; LBM_FLAGS=0 selects the library's default, compensated float
- * sums of relative error ~2^-44 per term, 1 - 2.5 % faster on the large decks, the same av_vels floats on every deck tested).
+ * sums of relative error ~2^-44 per term, 1 - 2.5 % faster on the large decks, the same av_vels floats on every deck tested;
+ * LBM_FLAGS=256, LBM_FLAG_FUSED_ARITH, selects the fused arithmetic of the cell update: final_state.dat and av_vels.dat then differ
+ * from the reference's in the last digits — 2e-4 / 4e-4 relative at most on the 128x128 deck — and `make check` still passes).
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
  * the reference's rule (d2q9-bgk.c:834-862), rank r lives on device LBM_DEVICES[r] (a comma list; default r), one host

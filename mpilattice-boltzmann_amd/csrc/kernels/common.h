@@ -216,9 +216,69 @@ typedef float f2u __attribute__((ext_vector_type(2), aligned(4)));
 
 __device__ __forceinline__ float splat_as(float, float v) { return v; }
 __device__ __forceinline__ f2 splat_as(f2, float v) { return f2{v, v}; }
+__device__ __forceinline__ float fused_mad(float a, float b, float c) { return __builtin_fmaf(a, b, c); }              // v_fma_f32
+__device__ __forceinline__ f2 fused_mad(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }             // v_pk_fma_f32
+
+// FUSED (LBM_FLAG_FUSED_ARITH): the second, equally fixed arithmetic of the cell update.  Not what a compiler contracts (the
+// library stays -ffp-contract=off) but this sequence, every "fma" one correctly rounded fused multiply-add, everything not
+// listed as in the exact form (rho, mx, my, e5, e8, a[i] = 3 m[i], rinv = 1 / rho correctly rounded, h = (0.5 rinv) 3):
+//   msq  = fma(my, my, mx * mx)
+//   d[i] = fma(a[i], m[i], -msq)                  m = {mx, my, e5, e8}; shared by opposite directions as in the exact form
+//   s[0] = fma(-h, msq, rho)
+//   s[k] = fma(h, d[i], rho +- a[i])              k = 1 .. 8
+//   r[k] = fma(w[k], s[k], -t[k])
+//   o[k] = fma(omega, r[k], t[k])
+// 28 float operations per cell fewer than the exact form's ~102.  The populations then differ from the reference's in the last
+// bits (what that comes to after a whole deck); tests/fused_ref.c restates the sequence on a CPU.
 template <typename T>
+__device__ __forceinline__ void relax_core_fused(const T (&t)[9], float omega, T (&o)[9], T& msq_out, T& rinv_out)
+{
+  const T csq_inv = splat_as(T{}, 3.0f);
+  const T w0 = splat_as(T{}, 4.0f / 9.0f), w1 = splat_as(T{}, 1.0f / 9.0f), w2 = splat_as(T{}, 1.0f / 36.0f);
+  const T om = splat_as(T{}, omega), half = splat_as(T{}, 0.5f);
+  T rho = t[0] + t[1];
+  T mx = t[1] + t[5];
+  T my = t[2] + t[5];
+  rho += t[2]; mx += t[8]; my += t[6];
+  rho += t[3]; mx -= t[3]; my -= t[4];
+  rho += t[4]; mx -= t[6]; my -= t[7];
+  rho += t[5]; mx -= t[7]; my -= t[8];
+  rho += t[6];
+  const T mxx = mx * mx;
+  const T e5 = mx + my, e8 = mx - my;
+  rho += t[7];
+  const T msq = fused_mad(my, my, mxx);
+  const T m[4] = {mx, my, e5, e8};
+  T a[4] = {mx * csq_inv, my * csq_inv, e5 * csq_inv, e8 * csq_inv};
+  rho += t[8];
+  const T rinv = recip_exact(rho);
+  T d[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) d[i] = fused_mad(a[i], m[i], -msq);
+  const T h = half * rinv * csq_inv;
+  T s[9];
+  s[1] = rho + a[0]; s[3] = rho - a[0];
+  s[2] = rho + a[1]; s[4] = rho - a[1];
+  s[5] = rho + a[2]; s[7] = rho - a[2];
+  s[8] = rho + a[3]; s[6] = rho - a[3];
+  s[0] = fused_mad(-h, msq, rho);
+  s[1] = fused_mad(h, d[0], s[1]); s[3] = fused_mad(h, d[0], s[3]);
+  s[2] = fused_mad(h, d[1], s[2]); s[4] = fused_mad(h, d[1], s[4]);
+  s[5] = fused_mad(h, d[2], s[5]); s[7] = fused_mad(h, d[2], s[7]);
+  s[8] = fused_mad(h, d[3], s[8]); s[6] = fused_mad(h, d[3], s[6]);
+  s[0] = fused_mad(w0, s[0], -t[0]);
+#pragma unroll
+  for (int k = 1; k < 9; ++k) s[k] = fused_mad((k < 5) ? w1 : w2, s[k], -t[k]);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) o[k] = fused_mad(om, s[k], t[k]);
+  msq_out = msq;
+  rinv_out = rinv;
+}
+
+template <typename T, bool FUSED = false>
 __device__ __forceinline__ void relax_core(const T (&t)[9], float omega, T (&o)[9], T& msq_out, T& rinv_out)
 {
+  if constexpr (FUSED) { relax_core_fused<T>(t, omega, o, msq_out, rinv_out); return; }
   const T csq_inv = splat_as(T{}, 3.0f);                                                     // :497
   const T w0 = splat_as(T{}, 4.0f / 9.0f), w1 = splat_as(T{}, 1.0f / 9.0f), w2 = splat_as(T{}, 1.0f / 36.0f);   // :499-501
   const T om = splat_as(T{}, omega), half = splat_as(T{}, 0.5f);
@@ -266,10 +326,11 @@ __device__ __forceinline__ void relax_core(const T (&t)[9], float omega, T (&o)[
 }
 
 // One cell; returns sqrt(m^2)/rho in double (:667).
+template <bool FUSED = false>
 __device__ __forceinline__ double relax_cell(const float (&t)[9], float omega, float (&o)[9])
 {
   float msq, rinv;
-  relax_core<float>(t, omega, o, msq, rinv);
+  relax_core<float, FUSED>(t, omega, o, msq, rinv);
   return sqrt_of_float(msq) * static_cast<double>(rinv);   // :667
 }
 
@@ -363,16 +424,18 @@ __device__ __forceinline__ auto& at_byte(B* base, uint32_t byte_off)
 //     the rsq argument is held at the smallest normal number.  msq = inf (a diverged run) gives NaN where the reference
 //     gives inf.
 //   kTermsFloat (LBM_FLAG_FAST_AVVELS): v_sqrt_f32 and one multiply; av_vels then agrees to ~1e-7 (an ulp of its float).
-constexpr int kTermsDouble = 0, kTermsFloat = 1, kTermsCompensated = 2;
+// kTermsFused added to one of them (LBM_FLAG_FUSED_ARITH): the same terms from the msq and rinv of the fused arithmetic (relax_core).
+constexpr int kTermsDouble = 0, kTermsFloat = 1, kTermsCompensated = 2, kTermsFused = 4;
 
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }     // v_pk_fma_f32
 
-template <int TERMS>
+template <int TERMS_ARITH>
 __device__ __forceinline__ double finish_pair_lo(const f2 (&t)[9], uint32_t mbits, float omega, bool tile_accel, bool accel, float w1, float w2,
                                                  uint32_t skip, f2 (&out)[9], float& lo_sum)
 {
+  constexpr int TERMS = TERMS_ARITH & ~kTermsFused;
   f2 o[9], msq, rinv;
-  relax_core<f2>(t, omega, o, msq, rinv);                               // :546-666 on both cells at once (v_pk_*_f32)
+  relax_core<f2, (TERMS_ARITH & kTermsFused) != 0>(t, omega, o, msq, rinv);   // :546-666 on both cells at once (v_pk_*_f32)
   // bounce-back select (d2q9-bgk.c:687-695) and the next step's accelerate_flow (:457-469), per cell
   static constexpr int opp[9] = {0, 3, 4, 1, 2, 7, 8, 5, 6};
 #pragma unroll
@@ -428,7 +491,7 @@ __device__ __forceinline__ double finish_pair(const f2 (&t)[9], uint32_t mbits, 
 {
   float lo = 0.0f;
   const double hi = finish_pair_lo<TERMS>(t, mbits, omega, tile_accel, accel, w1, w2, skip, out, lo);
-  return TERMS == kTermsCompensated ? hi + static_cast<double>(lo) : hi;
+  return (TERMS & ~kTermsFused) == kTermsCompensated ? hi + static_cast<double>(lo) : hi;
 }
 
 

@@ -209,7 +209,7 @@ __device__ __forceinline__ uint32_t pair_flag_bits(uint32_t mbits, bool kept, bo
   return mbits | (kept ? kPairKept : 0u) | (accel_row ? kPairAccelRow : 0u) | kPairComputed | (counted ? kPairCounted : 0u);
 }
 
-template <int K, int TERMS, int GEOM, int PART>   // TERMS: form of the sum|u| terms (kTermsCompensated by default), see finish_pair_lo; GEOM: kGeomStd / Narrow / Tall
+template <int K, int TERMS, int GEOM, int PART>   // TERMS: form of the sum|u| terms (kTermsCompensated by default; + kTermsFused: the fused arithmetic), see finish_pair_lo; GEOM: kGeomStd / Narrow / Tall
 __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEOM>::waves_per_simd)) lbm_multi_kernel(const MultiArgs a)
 {
   using G = MultiGeom<K, GEOM>;
@@ -633,7 +633,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   }
 
   // per-step sums over the owned cells of this tile
-  if constexpr (TERMS == kTermsCompensated && !G::owned_lanes) {
+  if constexpr ((TERMS & ~kTermsFused) == kTermsCompensated && !G::owned_lanes) {
 #pragma unroll
     for (int i = 0; i < K; ++i) acc[i] += static_cast<double>(acc_lo[i]);
   }

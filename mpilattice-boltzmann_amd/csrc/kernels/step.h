@@ -8,7 +8,7 @@ namespace {
 // Everything after the pull for the 4 cells at (y, x0..x0+3), partition-local cell index c:
 // relaxation / bounce-back select, next step's accelerate_flow on row ny-2, stores, outgoing halo
 // rows.  p[k] = streamed-in population k of the four cells.  Returns their sum|u| contribution.
-template <bool NT>
+template <bool NT, bool FUSED = false>
 __device__ __forceinline__ double finish_quad(const StepArgs& a, int c, int y, int x0, const f4 (&p)[9], uint32_t mbits)
 {
   const size_t ps = a.ps;
@@ -19,7 +19,7 @@ __device__ __forceinline__ double finish_quad(const StepArgs& a, int c, int y, i
     float t[9], o[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) t[k] = p[k][j];
-    const double term = relax_cell(t, a.omega, o);
+    const double term = relax_cell<FUSED>(t, a.omega, o);
     const bool blocked = (mbits >> j) & 1u;
     // bounce-back (d2q9-bgk.c:687-695): out[opposite(k)] = t[k]
     out[0][j] = blocked ? t[0] : o[0];
@@ -65,7 +65,7 @@ __device__ __forceinline__ double finish_quad(const StepArgs& a, int c, int y, i
 
 // Direct-load form: processes the 4 cells starting at partition-local cell index 4*quad
 // (nx % 4 == 0, so the four share a row).
-template <bool NT>
+template <bool NT, bool FUSED = false>
 __device__ __forceinline__ double step_quad(const StepArgs& a, int quad)
 {
   const int c = quad * kCellsPerLane;
@@ -98,13 +98,13 @@ __device__ __forceinline__ double step_quad(const StepArgs& a, int quad)
     p[7].w = r.n7[0];
   }
   const uint32_t mbits = (mword >> (c & 31)) & 0xFu;
-  return finish_quad<NT>(a, c, y, x0, p, mbits);
+  return finish_quad<NT, FUSED>(a, c, y, x0, p, mbits);
 }
 
 // One-cell-per-lane form: used for grids so small that a step is bound by the latency of one lane's
 // dependent instruction chain rather than by bandwidth (4x more lanes, each with a quarter of the
 // chain), and for row lengths that are not a multiple of 4.  `cell` = partition-local cell index.
-template <bool NT>
+template <bool NT, bool FUSED = false>
 __device__ __forceinline__ double step_cell(const StepArgs& a, int cell)
 {
   const int y = cell / a.nx;
@@ -119,7 +119,7 @@ __device__ __forceinline__ double step_cell(const StepArgs& a, int cell)
   t[3] = r.here[3 * ps + xe];  t[4] = r.n4[x];              t[5] = r.s5[xw];     // :533-535
   t[6] = r.s6[xe];             t[7] = r.n7[xe];             t[8] = r.n8[xw];     // :536-538
   const bool blocked = (a.mask[cell >> 5] >> (cell & 31)) & 1u;
-  const double term = relax_cell(t, a.omega, o);
+  const double term = relax_cell<FUSED>(t, a.omega, o);
   float out[9];
   out[0] = blocked ? t[0] : o[0];                                       // bounce-back :687-695
   out[1] = blocked ? t[3] : o[1];
@@ -248,55 +248,18 @@ __global__ void __launch_bounds__(kBlock) lbm_step_kernel_lds(const StepArgs a)
 }
 #endif   // LBM_EXPERIMENTS
 
-// The fused streaming-pull step.  Grid: ceil(#quads / (256*iters)) work blocks of 256 lanes (block b
-// owns `iters` consecutive 1024-cell chunks) after one fold block (block 0, dispatched first).
-template <bool NT>
-__global__ void __launch_bounds__(kBlock) lbm_step_kernel(const StepArgs a)
-{
-  __shared__ double red[kBlock / 64];
-  if (blockIdx.x == 0) { fold_previous(a, red); return; }
-  const int wblock = blockIdx.x - 1;   // work block index
-  double acc = 0.0;
-  const int n1 = a.quad_end - a.quad_begin;
-  const int n2 = a.quad_end2 > a.quad_begin2 ? a.quad_end2 - a.quad_begin2 : 0;
-  const int base = wblock * a.iters * kBlock + threadIdx.x;
-  for (int i = 0; i < a.iters; ++i) {
-    const int r = base + i * kBlock;
-    if (r < n1 + n2) acc += step_quad<NT>(a, r < n1 ? a.quad_begin + r : a.quad_begin2 + (r - n1));
-  }
-  acc = block_sum(acc, red);
-  // boundary launch of a peer-to-peer run: the outgoing halo rows were stored straight into the neighbours' windows;
-  // a full barrier drains every wave's stores (block_sum's barriers order LDS only), then one lane writes the XCD's L2
-  // back towards the peers
-  if (a.release_sends) __syncthreads();
-  if (threadIdx.x == 0) {
-    a.partials_out[wblock] = acc;
-    if (a.release_sends) __atomic_thread_fence(__ATOMIC_RELEASE);
-  }
-}
-
-// One cell per lane; the unit ranges of StepArgs are cell ranges here.
-template <bool NT>
-__global__ void __launch_bounds__(kBlock) lbm_step_kernel_narrow(const StepArgs a)
-{
-  __shared__ double red[kBlock / 64];
-  if (blockIdx.x == 0) { fold_previous(a, red); return; }
-  const int wblock = blockIdx.x - 1;   // work block index
-  double acc = 0.0;
-  const int n1 = a.quad_end - a.quad_begin;
-  const int n2 = a.quad_end2 > a.quad_begin2 ? a.quad_end2 - a.quad_begin2 : 0;
-  const int base = wblock * a.iters * kBlock + threadIdx.x;
-  for (int i = 0; i < a.iters; ++i) {
-    const int r = base + i * kBlock;
-    if (r < n1 + n2) acc += step_cell<NT>(a, r < n1 ? a.quad_begin + r : a.quad_begin2 + (r - n1));
-  }
-  acc = block_sum(acc, red);
-  if (a.release_sends) __syncthreads();                                  // see lbm_step_kernel
-  if (threadIdx.x == 0) {
-    a.partials_out[wblock] = acc;
-    if (a.release_sends) __atomic_thread_fence(__ATOMIC_RELEASE);
-  }
-}
+// The two one-step kernels are defined from ONE text, kernels/step_kernel_def.h, included once per arithmetic (as kernels/tile.h does for
+// lbm_tile_kernel): lbm_step_kernel<NT> / lbm_step_kernel_narrow<NT> (the exact arithmetic: the tokens, and with them the code, they had
+// before the fused form existed) and lbm_step_kernel_fused<NT> / lbm_step_kernel_narrow_fused<NT> (LBM_FLAG_FUSED_ARITH; not in the
+// experiment build).
+#define LBM_STEP_FUSED 0
+#include "step_kernel_def.h"
+#undef LBM_STEP_FUSED
+#if !LBM_EXPERIMENTS
+#define LBM_STEP_FUSED 1
+#include "step_kernel_def.h"
+#undef LBM_STEP_FUSED
+#endif
 
 __device__ __forceinline__ void fold_previous(const StepArgs& a, double* red)
 {

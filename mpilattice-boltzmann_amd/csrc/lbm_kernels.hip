@@ -126,6 +126,7 @@ struct lbm_ctx {
   int* ready_err = nullptr;
   bool nt_stores = false;
   bool fast_avvels = false;  // LBM_FLAG_FAST_AVVELS: float sum|u| terms in lbm_multi_kernel / lbm_tile_kernel
+  bool fused = false;        // LBM_FLAG_FUSED_ARITH: every launch takes the fused instantiation of its kernel (relax_core, kernels/common.h)
   int multi_terms = kTermsCompensated;   // lbm_multi_kernel's form of the terms (kernels/common.h): LBM_FLAG_FAST_AVVELS / LBM_FLAG_EXACT_AVVELS
   size_t ncells = 0, ncells_storage = 0, ps = 0, grid_floats = 0;   // owned cells; cells incl. ghost rows; plane stride
   float* grid_alloc[2] = {nullptr, nullptr};
@@ -272,6 +273,18 @@ StepArgs base_args(lbm_ctx* c, bool accel_next)
 void launch_step(lbm_ctx* c, const StepArgs& a, int blocks, hipStream_t s)
 {
   const dim3 grid(blocks + 1), block(kBlock);   // + the fold block
+#if !LBM_EXPERIMENTS
+  if (c->fused) {                   // LBM_FLAG_FUSED_ARITH
+    if (c->lane_cells == 1) {
+      if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_narrow_fused<true>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(lbm_step_kernel_narrow_fused<false>, grid, block, 0, s, a);
+    } else {
+      if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_fused<true>, grid, block, 0, s, a);
+      else hipLaunchKernelGGL(lbm_step_kernel_fused<false>, grid, block, 0, s, a);
+    }
+    return;
+  }
+#endif
   if (c->lane_cells == 1) {
     if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_narrow<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(lbm_step_kernel_narrow<false>, grid, block, 0, s, a);
@@ -288,8 +301,11 @@ void launch_step(lbm_ctx* c, const StepArgs& a, int blocks, hipStream_t s)
 
 // Every instantiation of lbm_multi_kernel a context may launch, one row per (geometry, steps, terms, launch form) with what a launch
 // of it needs.  Rows of the tall geometry with K < 4 name the standard kernels (geom_for): no instantiation of their own.
+// The terms index of a row: the three forms of the sum|u| terms, then (index kMultiTermsFused, not in the experiment build) the fused arithmetic
+// with lbm_multi_kernel's default form of them: the instantiation <K, kTermsCompensated + kTermsFused, GEOM, PART>.
 struct MultiKernel { void (*fn)(MultiArgs); int lanes; size_t lds_bytes; };
-constexpr int kMultiTerms = 3, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
+constexpr int kMultiTermsFused = 3;
+constexpr int kMultiTerms = LBM_EXPERIMENTS ? 3 : 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
 static_assert(kTermsDouble == 0 && kTermsFloat == 1 && kTermsCompensated == 2 && kPartPlain == 0 && kPartTile == 3 && kGeomTall == 2, "the values index the table");
 constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
 template <int ROW>
@@ -298,7 +314,7 @@ constexpr MultiKernel multi_kernel_row()
   constexpr int PART = ROW % kMultiParts, TERMS = ROW / kMultiParts % kMultiTerms, K = ROW / (kMultiParts * kMultiTerms) % kMaxMultiSteps + 1,
                 GEOM = geom_for(K, ROW / kMultiRowsPerGeom);
   static_assert(multi_row(K, ROW / kMultiRowsPerGeom, TERMS, PART) == ROW, "multi_row and its inverse");
-  return {&lbm_multi_kernel<K, TERMS, GEOM, PART>, MultiGeom<K, GEOM>::LANES, MultiGeom<K, GEOM>::lds_bytes};
+  return {&lbm_multi_kernel<K, TERMS == kMultiTermsFused ? (kTermsCompensated | kTermsFused) : TERMS, GEOM, PART>, MultiGeom<K, GEOM>::LANES, MultiGeom<K, GEOM>::lds_bytes};
 }
 template <size_t... ROW>
 constexpr std::array<MultiKernel, sizeof...(ROW)> multi_kernel_rows(std::index_sequence<ROW...>) { return {{multi_kernel_row<static_cast<int>(ROW)>()...}}; }
@@ -370,7 +386,7 @@ void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int 
   // the instantiation (kernels/multi.h PART): ghost rows computed too -> the counted test; ready words to say -> the fold block carries them
   // (a rank of the tile decomposition: ghost columns in every launch)
   const int part = c->ghost_x > 0 ? kPartTile : ext > 0 ? kPartGhost : a.ready_epoch != 0ull ? kPartReady : kPartPlain;
-  const MultiKernel& k = kMultiKernels[multi_row(std::min(ksteps, kMaxMultiSteps), c->multi_geom, c->multi_terms, part)];   // ksteps <= multi_K, or 4 in the tail of a K = 3 run (lbm_run)
+  const MultiKernel& k = kMultiKernels[multi_row(std::min(ksteps, kMaxMultiSteps), c->multi_geom, c->fused ? kMultiTermsFused : c->multi_terms, part)];   // ksteps <= multi_K, or 4 in the tail of a K = 3 run (lbm_run)
   k.fn<<<dim3(blocks + 1), dim3(k.lanes), k.lds_bytes, s>>>(a);
 }
 
@@ -415,9 +431,17 @@ void launch_sweep(lbm_ctx* c, bool accel_last, hipStream_t s)
 #endif   // LBM_EXPERIMENTS
 
 template <int T, int H>
-void launch_tile(dim3 grid, hipStream_t s, const TileArgs& a, bool fast)
+void launch_tile(dim3 grid, hipStream_t s, const TileArgs& a, bool fast, bool fused)
 {
   using G = TileGeom<T, H>;
+#if !LBM_EXPERIMENTS
+  if (fused) {                      // LBM_FLAG_FUSED_ARITH (never with `fast`: create_impl)
+    if (a.ksteps == H) lbm_tile_kernel_fused<T, H, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
+    else lbm_tile_kernel_fused<T, H, false><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
+    return;
+  }
+#endif
+  (void)fused;
   if (fast) {
     if (a.ksteps == H) lbm_tile_kernel<T, H, true, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
     else lbm_tile_kernel<T, H, false, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
@@ -665,6 +689,17 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
   if (p->ny < 3) { lbm_internal::set_error("lbm_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
   if (ny_local < 1 || y0 < 0 || y0 + ny_local > p->ny) { lbm_internal::set_error("lbm_create: partition rows out of range"); return 1; }
   if (free_cells <= 0) { lbm_internal::set_error("lbm_create: free_cells must be positive"); return 1; }
+  if (flags & LBM_FLAG_FUSED_ARITH) {
+    // one form of the sum|u| terms per kernel family for the fused arithmetic (that family's default): the flags that ask for another are refused
+    if (flags & (LBM_FLAG_FAST_AVVELS | LBM_FLAG_EXACT_AVVELS)) {
+      lbm_internal::set_error("lbm_create: LBM_FLAG_FUSED_ARITH cannot be combined with LBM_FLAG_FAST_AVVELS or LBM_FLAG_EXACT_AVVELS (the fused kernels carry each family's default sum|u| terms only)");
+      return 1;
+    }
+#if LBM_EXPERIMENTS
+    lbm_internal::set_error("lbm_create: LBM_FLAG_FUSED_ARITH is not built into the experiment library (-DLBM_EXPERIMENTS=1)");
+    return 1;
+#endif
+  }
   const bool self_periodic = (ny_local == p->ny) && !(flags & LBM_FLAG_FORCE_HALO);
   const int accel_global = p->ny - 2;
   int accel_row = -1;
@@ -689,6 +724,7 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
   }
   c->self_periodic = self_periodic;
   c->fast_avvels = (flags & LBM_FLAG_FAST_AVVELS) != 0;
+  c->fused = (flags & LBM_FLAG_FUSED_ARITH) != 0;
   c->multi_terms = c->fast_avvels ? kTermsFloat : (flags & LBM_FLAG_EXACT_AVVELS) ? kTermsDouble : kTermsCompensated;
   {
     const int t = knobs.terms;                                // 0 double, 1 float, 2 compensated (A/B runs of the DEFAULT form:
@@ -874,6 +910,10 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
       const void* big[4] = {reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, true, false>), reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, false, false>),
                             reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, true, true>), reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, false, true>)};
       for (const void* k : big) HIP_TRY_C(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G168::lds_bytes)));
+#if !LBM_EXPERIMENTS
+      const void* big_fused[2] = {reinterpret_cast<const void*>(&lbm_tile_kernel_fused<16, 8, true>), reinterpret_cast<const void*>(&lbm_tile_kernel_fused<16, 8, false>)};
+      for (const void* k : big_fused) HIP_TRY_C(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G168::lds_bytes)));
+#endif
     }
   }
   for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * c->partials_cap));
@@ -1149,10 +1189,10 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
     a.sums = c->sums; a.counter = c->counter;
     const dim3 grid(c->n_tiles + 1);
     hipEvent_t pb = prof_stamp(c, s);
-    if (c->tile_T == 16 && c->tile_H == 8) launch_tile<16, 8>(grid, s, a, c->fast_avvels);
-    else if (c->tile_T == 16) launch_tile<16, 4>(grid, s, a, c->fast_avvels);
-    else if (c->tile_H == 8) launch_tile<8, 8>(grid, s, a, c->fast_avvels);
-    else launch_tile<8, 4>(grid, s, a, c->fast_avvels);
+    if (c->tile_T == 16 && c->tile_H == 8) launch_tile<16, 8>(grid, s, a, c->fast_avvels, c->fused);
+    else if (c->tile_T == 16) launch_tile<16, 4>(grid, s, a, c->fast_avvels, c->fused);
+    else if (c->tile_H == 8) launch_tile<8, 8>(grid, s, a, c->fast_avvels, c->fused);
+    else launch_tile<8, 4>(grid, s, a, c->fast_avvels, c->fused);
     if (c->profile) c->prof_launches.push_back({k, pb, prof_stamp(c, s)});
     ++tile_launches;
     c->n_prev = c->n_tiles; c->n_prev_vecs = k;
@@ -1714,6 +1754,11 @@ int lbm_describe(const lbm_ctx* c, char* kernel_name, size_t len, long long* cel
       std::snprintf(kernel_name, len, "lbm_step_kernel_lds<%s>", c->nt_stores ? "true" : "false");
     else
 #endif
+    if (c->fused) {                 // LBM_FLAG_FUSED_ARITH, named as a profiler prints them: lbm_multi_kernel<K, 6, GEOM, PART> (6 = kTermsCompensated + kTermsFused), lbm_tile_kernel_fused, lbm_step_kernel*_fused
+      if (c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) std::snprintf(kernel_name, len, "lbm_multi_kernel<%d, 6> (fused arithmetic)", c->multi_K);
+      else if (c->tile_kernel && c->self_periodic) std::snprintf(kernel_name, len, "lbm_tile_kernel_fused<%d, %d>", c->tile_T, c->tile_H);
+      else std::snprintf(kernel_name, len, c->lane_cells == 1 ? "lbm_step_kernel_narrow_fused<%s>" : "lbm_step_kernel_fused<%s>", c->nt_stores ? "true" : "false");
+    } else
     if (c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) std::snprintf(kernel_name, len, c->multi_terms == kTermsFloat ? "lbm_multi_kernel<%d, fast av_vels>" : c->multi_terms == kTermsDouble ? "lbm_multi_kernel<%d, double-precision av_vels terms>" : "lbm_multi_kernel<%d>", c->multi_K);
     else if (c->tile_kernel && c->self_periodic) std::snprintf(kernel_name, len, c->fast_avvels ? "lbm_tile_kernel<%d, %d, fast av_vels>" : "lbm_tile_kernel<%d, %d>", c->tile_T, c->tile_H);
     else if (c->lane_cells == 1) std::snprintf(kernel_name, len, "lbm_step_kernel_narrow<%s>", c->nt_stores ? "true" : "false");

@@ -212,6 +212,7 @@ class Partition:
         self._lib = _capi.load_library()
         obst = np.ascontiguousarray(obstacles_rows, dtype=np.int32)
         self.x0, self.nx_local = 0, params.nx
+        self.flags = int(flags)
         if tile_of is not None:
             rank, px, py = tile_of
             lay = tile_layout(params, px, py, rank, flags)
@@ -367,7 +368,8 @@ class Partition:
         name = C.create_string_buffer(256)
         cells, nbytes = C.c_longlong(0), C.c_longlong(0)
         check(self._lib.lbm_describe(self._ctx, name, 256, C.byref(cells), C.byref(nbytes)))
-        return {"kernel": name.value.decode(), "cells_per_launch": cells.value, "state_bytes": nbytes.value}
+        return {"kernel": name.value.decode(), "cells_per_launch": cells.value, "state_bytes": nbytes.value,
+                "fused_arith": bool(self.flags & _capi.FLAG_FUSED_ARITH)}
 
     # -- split-phase stepping (row-partitioned runs) --
     @property
@@ -895,7 +897,8 @@ class Simulation:
     def describe(self) -> dict:
         """What actually runs: loop, K, ranks as the transport itself reports them."""
         d = {"loop": self.loop, "macro_k": self.partition.macro_steps, "ranks": self.size, "rccl_nranks": None, "p2p": None,
-             "step_allreduce": bool(self._ring is not None and self._ring.step_allreduce)}
+             "step_allreduce": bool(self._ring is not None and self._ring.step_allreduce),
+             "fused_arith": bool(self._flags & _capi.FLAG_FUSED_ARITH)}
         if self._ring is not None:
             d["rccl_nranks"] = self._ring.nranks
         if self._p2p is not None:
