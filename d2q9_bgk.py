@@ -68,19 +68,21 @@ def main(argv) -> int:
     # the contract path forms every sum|u| term as the reference does (double precision, d2q9-bgk.c:667); LBM_FLAGS=0: the library's default;
     # LBM_FLAGS=256 (FLAG_FUSED_ARITH): the fused arithmetic of the cell update — inside check.py's 1 %, not the reference's bits
     flags = int(os.environ.get("LBM_FLAGS", lbm._capi.FLAG_EXACT_AVVELS))
-    # LBM_RANK_GRID=PXxPY (PX * PY = the ranks): the tile (2-D) decomposition instead of the reference's row blocks (peer-to-peer loop)
+    # LBM_RANK_GRID=PXxPY (PX * PY = the ranks): the tile (2-D) decomposition instead of the reference's row blocks — the peer-to-peer loop, or the
+    # RCCL loop where LBM_EXCHANGE=rccl asks for it or the peer-to-peer transport cannot be set up
     rank_grid = None
     if os.environ.get("LBM_RANK_GRID") == "auto":             # lbm_choose_rank_grid: row blocks unless the grid is much wider than tall
         rank_grid = lbm.choose_rank_grid(params, world, flags)
-        if rank_grid is not None:
-            exchange = "p2p"
+        if rank_grid is not None and exchange != "rccl":
+            exchange = "auto"                                 # p2p, then rccl
     elif os.environ.get("LBM_RANK_GRID"):
         try:
             rank_grid = tuple(int(v) for v in os.environ["LBM_RANK_GRID"].lower().split("x"))
             assert len(rank_grid) == 2 and rank_grid[0] * rank_grid[1] == world
         except (ValueError, AssertionError):
             die("LBM_RANK_GRID: expected PXxPY with PX * PY = the number of ranks")
-        exchange = "p2p"
+        if exchange != "rccl":
+            exchange = "auto"                                 # p2p, then rccl
     try:
         sim = lbm.Simulation(params, obstacles, device=local_rank, distributed=world > 1, exchange=exchange, flags=flags, rank_grid=rank_grid)
     except lbm.LbmError as e:

@@ -161,10 +161,11 @@ int lbm_create_rank(lbm_ctx** ctx, const lbm_params* p, int free_cells, const in
  * The reference splits rows only (d2q9-bgk.c:834-862); its report discusses a 2-D split for grids wider than tall and never
  * built it (report.odt, "MPI Design").  Here: rows by the reference's rule over py, columns in whole x-pairs over px
  * (lbm_decompose_columns), every rank in K-step mode with `ghost` ghost rows AND `ghost_x` ghost columns around its block, refreshed
- * once per group of launches (lbm_plan_group) by the peer-to-peer loop (lbm_d2q9_p2p.h): columns from the west / east neighbours
+ * once per group of launches (lbm_plan_group): columns from the west / east neighbours
  * first, then whole storage rows — ghost columns included, which carries the corners — from south / north.  px = 1 is allowed
  * (the rank is its own west and east neighbour); the layout fails where a rank would not be eligible for K-step mode (use the row
- * decomposition there).  The RCCL loop and the split-phase calls take row partitions only. */
+ * decomposition there).  Three ways to step such ranks: the peer-to-peer loop (lbm_d2q9_p2p.h), the RCCL loop (lbm_d2q9_rccl.h), and the
+ * split-phase calls for a caller with its own communicator (lbm_tile_prepare, lbm_macro_pack_x ... below). */
 typedef struct lbm_tile_layout {
   int px, py, rx, ry;               /* the rank grid and this rank's place in it */
   int x0, nx_local, y0, ny_local;   /* columns [x0, x0+nx_local) of rows [y0, y0+ny_local) belong to the rank */
@@ -188,6 +189,9 @@ int lbm_create_tile(lbm_ctx** ctx, const lbm_params* p, int free_cells, const in
                     int px, int py, int rank, int device, unsigned flags);
 /* The block a context owns, whichever call created it (px = py = 1, ghost_x = 0 for everything but lbm_create_tile). */
 int lbm_tile_info(const lbm_ctx* ctx, lbm_tile_layout* out);
+/* The neighbours of rank = ry * px + rx of a px x py rank grid, periodic in both directions: out = {south, north, west, east} (south =
+ * towards row y-1, the reference's `top`, d2q9-bgk.c:245-247; west = towards column x-1).  Host only; the one rule of every loop here. */
+int lbm_tile_neighbours(int px, int py, int rank, int out[4]);
 
 /* Replaces the whole timestep loop d2q9-bgk.c:315-394 for a self-contained domain
  * (ny_local == ny): n_steps x { accelerate_flow (:442-478); timestep (:493-704); av_vels[tt]
@@ -285,6 +289,43 @@ int    lbm_macro_edge(lbm_ctx* ctx, void* stream);
 int    lbm_macro_all(lbm_ctx* ctx, void* stream);
 int    lbm_macro_finish(lbm_ctx* ctx, void* stream);
 int    lbm_macro_exchange_local(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream);
+/* ---- split-phase stepping of a rank of the TILE decomposition (contexts from lbm_create_tile) ----
+ *
+ * The macro-step of a tile rank is the one above with a two-phase packed exchange in front of it, columns first, then rows:
+ *     lbm_macro_pack_x(ctx, stream)     gathers the first / last ghost_x owned columns of the owned rows into lbm_macro_pack_ptr_x(dir, 0)
+ *     [caller: moves lbm_macro_pack_ptr_x(dir, 0) into the neighbour's lbm_macro_pack_ptr_x(dir ^ 1, 1); dir 0 = west, 1 = east]
+ *     lbm_macro_unpack_x(ctx, stream)   scatters the incoming messages into the west / east ghost columns
+ *   then, unless the rank is a column block (lbm_tile_layout.ghost_y == 0: lbm_macro_pack_floats() == 0, its rows wrap inside the launch
+ *   and lbm_macro_pack / lbm_macro_unpack refuse):
+ *     lbm_macro_pack(ctx, stream)       first / last `ghost` owned STORAGE rows — the ghost columns that have just arrived included, which
+ *     [caller: moves 2 + 2 messages]    carries the corners from the diagonal neighbours in two hops
+ *     lbm_macro_unpack(ctx, stream)
+ *   then lbm_macro_interior + lbm_macro_edge (or lbm_macro_all) and lbm_macro_finish as above.  lbm_macro_interior may overlap BOTH phases:
+ *   its tiles read neither an exchanged row nor an exchanged column.  Neighbours: lbm_tile_neighbours.
+ * One column message holds lbm_macro_pack_floats_x() = 9 * ny_local * ghost_x floats, laid out [plane][owned row][ghost_x columns]:
+ *     outgoing west (dir 0)   the first ghost_x owned columns (storage columns [ghost_x, 2 ghost_x)) of the owned rows
+ *     outgoing east (dir 1)   the last ghost_x owned columns (storage columns [nx_local, nx_local + ghost_x))
+ *     incoming from the west  (dir 0) lands in the west ghost columns, storage columns [0, ghost_x)
+ *     incoming from the east  (dir 1) lands in the east ghost columns, storage columns [ghost_x + nx_local, 2 ghost_x + nx_local)
+ * owned rows only; west and east neighbours own the same rows, so both ends of a message agree on its size (south and north neighbours
+ * own the same columns: the row messages of lbm_macro_pack_floats() = 9 * ghost * (nx_local + 2 ghost_x) floats, [plane][row][storage column]).
+ * All ghost_x columns and `ghost` rows travel every time, whatever the next group's step count.  The buffers are the library's, allocated by
+ * lbm_create_tile and freed by lbm_destroy.  On other contexts the _x calls return 0 / NULL or refuse.
+ * lbm_tile_prepare is lbm_macro_prepare for these contexts — a call of its own, and lbm_macro_prepare keeps refusing them: a caller
+ * that knows the row protocol only would exchange rows, never columns, and step the tile wrongly.
+ * lbm_macro_exchange_local_x / _y: the caller's part between two tile contexts of one process, one device copy: src's packed message of
+ * direction dir (0 = west / south, 1 = east / north) into dst's incoming buffer of the opposite side; after pack on src, before unpack on
+ * dst; dst == src for a rank that is its own neighbour.
+ * Cost, measured: 2048 x 512 as a 1 x 1 rank grid that exchanges with itself, one MI355X, one session, the rings alternated run by run, medians
+ * of 2000-step runs, RCCL loop against peer-to-peer loop: 7.69 against 7.30 us/step as a column block (ratio 1.053), 9.76 against 8.43 with ghost
+ * rows (LBM_TUNE_TILE_GHOST_ROWS=1; 1.158) — the order of the row blocks' gap (3.53 against 3.12 on 1024 x 128 rows, 1.131); profiles/r05/tile_rccl_ring.txt. */
+int    lbm_tile_prepare(lbm_ctx* ctx, int n_steps, void* stream);
+size_t lbm_macro_pack_floats_x(const lbm_ctx* ctx);
+void*  lbm_macro_pack_ptr_x(lbm_ctx* ctx, int dir, int incoming);
+int    lbm_macro_pack_x(lbm_ctx* ctx, void* stream);
+int    lbm_macro_unpack_x(lbm_ctx* ctx, void* stream);
+int    lbm_macro_exchange_local_x(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream);
+int    lbm_macro_exchange_local_y(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream);
 
 /* Fold the per-block sums of the (macro-)step just finished into the per-step totals NOW, on `stream`,
  * instead of leaving them to block 0 of the next launch: for callers that need this step's total before the

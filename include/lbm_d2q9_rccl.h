@@ -29,7 +29,12 @@ int lbm_comm_unique_id(char id[LBM_COMM_ID_BYTES]);
 /* Collective over the nranks processes (ncclCommInitRank) on ctx's device.  Ring neighbours follow
  * d2q9-bgk.c:245-247: south = `top` = rank-1 (wrapping), north = `bottom` = (rank+1) % nranks.
  * With nranks == 1 the rank exchanges with itself (the reference's 1-rank behaviour); the context
- * must then have been created with LBM_FLAG_FORCE_HALO. */
+ * must then have been created with LBM_FLAG_FORCE_HALO.
+ * A context from lbm_create_tile (recognised by lbm_tile_info) makes the rank one of the px x py tile decomposition: nranks must be
+ * px * py and rank ry * px + rx, the four neighbours are lbm_tile_neighbours', and every exchange of lbm_comm_run is two RCCL groups on
+ * the exchange stream — columns (sends [west, east], receives [east, west]), then, unless the rank is a column block, storage rows
+ * (sends [south, north], receives [north, south]) — around the pack / unpack kernels of lbm_macro_pack_x and lbm_macro_pack; schedules,
+ * events and reductions are the row partitions'.  The ranks must agree on (K, ghost, ghost_x, ghost_y, px, py); message sizes may differ. */
 int lbm_comm_create(lbm_comm** comm, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTES], int nranks, int rank);
 int lbm_comm_destroy(lbm_comm* comm);
 

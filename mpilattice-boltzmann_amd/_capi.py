@@ -63,6 +63,7 @@ _SIGNATURES = {
     "lbm_choose_rank_grid": (C.c_int, [_P(CParams), C.c_int, C.c_uint, _P(C.c_int), _P(C.c_int)]),
     "lbm_create_tile": (C.c_int, [_P(_ctx), _P(CParams), C.c_int, _P(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint]),
     "lbm_tile_info": (C.c_int, [_ctx, _P(CTileLayout)]),
+    "lbm_tile_neighbours": (C.c_int, [C.c_int, C.c_int, C.c_int, _P(C.c_int)]),
     "lbm_destroy": (C.c_int, [_ctx]),
     "lbm_run": (C.c_int, [_ctx, C.c_int, _P(C.c_float)]),
     "lbm_get_cells": (C.c_int, [_ctx, _P(C.c_float)]),
@@ -94,6 +95,13 @@ _SIGNATURES = {
     "lbm_macro_edge": (C.c_int, [_ctx, C.c_void_p]),
     "lbm_macro_finish": (C.c_int, [_ctx, C.c_void_p]),
     "lbm_macro_exchange_local": (C.c_int, [_ctx, _ctx, C.c_int, C.c_void_p]),
+    "lbm_tile_prepare": (C.c_int, [_ctx, C.c_int, C.c_void_p]),
+    "lbm_macro_pack_floats_x": (C.c_size_t, [_ctx]),
+    "lbm_macro_pack_ptr_x": (C.c_void_p, [_ctx, C.c_int, C.c_int]),
+    "lbm_macro_pack_x": (C.c_int, [_ctx, C.c_void_p]),
+    "lbm_macro_unpack_x": (C.c_int, [_ctx, C.c_void_p]),
+    "lbm_macro_exchange_local_x": (C.c_int, [_ctx, _ctx, C.c_int, C.c_void_p]),
+    "lbm_macro_exchange_local_y": (C.c_int, [_ctx, _ctx, C.c_int, C.c_void_p]),
     "lbm_step_fold": (C.c_int, [_ctx, C.c_void_p]),
     "lbm_step_collect": (C.c_int, [_ctx, C.c_void_p, _P(C.c_double), C.c_int]),
     "lbm_step_sums_device_ptr": (C.c_void_p, [_ctx]),

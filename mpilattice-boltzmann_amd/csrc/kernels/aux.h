@@ -133,6 +133,55 @@ __global__ void lbm_macro_pack_kernel(const float* grid, float* buf, size_t ps, 
   else *reinterpret_cast<f2*>(buf + boff) = *reinterpret_cast<const f2*>(grid + goff);
 }
 
+// Tile ranks, the column half of a packed exchange: gather the first / last ghost_x owned COLUMNS of the owned rows of all 9 planes into
+// one contiguous message per direction (pack: dir 0 = towards the west neighbour, 1 = east), or scatter the two received messages into the
+// west / east ghost columns (unpack: dir = the side the message came from).  buf layout: [dir][plane][owned row][ghost_x], so vector w of the
+// launch IS vector w of buf: lanes run along the messages (whole cache lines), and the grid side is a chain of ghost_x-float row segments
+// at the storage-row stride — consecutive lanes fill one segment, then the next row's.  One launch, both directions, no LDS.
+struct MacroPackColsArgs {
+  float* grid;                           // plane 0, storage row 0 of the current grid
+  float* buf;                            // outgoing (pack) or incoming (unpack) messages
+  size_t ps;
+  int w;                                 // storage row width
+  int row0, nrows;                       // first owned storage row, owned rows
+  int gx;                                // columns per message row
+  int col[2];                            // storage column where direction d's segment starts
+  int unpack;
+};
+
+template <typename V>                    // V = f4, f2 or float: the widest access every row segment is aligned for
+__global__ void __launch_bounds__(256) lbm_macro_pack_cols_kernel(const MacroPackColsArgs a)
+{
+  constexpr int kPer = sizeof(V) / sizeof(float);
+  constexpr int kUnroll = 4;
+  const int kv = a.gx / kPer;                                  // vectors of one row segment
+  const int per_plane = a.nrows * kv;
+  const int total = per_plane * 18;
+  const int stride = gridDim.x * 256;
+  for (int w0 = blockIdx.x * 256 + threadIdx.x; w0 < total; w0 += stride * kUnroll) {
+    V v[kUnroll];
+    float* g[kUnroll];
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      const int w = w0 + u * stride;
+      g[u] = nullptr;
+      if (w < total) {
+        const int seg = w / per_plane, i = w - seg * per_plane;
+        const int dir = seg / 9, plane = seg - dir * 9;
+        const int r = i / kv, j = i - r * kv;
+        g[u] = a.grid + plane * a.ps + static_cast<size_t>(a.row0 + r) * a.w + a.col[dir] + j * kPer;
+        v[u] = a.unpack ? *reinterpret_cast<const V*>(a.buf + static_cast<size_t>(w) * kPer) : *reinterpret_cast<const V*>(g[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kUnroll; ++u) {
+      if (!g[u]) continue;
+      if (a.unpack) *reinterpret_cast<V*>(g[u]) = v[u];
+      else *reinterpret_cast<V*>(a.buf + static_cast<size_t>(w0 + u * stride) * kPer) = v[u];
+    }
+  }
+}
+
 // av_velocity (d2q9-bgk.c:716-751): per-cell float arithmetic as the reference, double accumulation.
 // Cell c of the owned rows is bit c + bit0 of the obstacle bitfield (K-step partitions: bit0 = ghost*nx,
 // any value, not only multiples of 32).

@@ -122,6 +122,19 @@ int lbm_decompose_columns(int nx, int px, int* nx_local, int* displs)
   return 0;
 }
 
+// Neighbours of a rank of the px x py rank grid, rank = ry * px + rx, periodic in both directions (the reference's `top` / `bottom`,
+// d2q9-bgk.c:245-247, in each of them): the one rule of the peer-to-peer loop, the RCCL loop and a caller's own communicator.
+int lbm_tile_neighbours(int px, int py, int rank, int out[4])
+{
+  if (px < 1 || py < 1 || rank < 0 || !out || static_cast<long long>(px) * py > 0x7fffffffLL || rank >= px * py) { set_error("lbm_tile_neighbours: bad argument"); return 1; }
+  const int rx = rank % px, ry = rank / px;
+  out[0] = ((ry + py - 1) % py) * px + rx;   // south
+  out[1] = ((ry + 1) % py) * px + rx;        // north
+  out[2] = ry * px + (rx + px - 1) % px;     // west
+  out[3] = ry * px + (rx + 1) % px;          // east
+  return 0;
+}
+
 int lbm_plan_next(int K, int four_rows, int tail4, int left)
 {
   int k = left < K ? left : K;

@@ -139,6 +139,7 @@ struct lbm_ctx {
   int nxp = 0;
   float* halo_alloc = nullptr;
   float* macro_pack[2] = {nullptr, nullptr};   // K-step mode: packed outgoing / incoming messages, [dir][plane][K*nx] each
+  float* macro_pack_x[2] = {nullptr, nullptr}; // tile ranks: packed outgoing / incoming COLUMN messages, [dir][plane][nyl][ghost_x] each (lbm_macro_pack_x)
   float* send[2] = {nullptr, nullptr};
   bool release_sends = false;   // send[] point into peers' windows (one-step peer-to-peer loop)
   float* recv[2] = {nullptr, nullptr};
@@ -852,6 +853,10 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
   if (c->ghost > 0) {
     const size_t pack_floats = static_cast<size_t>(2) * 9 * std::max(c->ghost_rows, 1) * p->nx;
     for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack[i], sizeof(float) * pack_floats));
+    if (c->ghost_x > 0) {             // a tile rank's column messages: here, never during a run (ensure_sums)
+      const size_t pack_floats_x = static_cast<size_t>(2) * 9 * ny_local * c->ghost_x;
+      for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack_x[i], sizeof(float) * pack_floats_x));
+    }
     c->tile_kernel = false;
     c->multi_geom = pick_geom(knobs, c->ncells);
     if (tile && c->ghost_rows == 0 && c->multi_geom == kGeomTall && knobs.multi_geom < 0) {
@@ -1117,6 +1122,7 @@ int lbm_destroy(lbm_ctx* c)
   if (c->mask) (void)hipFree(c->mask);
   if (c->halo_alloc) (void)hipFree(c->halo_alloc);
   for (float* b : c->macro_pack) if (b) (void)hipFree(b);
+  for (float* b : c->macro_pack_x) if (b) (void)hipFree(b);
   for (int i = 0; i < 2; ++i) if (c->partials[i]) (void)hipFree(c->partials[i]);
   if (c->sums) (void)hipFree(c->sums);
   if (c->sums_host) (void)hipHostFree(c->sums_host);
@@ -1460,11 +1466,12 @@ void* lbm_macro_recv_ptr(lbm_ctx* c, int dir, int plane)
 }
 
 // Packed form of the exchange: 2 messages per direction instead of 18.
-size_t lbm_macro_pack_floats(const lbm_ctx* c) { return (c && c->ghost > 0) ? static_cast<size_t>(9) * c->ghost * c->p.nx : 0; }
+// (A column block — a tile rank that owns every row, ghost_rows == 0 — has no row exchange: 0 floats, and pack / unpack refuse.)
+size_t lbm_macro_pack_floats(const lbm_ctx* c) { return (c && c->ghost > 0 && c->ghost_rows > 0) ? static_cast<size_t>(9) * c->ghost * c->p.nx : 0; }
 
 void* lbm_macro_pack_ptr(lbm_ctx* c, int dir, int incoming)
 {
-  if (!c || c->ghost == 0 || (dir != 0 && dir != 1)) return nullptr;
+  if (!c || c->ghost == 0 || c->ghost_rows == 0 || (dir != 0 && dir != 1)) return nullptr;
   return c->macro_pack[incoming ? 1 : 0] + static_cast<size_t>(dir) * lbm_macro_pack_floats(c);
 }
 
@@ -1485,13 +1492,68 @@ static int macro_pack_launch(lbm_ctx* c, bool unpack, hipStream_t s)
 int lbm_macro_pack(lbm_ctx* c, void* stream)
 {
   if (!c || c->ghost == 0) { lbm_internal::set_error("lbm_macro_pack: not a K-step context"); return 1; }
+  if (c->ghost_rows == 0) { lbm_internal::set_error("lbm_macro_pack: a column block keeps no ghost rows (its rows wrap inside the launch): the column exchange is its whole exchange"); return 1; }
   return macro_pack_launch(c, false, pick_stream(c, stream));
 }
 
 int lbm_macro_unpack(lbm_ctx* c, void* stream)
 {
   if (!c || c->ghost == 0) { lbm_internal::set_error("lbm_macro_unpack: not a K-step context"); return 1; }
+  if (c->ghost_rows == 0) { lbm_internal::set_error("lbm_macro_unpack: a column block keeps no ghost rows (its rows wrap inside the launch): the column exchange is its whole exchange"); return 1; }
   return macro_pack_launch(c, true, pick_stream(c, stream));
+}
+
+// ---- the column half of a tile rank's packed exchange ----
+size_t lbm_macro_pack_floats_x(const lbm_ctx* c) { return (c && c->ghost > 0 && c->ghost_x > 0) ? static_cast<size_t>(9) * c->nyl * c->ghost_x : 0; }
+
+void* lbm_macro_pack_ptr_x(lbm_ctx* c, int dir, int incoming)
+{
+  if (!c || c->ghost == 0 || c->ghost_x == 0 || (dir != 0 && dir != 1)) return nullptr;
+  return c->macro_pack_x[incoming ? 1 : 0] + static_cast<size_t>(dir) * lbm_macro_pack_floats_x(c);
+}
+
+static int macro_pack_cols_launch(lbm_ctx* c, bool unpack, hipStream_t s)
+{
+  const int gx = c->ghost_x;
+  MacroPackColsArgs a{};
+  a.grid = c->grid[c->cur]; a.buf = c->macro_pack_x[unpack ? 1 : 0]; a.ps = c->ps; a.w = c->p.nx;
+  a.row0 = c->ghost_rows; a.nrows = c->nyl; a.gx = gx; a.unpack = unpack ? 1 : 0;
+  // outgoing: the first ghost_x owned columns (dir 0, west) and the last (dir 1, east);
+  // incoming: the ghost columns before the owned ones (from the west, dir 0) and after them (from the east, dir 1)
+  a.col[0] = unpack ? 0 : gx;
+  a.col[1] = unpack ? gx + c->nxl : c->nxl;
+  // the widest access every row segment is aligned for, in the grid and in the messages (the test of p2p_push_cols)
+  auto all_mult = [&](int m) { return gx % m == 0 && c->nxl % m == 0 && c->p.nx % m == 0 && c->ps % m == 0; };
+  const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
+  const long long work = 18LL * c->nyl * (gx / per);                 // vectors of the launch
+  if (18LL * c->nyl * gx >= (1LL << 30)) { lbm_internal::set_error("lbm_macro_pack_x: column messages too large for the kernel's 32-bit indices"); return 1; }
+  const dim3 grid(static_cast<unsigned>(std::max(1LL, std::min(4096LL, (work + 1023) / 1024))));
+  if (per == 4) hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<f4>, grid, dim3(256), 0, s, a);
+  else if (per == 2) hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<f2>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<float>, grid, dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int lbm_macro_pack_x(lbm_ctx* c, void* stream)
+{
+  if (!c || c->ghost == 0 || c->ghost_x == 0) { lbm_internal::set_error("lbm_macro_pack_x: not a rank of the tile decomposition (row partitions exchange rows only: lbm_macro_pack)"); return 1; }
+  return macro_pack_cols_launch(c, false, pick_stream(c, stream));
+}
+
+int lbm_macro_unpack_x(lbm_ctx* c, void* stream)
+{
+  if (!c || c->ghost == 0 || c->ghost_x == 0) { lbm_internal::set_error("lbm_macro_unpack_x: not a rank of the tile decomposition (row partitions exchange rows only: lbm_macro_unpack)"); return 1; }
+  return macro_pack_cols_launch(c, true, pick_stream(c, stream));
+}
+
+// lbm_macro_prepare for a rank of the tile decomposition.  A call of its own: a caller that knows the row protocol only would exchange
+// rows and never columns, so lbm_macro_prepare keeps refusing these contexts.
+int lbm_tile_prepare(lbm_ctx* c, int n_steps, void* stream)
+{
+  if (!c || n_steps < 0 || c->ghost == 0 || c->ghost_x == 0) { lbm_internal::set_error("lbm_tile_prepare: not a rank of the tile decomposition (row partitions: lbm_macro_prepare)"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  return begin_run(c, n_steps, pick_stream(c, stream));
 }
 
 int lbm_macro_prepare(lbm_ctx* c, int n_steps, void* stream)
@@ -1683,6 +1745,31 @@ int lbm_macro_exchange_local(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream)
   const size_t bytes = sizeof(float) * lbm_macro_halo_floats(src);
   for (int k = 0; k < 9; ++k)
     HIP_TRY(hipMemcpyAsync(lbm_macro_recv_ptr(dst, dir ^ 1, k), lbm_macro_send_ptr(src, dir, k), bytes, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+// Tile ranks of one process: src's packed message of direction `dir` into dst's incoming buffer of the opposite side, one device copy
+// (between lbm_macro_pack_x / lbm_macro_pack on src and lbm_macro_unpack_x / lbm_macro_unpack on dst; dst == src: a rank that is its own neighbour).
+int lbm_macro_exchange_local_x(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream)
+{
+  if (!dst || !src || dst->ghost_x == 0 || src->ghost_x != dst->ghost_x || src->nyl != dst->nyl || src->ghost != dst->ghost || (dir != 0 && dir != 1)) {
+    lbm_internal::set_error("lbm_macro_exchange_local_x: incompatible contexts (two tile ranks of one rank-grid row, dir 0 or 1)");
+    return 1;
+  }
+  HIP_TRY(hipMemcpyAsync(lbm_macro_pack_ptr_x(dst, dir ^ 1, 1), lbm_macro_pack_ptr_x(src, dir, 0), sizeof(float) * lbm_macro_pack_floats_x(src),
+                         hipMemcpyDeviceToDevice, pick_stream(dst, stream)));
+  return 0;
+}
+
+int lbm_macro_exchange_local_y(lbm_ctx* dst, lbm_ctx* src, int dir, void* stream)
+{
+  if (!dst || !src || dst->ghost_x == 0 || dst->ghost_rows == 0 || src->ghost_rows != dst->ghost_rows || src->ghost_x != dst->ghost_x || src->p.nx != dst->p.nx ||
+      (dir != 0 && dir != 1)) {
+    lbm_internal::set_error("lbm_macro_exchange_local_y: incompatible contexts (two tile ranks with ghost rows of one rank-grid column, dir 0 or 1)");
+    return 1;
+  }
+  HIP_TRY(hipMemcpyAsync(lbm_macro_pack_ptr(dst, dir ^ 1, 1), lbm_macro_pack_ptr(src, dir, 0), sizeof(float) * lbm_macro_pack_floats(src),
+                         hipMemcpyDeviceToDevice, pick_stream(dst, stream)));
   return 0;
 }
 

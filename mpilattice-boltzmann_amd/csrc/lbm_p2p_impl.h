@@ -392,10 +392,9 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
     const int px = ctx->tiles_px, py = ctx->tiles_py, rx = ctx->tile_rx, ry = ctx->tile_ry;
     if (nranks != px * py || rank != ry * px + rx) { lbm_internal::set_error("lbm_p2p_create: the context is rank " + std::to_string(ry * px + rx) + " of " + std::to_string(px * py) + " tiles"); delete t; return 1; }
     t->tiles = true;
-    t->south = ((ry + py - 1) % py) * px + rx;
-    t->north = ((ry + 1) % py) * px + rx;
-    t->west = ry * px + (rx + px - 1) % px;
-    t->east = ry * px + (rx + 1) % px;
+    int nb[4];
+    if (lbm_tile_neighbours(px, py, rank, nb)) { delete t; return 1; }
+    t->south = nb[0]; t->north = nb[1]; t->west = nb[2]; t->east = nb[3];
   }
   t->compute = ctx->stream;
   t->peers.resize(nranks);

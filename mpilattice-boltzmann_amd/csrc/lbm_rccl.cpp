@@ -1,4 +1,5 @@
 // lbm_rccl.cpp — row-partitioned step loop with RCCL halo exchange (include/lbm_d2q9_rccl.h).
+// (Also ranks of the tile decomposition: run_macro below exchanges their columns, then their rows, in the same schedules.)
 //
 // A pure client of the core C ABI (lbm_step_* + halo buffer accessors): this file adds the
 // communicator, two side streams and a few events.  Three queues per rank (reference lines d2q9-bgk.c):
@@ -34,6 +35,9 @@ struct lbm_comm {
   lbm_ctx* ctx = nullptr;
   ncclComm_t nccl = nullptr;
   int nranks = 1, rank = 0, south = 0, north = 0, device = 0;
+  bool tiles = false;              // the context is a rank of the tile decomposition: columns from west / east first, then rows
+  int west = 0, east = 0;
+  bool rows = true;                // ... with ghost rows (a column block exchanges columns only)
   hipStream_t compute = nullptr;   // the context's own stream: interior kernels, folds, final collect
   hipStream_t side = nullptr;      // exchange stream
   hipStream_t edge = nullptr;      // boundary-row kernels
@@ -81,12 +85,16 @@ int lbm_comm_create(lbm_comm** out, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTE
 {
   if (!out || !ctx || !id || nranks < 1 || rank < 0 || rank >= nranks) { lbm_internal::set_error("lbm_comm_create: bad argument"); return 1; }
   *out = nullptr;
-  {
-    lbm_tile_layout tile;
-    if (lbm_tile_info(ctx, &tile) == 0 && tile.ghost_x > 0) {
-      lbm_internal::set_error("lbm_comm_create: the context is a rank of the tile decomposition, which the peer-to-peer loop steps (lbm_p2p_run); the RCCL loop takes row partitions");
+  lbm_tile_layout tile;
+  const bool tiles = lbm_tile_info(ctx, &tile) == 0 && tile.ghost_x > 0;
+  int nb[4] = {0, 0, 0, 0};
+  if (tiles) {
+    if (nranks != tile.px * tile.py || rank != tile.ry * tile.px + tile.rx) {
+      lbm_internal::set_error("lbm_comm_create: the context is rank " + std::to_string(tile.ry * tile.px + tile.rx) + " of the " + std::to_string(tile.px) + " x " +
+                              std::to_string(tile.py) + " tile decomposition, the communicator's rank " + std::to_string(rank) + " of " + std::to_string(nranks));
       return 1;
     }
+    LBM_TRY(lbm_tile_neighbours(tile.px, tile.py, rank, nb));
   }
   lbm_comm* c = new lbm_comm();
   c->ctx = ctx;
@@ -94,6 +102,11 @@ int lbm_comm_create(lbm_comm** out, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTE
   c->rank = rank;
   c->south = (rank + nranks - 1) % nranks;   // `top`    d2q9-bgk.c:245-246
   c->north = (rank + 1) % nranks;            // `bottom` d2q9-bgk.c:247
+  if (tiles) {                               // rank = ry * px + rx, periodic in both directions
+    c->tiles = true;
+    c->south = nb[0]; c->north = nb[1]; c->west = nb[2]; c->east = nb[3];
+    c->rows = tile.ghost_y > 0;
+  }
   c->device = lbm_device(ctx);
   c->compute = static_cast<hipStream_t>(lbm_stream(ctx));
   auto fail = [&]() { lbm_comm_destroy(c); return 1; };
@@ -106,8 +119,13 @@ int lbm_comm_create(lbm_comm** out, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTE
     // every rank must run the same stepping mode with the same K and message size: ranks that disagree would
     // post sends and receives of different sizes at different cadences (hang, or corrupted ghost rows).
     // min and max over ranks of (K, message floats) must coincide.
+    // (Tile ranks: the message sizes legitimately differ between ranks — column blocks are uneven — and the two ends of every message agree
+    // by construction: west / east neighbours share their rows, south / north neighbours their columns.  What must coincide is
+    // (K, ghost, ghost_x, ghost_y, px, py), packed into the second word; a row partition's word is its message size, never negative.)
     long long mine[4], *dev = nullptr;
-    const long long k = lbm_macro_steps(ctx), n = k > 0 ? static_cast<long long>(lbm_macro_pack_floats(ctx)) : static_cast<long long>(lbm_halo_floats(ctx));
+    const long long k = lbm_macro_steps(ctx);
+    long long n = k > 0 ? static_cast<long long>(lbm_macro_pack_floats(ctx)) : static_cast<long long>(lbm_halo_floats(ctx));
+    if (tiles) n = -1 - ((((static_cast<long long>(tile.ghost) * 64 + tile.ghost_x) * 64 + tile.ghost_y) * 65536 + tile.px) * 65536 + tile.py);
     mine[0] = k; mine[1] = -k; mine[2] = n; mine[3] = -n;
     hipStream_t s0 = c->compute;
     bool ok = hipMalloc(&dev, sizeof mine) == hipSuccess && hipMemcpyAsync(dev, mine, sizeof mine, hipMemcpyHostToDevice, s0) == hipSuccess;
@@ -117,6 +135,10 @@ int lbm_comm_create(lbm_comm** out, lbm_ctx* ctx, const char id[LBM_COMM_ID_BYTE
     }
     if (dev) (void)hipFree(dev);
     if (!ok) { lbm_internal::set_error("lbm_comm_create: layout check (ncclAllReduce) failed"); return fail(); }
+    if (tiles && (mine[0] != -mine[1] || mine[2] != -mine[3])) {
+      lbm_internal::set_error("lbm_comm_create: ranks of the tile decomposition disagree about their layout (K, ghost rows, ghost columns or the rank grid): create every rank with lbm_create_tile on one rank grid");
+      return fail();
+    }
     if (mine[0] != -mine[1] || mine[2] != -mine[3]) {
       lbm_internal::set_error("lbm_comm_create: ranks disagree about the stepping mode (K between " + std::to_string(-mine[1]) + " and " +
                               std::to_string(mine[0]) + ", halo message between " + std::to_string(-mine[3]) + " and " + std::to_string(mine[2]) +
@@ -182,13 +204,14 @@ int lbm_comm_destroy(lbm_comm* c)
 static int run_macro(lbm_comm* c, int n_steps, double* tot_u_per_step)
 {
   lbm_ctx* ctx = c->ctx;
-  const size_t np = lbm_macro_pack_floats(ctx);
+  const size_t np = lbm_macro_pack_floats(ctx), npx = lbm_macro_pack_floats_x(ctx);   // (np = 0: a column block, no row exchange)
   const bool three_queues = c->three_queues;
   hipStream_t edge_stream = c->edge;
   // small ranks (one-queue schedule): the exchange goes to the compute stream as well — every hand-off between queues costs 6 - 8 us of idle
   // queue, and there is no launch long enough to hide the exchange behind (a 1024 x 128-row ring: 26 of 98 us per exchange were hand-offs)
   hipStream_t xs = three_queues ? c->side : c->compute;
-  LBM_TRY(lbm_macro_prepare(ctx, n_steps, c->compute));   // step-0 accelerate_flow
+  if (c->tiles) LBM_TRY(lbm_tile_prepare(ctx, n_steps, c->compute));
+  else LBM_TRY(lbm_macro_prepare(ctx, n_steps, c->compute));   // step-0 accelerate_flow
   HIP_TRY(hipEventRecord(c->edge_done, c->compute));
   HIP_TRY(hipEventRecord(c->interior_done, c->compute));
   int prev_launches = 1;
@@ -201,15 +224,29 @@ static int run_macro(lbm_comm* c, int n_steps, double* tot_u_per_step)
       HIP_TRY(hipStreamWaitEvent(c->side, c->edge_done, 0));
       HIP_TRY(hipStreamWaitEvent(c->side, c->interior_done, 0));
     }
-    // gather the 9 planes' rows into one message per direction, exchange 2 + 2 messages, scatter
-    LBM_TRY(lbm_macro_pack(ctx, xs));
-    NCCL_TRY(ncclGroupStart());                            // order as in the one-step loop: sends [S, N], receives [N, S]
-    NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 0, 0), np, ncclFloat, c->south, c->nccl, xs));
-    NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 1, 0), np, ncclFloat, c->north, c->nccl, xs));
-    NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 1, 1), np, ncclFloat, c->north, c->nccl, xs));
-    NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 0, 1), np, ncclFloat, c->south, c->nccl, xs));
-    NCCL_TRY(ncclGroupEnd());
-    LBM_TRY(lbm_macro_unpack(ctx, xs));
+    if (c->tiles) {
+      // tile rank, first phase: the ghost columns — sends [W, E], receives [E, W], which keeps two messages to one peer apart (px <= 2) as below
+      LBM_TRY(lbm_macro_pack_x(ctx, xs));
+      NCCL_TRY(ncclGroupStart());
+      NCCL_TRY(ncclSend(lbm_macro_pack_ptr_x(ctx, 0, 0), npx, ncclFloat, c->west, c->nccl, xs));
+      NCCL_TRY(ncclSend(lbm_macro_pack_ptr_x(ctx, 1, 0), npx, ncclFloat, c->east, c->nccl, xs));
+      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr_x(ctx, 1, 1), npx, ncclFloat, c->east, c->nccl, xs));
+      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr_x(ctx, 0, 1), npx, ncclFloat, c->west, c->nccl, xs));
+      NCCL_TRY(ncclGroupEnd());
+      LBM_TRY(lbm_macro_unpack_x(ctx, xs));
+    }
+    // gather the 9 planes' rows into one message per direction, exchange 2 + 2 messages, scatter (tile ranks: storage rows, with the ghost
+    // columns that have just arrived — the corners; a column block has no rows to exchange)
+    if (c->rows) {
+      LBM_TRY(lbm_macro_pack(ctx, xs));
+      NCCL_TRY(ncclGroupStart());                            // order as in the one-step loop: sends [S, N], receives [N, S]
+      NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 0, 0), np, ncclFloat, c->south, c->nccl, xs));
+      NCCL_TRY(ncclSend(lbm_macro_pack_ptr(ctx, 1, 0), np, ncclFloat, c->north, c->nccl, xs));
+      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 1, 1), np, ncclFloat, c->north, c->nccl, xs));
+      NCCL_TRY(ncclRecv(lbm_macro_pack_ptr(ctx, 0, 1), np, ncclFloat, c->south, c->nccl, xs));
+      NCCL_TRY(ncclGroupEnd());
+      LBM_TRY(lbm_macro_unpack(ctx, xs));
+    }
     if (three_queues) HIP_TRY(hipEventRecord(c->halo, c->side));
     if (three_queues) {
       if (prev_launches == 1) HIP_TRY(hipStreamWaitEvent(c->compute, c->edge_done, 0));

@@ -113,6 +113,14 @@ def tile_layout(params: Params, px: int, py: int, rank: int, flags: int = 0) -> 
     return {name: int(getattr(lay, name)) for name, _ in _capi.CTileLayout._fields_}
 
 
+def tile_neighbours(px: int, py: int, rank: int) -> dict:
+    """`lbm_tile_neighbours`: the ranks south, north, west and east of rank = ry * px + rx on the periodic px x py rank grid."""
+    lib = _capi.load_library()
+    out = (C.c_int * 4)()
+    check(lib.lbm_tile_neighbours(px, py, rank, out))
+    return dict(zip(("south", "north", "west", "east"), (int(v) for v in out)))
+
+
 def choose_rank_grid(params: Params, nranks: int, flags: int = 0) -> Optional[tuple[int, int]]:
     """`lbm_choose_rank_grid`: None for the reference's row blocks, or (px, py) for the tile decomposition — whichever leaves the ranks
     the fewest cells to recompute (grids much wider than tall come out as tiles)."""
@@ -282,6 +290,58 @@ class Partition:
     def macro_receive_from(self, src: "Partition", direction: int, stream=None) -> None:
         """In-process exchange: src's rows travelling in `direction` become this partition's ghost rows."""
         check(self._lib.lbm_macro_exchange_local(self._ctx, src._ctx, direction, self._stream_ptr(stream)))
+
+    # -- split-phase stepping of a rank of the tile decomposition (include/lbm_d2q9.h): columns first, then rows --
+    def tile_prepare(self, n_steps: int, stream=None) -> None:
+        """`lbm_tile_prepare`: what `macro_prepare` is for row partitions."""
+        check(self._lib.lbm_tile_prepare(self._ctx, n_steps, self._stream_ptr(stream)))
+
+    def tile_neighbours(self) -> dict:
+        """The neighbours of this rank on its rank grid (`tile_neighbours`)."""
+        lay = self.tile_info()
+        return tile_neighbours(lay["px"], lay["py"], lay["ry"] * lay["px"] + lay["rx"])
+
+    @property
+    def macro_pack_floats_x(self) -> int:
+        """Floats of one column message (0: not a tile rank)."""
+        return int(self._lib.lbm_macro_pack_floats_x(self._ctx))
+
+    @property
+    def macro_pack_floats(self) -> int:
+        """Floats of one row message of the packed exchange (0: no row exchange — a column block, or not a K-step context)."""
+        return int(self._lib.lbm_macro_pack_floats(self._ctx))
+
+    def macro_pack_ptr_x(self, direction: int, incoming: bool) -> Optional[int]:
+        """Device address of a column message: direction 0 west, 1 east; an incoming one is named by the side it came from."""
+        return self._lib.lbm_macro_pack_ptr_x(self._ctx, direction, 1 if incoming else 0)
+
+    def macro_pack_ptr(self, direction: int, incoming: bool) -> Optional[int]:
+        return self._lib.lbm_macro_pack_ptr(self._ctx, direction, 1 if incoming else 0)
+
+    def macro_pack_x(self, stream=None) -> None:
+        check(self._lib.lbm_macro_pack_x(self._ctx, self._stream_ptr(stream)))
+
+    def macro_unpack_x(self, stream=None) -> None:
+        check(self._lib.lbm_macro_unpack_x(self._ctx, self._stream_ptr(stream)))
+
+    def macro_pack(self, stream=None) -> None:
+        check(self._lib.lbm_macro_pack(self._ctx, self._stream_ptr(stream)))
+
+    def macro_unpack(self, stream=None) -> None:
+        check(self._lib.lbm_macro_unpack(self._ctx, self._stream_ptr(stream)))
+
+    def macro_all(self, stream=None) -> None:
+        """`macro_interior` + `macro_edge` as one launch, for an exchange that is complete in stream order."""
+        check(self._lib.lbm_macro_all(self._ctx, self._stream_ptr(stream)))
+
+    def macro_receive_from_x(self, src: "Partition", direction: int, stream=None) -> None:
+        """In-process exchange of tile ranks: src's packed column message of `direction` (0 west, 1 east) becomes this rank's incoming
+        message from the opposite side (between `macro_pack_x` on src and `macro_unpack_x` here)."""
+        check(self._lib.lbm_macro_exchange_local_x(self._ctx, src._ctx, direction, self._stream_ptr(stream)))
+
+    def macro_receive_from_y(self, src: "Partition", direction: int, stream=None) -> None:
+        """The row twin: src's packed row message of `direction` (0 south, 1 north), between `macro_pack` and `macro_unpack`."""
+        check(self._lib.lbm_macro_exchange_local_y(self._ctx, src._ctx, direction, self._stream_ptr(stream)))
 
     # -- lifetime --
     def close(self) -> None:
@@ -752,7 +812,7 @@ class Simulation:
         hands each rank its window of rows (the reference's `MPI_Scatterv`, `d2q9-bgk.c:968-970`) and the
         free-cell count (`MPI_Bcast`, `:966`).
         rank_grid = (px, py): the tile (2-D) decomposition over px x py = size ranks (`tile_layout`) instead of the
-        reference's row blocks — peer-to-peer loop only; (1, 1) is a one-rank ring that exchanges with itself;
+        reference's row blocks — the native loops only (p2p, then rccl); (1, 1) is a one-rank ring that exchanges with itself;
         "auto": `choose_rank_grid` decides between row blocks and tiles."""
         if exchange not in EXCHANGES:
             raise ValueError(f"exchange must be one of {EXCHANGES}")
@@ -775,13 +835,13 @@ class Simulation:
         if isinstance(rank_grid, str):
             if rank_grid != "auto":
                 raise ValueError("rank_grid is (px, py), None or \"auto\"")
-            rank_grid = choose_rank_grid(params, self.size, flags) if exchange in ("auto", "p2p") and not step_allreduce else None
+            rank_grid = choose_rank_grid(params, self.size, flags) if exchange in ("auto", "p2p", "rccl") else None
         if rank_grid is not None:
             px, py = int(rank_grid[0]), int(rank_grid[1])
             if px < 1 or py < 1 or px * py != self.size:
                 raise ValueError(f"rank_grid {rank_grid} does not match {self.size} rank(s)")
-            if exchange not in ("auto", "p2p") or step_allreduce:
-                raise ValueError("the tile decomposition is stepped by the peer-to-peer loop only")
+            if exchange not in ("auto", "p2p", "rccl"):
+                raise ValueError("the tile decomposition is stepped by the native loops (exchange \"auto\", \"p2p\" or \"rccl\"); the torch loop takes row blocks")
             self.rank_grid = (px, py)
         self._partitioned = self.size > 1 or bool(flags & _capi.FLAG_FORCE_HALO) or self.rank_grid is not None
         self._flags = flags
@@ -811,7 +871,7 @@ class Simulation:
         # try the loops in order; what could not be set up on EVERY rank is skipped by all ranks together
         order = {"p2p": ["p2p", "rccl", "torch"], "rccl": ["rccl", "torch"], "torch": ["torch"]}[want]
         if self.rank_grid is not None:
-            order = ["p2p"]
+            order = [loop for loop in order if loop != "torch"]   # (the Python-driven one-step loop takes row blocks)
         last_err = None
         for loop in order:
             one_step = _capi.FLAG_ONE_STEP if loop == "torch" else 0

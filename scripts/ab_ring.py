@@ -7,7 +7,12 @@ synchronise per run as bench.py times it.
 
 Each positional argument is one setting: comma-separated KEY=VALUE pairs put into the environment while its ring is created
 (the library reads its knobs when it creates a context or a transport: csrc/lbm_knobs.h); a setting "-" is the default
-environment.  --per-context is the only mode and is accepted for old command lines; --single runs the grid as one periodic
+environment.  The key LBM_EXCHANGE in a setting is that ring's loop (p2p | rccl) instead of --exchange; --rank-grid 1x1 makes the rings
+one rank of the tile (2-D) decomposition:
+
+    python scripts/ab_ring.py --grid 2048x512 --rank-grid 1x1 --steps 400 --rounds 24 - LBM_EXCHANGE=rccl
+
+--per-context is the only mode and is accepted for old command lines; --single runs the grid as one periodic
 launch per macro-step instead of a ring."""
 import argparse
 import os
@@ -25,6 +30,7 @@ ap.add_argument("--grid", default="8192x1024")
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=40)
 ap.add_argument("--exchange", default="p2p")
+ap.add_argument("--rank-grid", default="", help="1x1: a tile rank that is its own neighbour in all four directions")
 ap.add_argument("--per-context", action="store_true", help="the only mode (every setting gets its own ring)")
 ap.add_argument("--single", action="store_true")
 ap.add_argument("settings", nargs="+")
@@ -45,13 +51,17 @@ def apply(setting):
 def make():
     if a.single:
         return lbm.Simulation(p, obst)
-    return lbm.Simulation(p, obst, flags=lbm._capi.FLAG_FORCE_HALO, exchange=a.exchange, strict=True)
+    exchange = os.environ.get("LBM_EXCHANGE", a.exchange)
+    if a.rank_grid:
+        return lbm.Simulation(p, obst, exchange=exchange, strict=True, rank_grid=tuple(int(v) for v in a.rank_grid.split("x")))
+    return lbm.Simulation(p, obst, flags=lbm._capi.FLAG_FORCE_HALO, exchange=exchange, strict=True)
 
 
 sims = {}
 for s in a.settings:
     keys = apply(s)
     sims[s] = make()
+    assert sims[s].loop in ("single", os.environ.get("LBM_EXCHANGE", a.exchange)), sims[s].describe()
     for k in keys:
         os.environ.pop(k, None)
     sims[s].run(a.steps)
