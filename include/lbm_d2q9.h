@@ -45,7 +45,8 @@ typedef struct lbm_ctx lbm_ctx;     /* opaque: device state of one partition */
 #define LBM_FLAG_DEFAULT       0u
 #define LBM_FLAG_NT_STORES     1u   /* force non-temporal stores of the output grid (default: auto by size) */
 #define LBM_FLAG_NO_NT_STORES  2u   /* force plain stores */
-#define LBM_FLAG_KERNEL_LDS    4u   /* use the LDS-staged row kernel instead of the direct-load kernel */
+#define LBM_FLAG_KERNEL_LDS    4u   /* RETIRED: selected the LDS-staged one-step kernel, which was never faster and is no longer built;
+                                       lbm_create* refuse it (the value stays reserved) */
 #define LBM_FLAG_GRAPH        16u   /* lbm_run: replay 64-step hipGraphs instead of launching every step (measured: no
                                        gain on MI355X, the small grids are bound by device-side launch latency) */
 #define LBM_FLAG_ONE_STEP     32u   /* row-partitioned run: keep the one-step split-phase calls (lbm_step_*) even when
@@ -70,8 +71,8 @@ typedef struct lbm_ctx lbm_ctx;     /* opaque: device state of one partition */
                                        128 x 128 0.965 against 1.012 us (0.953).
                                        May be combined with LBM_FLAG_GRAPH (the captured launches are the fused ones).
                                        Refused together with LBM_FLAG_FAST_AVVELS / LBM_FLAG_EXACT_AVVELS (each kernel family carries its
-                                       default form of the sum|u| terms only) and by a library built with -DLBM_EXPERIMENTS=1.  Every rank
-                                       of a partitioned run must pass it or none (not checked, as for every flag). */
+                                       default form of the sum|u| terms only).  Every rank of a partitioned run must pass it or none
+                                       (not checked, as for every flag). */
 #define LBM_FLAG_FORCE_HALO    8u   /* treat a whole-grid partition like any other rank: edge rows read the halo
                                        buffers (a 1-rank run that exchanges with itself, d2q9-bgk.c:245-247) */
 

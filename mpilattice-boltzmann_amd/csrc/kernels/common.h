@@ -411,7 +411,7 @@ __device__ __forceinline__ auto& at_byte(B* base, uint32_t byte_off)
 // tile_accel is block-uniform: false for the tiles whose frame does not meet row ny-2, which then skip
 // the accelerate_flow code instead of predicating it away in every pair.
 // TERMS: how the sum|u| term of a cell, sqrt((double)msq) * (double)rinv (:667), is formed.  Populations never depend on it.
-//   kTermsDouble (LBM_FLAG_EXACT_AVVELS; the tile and sweep kernels' default): in double precision, every term correctly
+//   kTermsDouble (LBM_FLAG_EXACT_AVVELS; lbm_tile_kernel's default): in double precision, every term correctly
 //     rounded before the product: v_rsq_f64 + 9 double-precision instructions per CELL.
 //   kTermsCompensated (lbm_multi_kernel's default): without double-precision arithmetic.  The root as an unevaluated float
 //     sum s + c (s = msq * rsq(msq); c = the Newton correction of s from the residual msq - s*s, which a fused multiply-add
@@ -484,7 +484,7 @@ __device__ __forceinline__ double finish_pair_lo(const f2 (&t)[9], uint32_t mbit
   return term;
 }
 
-// The same with the pair's sum as one double (the tile and sweep kernels: TERMS = false / true = double / float).
+// The same with the pair's sum as one double (lbm_tile_kernel, and lbm_multi_kernel's tall geometry).
 template <int TERMS = kTermsDouble>
 __device__ __forceinline__ double finish_pair(const f2 (&t)[9], uint32_t mbits, float omega, bool tile_accel, bool accel, float w1, float w2,
                                               uint32_t skip, f2 (&out)[9])

@@ -1,4 +1,4 @@
-// step.h — one step per launch: lbm_step_kernel (4 cells per lane), lbm_step_kernel_narrow (1 cell per lane), lbm_step_kernel_lds (LDS-staged variant)
+// step.h — one step per launch: lbm_step_kernel<CELLS, NT, FUSED> (4 cells per lane, or 1: the narrow form)
 // Part of the single translation unit lbm_kernels.hip (device code of liblbm_d2q9.so, gfx950 only).
 #pragma once
 #include "common.h"
@@ -152,114 +152,41 @@ __device__ __forceinline__ double step_cell(const StepArgs& a, int cell)
   return blocked ? 0.0 : term;
 }
 
-#if LBM_EXPERIMENTS   // (not in liblbm_d2q9.so as shipped: never faster than the direct-load form — no value is reused)
-// LDS-staged form (LBM_FLAG_KERNEL_LDS), the tiling BASELINE.json's north_star sentence describes:
-// every global load is 16-byte aligned; the x-1 / x+1 values a lane needs from its neighbours'
-// vectors travel through an LDS tile row with one halo column per side (filled from global memory
-// by the first / last lane of the block), and the chunk's 1024 obstacle bits sit in LDS as a
-// bitfield.  Same arithmetic, same results; kept as a measured alternative.
-struct LdsTile {
-  float w[3][kBlock + 2];      // [k][1+lane] = .w of populations 1,5,8 of that lane: the x-1 source of lane+1; [0] = halo
-  float e[3][kBlock + 2];      // [k][1+lane] = .x of populations 3,6,7: the x+1 source of lane-1; [kBlock+1] = halo
-  uint32_t mask[kBlock / 8 + 1];   // the (up to) 33 words holding the chunk's 1024 obstacle bits
-};
-
-template <bool NT>
-__device__ __forceinline__ double step_quad_lds(const StepArgs& a, int quad, bool active, int chunk_first_cell, LdsTile& tile)
+// The one-step kernel, one definition for every instantiation (the host's kStepKernels table, lbm_kernels.hip): CELLS = cells per lane
+// (kCellsPerLane: step_quad; 1: step_cell — the unit ranges of StepArgs are then cell ranges), NT = non-temporal stores, FUSED =
+// LBM_FLAG_FUSED_ARITH.  lbm_describe still names the families lbm_step_kernel / lbm_step_kernel_narrow and *_fused.  That this text
+// compiles to the code the per-family definitions gave is recorded in profiles/r06/isa_identity.txt.
+// Grid: ceil(#units / (256*iters)) work blocks of 256 lanes (block b owns `iters` consecutive 256-unit chunks) after one fold
+// block (block 0, dispatched first).
+template <int CELLS, bool NT, bool FUSED>
+__global__ void __launch_bounds__(kBlock) lbm_step_kernel(const StepArgs a)
 {
-  const int tid = threadIdx.x;
-  const int c = quad * kCellsPerLane;
-  const int y = active ? c / a.nx : 0;
-  const int x0 = c - y * a.nx;
-  const size_t ps = a.ps;
-  const int nx = a.nx;
-  const int word0 = chunk_first_cell >> 5;
-  f4 p[9];
-  float hw[3] = {0.f, 0.f, 0.f}, he[3] = {0.f, 0.f, 0.f};
-  const bool row_start = active && x0 == 0;                       // x_w wraps to nx-1 (:529)
-  const bool row_end = active && x0 == nx - kCellsPerLane;        // x_e wraps to 0   (:527-528)
-  if (tid <= kBlock / 8 && word0 + tid < a.mask_words) tile.mask[tid] = a.mask[word0 + tid];
-  if (active) {
-    const RowPtrs r = source_rows(a, y);
-    p[0] = load4(r.here + x0);
-    p[1] = load4(r.here + ps + x0);
-    p[2] = load4(r.s2 + x0);
-    p[3] = load4(r.here + 3 * ps + x0);
-    p[4] = load4(r.n4 + x0);
-    p[5] = load4(r.s5 + x0);
-    p[6] = load4(r.s6 + x0);
-    p[7] = load4(r.n7 + x0);
-    p[8] = load4(r.n8 + x0);
-    tile.w[0][tid + 1] = p[1].w; tile.w[1][tid + 1] = p[5].w; tile.w[2][tid + 1] = p[8].w;
-    tile.e[0][tid + 1] = p[3].x; tile.e[1][tid + 1] = p[6].x; tile.e[2][tid + 1] = p[7].x;
-    // halo columns of the tile row (only the block's first / last lane have no neighbour lane) and
-    // the periodic wrap for lanes sitting on a row edge inside the block
-    if (tid == 0 || row_start) {
-      const int xw = row_start ? nx - 1 : x0 - 1;
-      hw[0] = r.here[ps + xw]; hw[1] = r.s5[xw]; hw[2] = r.n8[xw];
-      if (tid == 0) { tile.w[0][0] = hw[0]; tile.w[1][0] = hw[1]; tile.w[2][0] = hw[2]; }
-    }
-    if (tid == kBlock - 1 || row_end) {
-      const int xe = row_end ? 0 : x0 + kCellsPerLane;
-      he[0] = r.here[3 * ps + xe]; he[1] = r.s6[xe]; he[2] = r.n7[xe];
-      if (tid == kBlock - 1) { tile.e[0][kBlock + 1] = he[0]; tile.e[1][kBlock + 1] = he[1]; tile.e[2][kBlock + 1] = he[2]; }
-    }
-  }
-  __syncthreads();
-  double acc = 0.0;
-  if (active) {
-    const float w1 = row_start ? hw[0] : tile.w[0][tid], w5 = row_start ? hw[1] : tile.w[1][tid],
-                w8 = row_start ? hw[2] : tile.w[2][tid];
-    const float e3 = row_end ? he[0] : tile.e[0][tid + 2], e6 = row_end ? he[1] : tile.e[1][tid + 2],
-                e7 = row_end ? he[2] : tile.e[2][tid + 2];
-    const f4 c1 = p[1], c5 = p[5], c8 = p[8], c3 = p[3], c6 = p[6], c7 = p[7];
-    p[1] = f4{w1, c1.x, c1.y, c1.z};
-    p[5] = f4{w5, c5.x, c5.y, c5.z};
-    p[8] = f4{w8, c8.x, c8.y, c8.z};
-    p[3] = f4{c3.y, c3.z, c3.w, e3};
-    p[6] = f4{c6.y, c6.z, c6.w, e6};
-    p[7] = f4{c7.y, c7.z, c7.w, e7};
-    const uint32_t mbits = (tile.mask[(c >> 5) - word0] >> (c & 31)) & 0xFu;
-    acc = finish_quad<NT>(a, c, y, x0, p, mbits);
-  }
-  __syncthreads();   // the tile is rewritten by the next chunk
-  return acc;
-}
-
-// Same grid / chunk mapping as lbm_step_kernel, single contiguous quad range only (the two-row
-// boundary launch of a row-partitioned run always uses the direct form).
-template <bool NT>
-__global__ void __launch_bounds__(kBlock) lbm_step_kernel_lds(const StepArgs a)
-{
+  static_assert(CELLS == 1 || CELLS == kCellsPerLane, "one cell or one quad per lane");
   __shared__ double red[kBlock / 64];
-  __shared__ LdsTile tile;
   if (blockIdx.x == 0) { fold_previous(a, red); return; }
   const int wblock = blockIdx.x - 1;   // work block index
   double acc = 0.0;
   const int n1 = a.quad_end - a.quad_begin;
+  const int n2 = a.quad_end2 > a.quad_begin2 ? a.quad_end2 - a.quad_begin2 : 0;
+  const int base = wblock * a.iters * kBlock + threadIdx.x;
   for (int i = 0; i < a.iters; ++i) {
-    const int r0 = (wblock * a.iters + i) * kBlock;          // block-uniform: every lane reaches the barriers
-    if (r0 >= n1) break;
-    const int r = r0 + threadIdx.x;
-    acc += step_quad_lds<NT>(a, a.quad_begin + r, r < n1, (a.quad_begin + r0) * kCellsPerLane, tile);
+    const int r = base + i * kBlock;
+    if (r < n1 + n2) {
+      const int unit = r < n1 ? a.quad_begin + r : a.quad_begin2 + (r - n1);
+      if constexpr (CELLS == 1) acc += step_cell<NT, FUSED>(a, unit);
+      else acc += step_quad<NT, FUSED>(a, unit);
+    }
   }
   acc = block_sum(acc, red);
-  if (threadIdx.x == 0) a.partials_out[wblock] = acc;
+  // boundary launch of a peer-to-peer run: the outgoing halo rows were stored straight into the neighbours' windows;
+  // a full barrier drains every wave's stores (block_sum's barriers order LDS only), then one lane writes the XCD's L2
+  // back towards the peers
+  if (a.release_sends) __syncthreads();
+  if (threadIdx.x == 0) {
+    a.partials_out[wblock] = acc;
+    if (a.release_sends) __atomic_thread_fence(__ATOMIC_RELEASE);
+  }
 }
-#endif   // LBM_EXPERIMENTS
-
-// The two one-step kernels are defined from ONE text, kernels/step_kernel_def.h, included once per arithmetic (as kernels/tile.h does for
-// lbm_tile_kernel): lbm_step_kernel<NT> / lbm_step_kernel_narrow<NT> (the exact arithmetic: the tokens, and with them the code, they had
-// before the fused form existed) and lbm_step_kernel_fused<NT> / lbm_step_kernel_narrow_fused<NT> (LBM_FLAG_FUSED_ARITH; not in the
-// experiment build).
-#define LBM_STEP_FUSED 0
-#include "step_kernel_def.h"
-#undef LBM_STEP_FUSED
-#if !LBM_EXPERIMENTS
-#define LBM_STEP_FUSED 1
-#include "step_kernel_def.h"
-#undef LBM_STEP_FUSED
-#endif
 
 __device__ __forceinline__ void fold_previous(const StepArgs& a, double* red)
 {

@@ -16,8 +16,7 @@
 //   kernels/multi.h  lbm_multi_kernel<K>                K steps per pass over HBM, 64x16 / 64x13 / 64x24 tiles, intermediate
 //                                                       states in LDS — large grids and K-step row partitions
 //   kernels/tile.h   lbm_tile_kernel<T,H>               up to H steps per launch, launch-latency-bound small grids
-//   kernels/step.h   lbm_step_kernel / _narrow / _lds   one step per launch (4 cells or 1 cell per lane; the
-//                                                       LDS-staged variant) — everything else
+//   kernels/step.h   lbm_step_kernel / _narrow          one step per launch (4 cells or 1 cell per lane) — everything else
 //   kernels/aux.h    fold, accelerate pre-pass, initial state, AoS<->SoA, halo pack/unpack, av_velocity
 //
 // Layout in HBM: struct-of-arrays, 9 planes of rows*nx floats (plane stride padded, see
@@ -54,12 +53,6 @@
 #include "kernels/step.h"
 #include "kernels/tile.h"
 #include "kernels/multi.h"
-#ifndef LBM_EXPERIMENTS      // -DLBM_EXPERIMENTS=1 (scripts/build_variant.sh experiments): the forms that measured slower and are kept for the
-#define LBM_EXPERIMENTS 0    // record — lbm_sweep_kernel (LBM_TUNE_SWEEP), lbm_step_kernel_lds (LBM_FLAG_KERNEL_LDS) — with their parity tests
-#endif                       // (tests/experiments_suite.py); liblbm_d2q9.so as shipped does not carry them
-#if LBM_EXPERIMENTS
-#include "kernels/sweep.h"
-#endif
 #include "kernels/aux.h"
 #include "kernels/p2p.h"
 
@@ -134,7 +127,6 @@ struct lbm_ctx {
   int cur = 0;
   uint32_t* mask = nullptr;
   int mask_words = 0;
-  bool lds_kernel = false;   // LBM_FLAG_KERNEL_LDS
   int lane_cells = kCellsPerLane;   // cells per lane: 4 (vector form) or 1 (narrow form: tiny grids, nx % 4 != 0)
   int nxp = 0;
   float* halo_alloc = nullptr;
@@ -174,9 +166,6 @@ struct lbm_ctx {
   int multi_geom = kGeomStd; // geometry of lbm_multi_kernel's launches (kernels/multi.h): standard, narrow (32-wide tiles), tall (K = 4 on 64 x 24)
   int multi_tx = kMTX;       // its tile width: 64, or 32 for partitions of one round of blocks
   bool multi_tail4 = true;   // lbm_run at K = 3: 4-step launches instead of a 1- or 2-step tail (LBM_TUNE_MULTI_TAIL4)
-  int sweep_R = 0;           // > 0: lbm_run's 3-step launches are lbm_sweep_kernel<R> (streaming temporal blocking, kernels/sweep.h)
-  int sweep_nseg = 0, sweep_seg_rows = 0;
-  int sweep_mode = 2;        // storage form of the pipeline (kernels/sweep.h SweepGeom; LBM_TUNE_SWEEP_MODE)
   bool tile_kernel = false;  // lbm_run advances several steps per launch with lbm_tile_kernel (small grids)
   int tile_T = 16, tile_H = 8;   // its geometry: owned tile edge, ghost ring = max steps per launch
   int tile_single_max = 0;       // sub-steps with regions of at most this many cells deal one cell per lane
@@ -191,6 +180,15 @@ struct lbm_ctx {
 };
 
 namespace {
+
+// Which kernel family advances this context: lbm_multi_kernel (whole grids it tiles and every K-step partition), lbm_tile_kernel (small whole
+// grids), or the one-step kernels (everything else).  lbm_run launches by it and lbm_describe names it.
+enum KernelFamily { kFamilyMulti, kFamilyTile, kFamilyStep };
+KernelFamily family_of(const lbm_ctx* c)
+{
+  if (c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) return kFamilyMulti;
+  return (c->tile_kernel && c->self_periodic) ? kFamilyTile : kFamilyStep;
+}
 
 // max_blocks (LBM_TUNE_MAXBLOCKS): measured on 8192x8192, 16384 blocks x 4 chunks ~7 % faster than 4096 x 16
 int pick_iters(long long quads, int max_blocks)
@@ -271,42 +269,27 @@ StepArgs base_args(lbm_ctx* c, bool accel_next)
   return a;
 }
 
+// Every instantiation of the one-step kernel, by [narrow form: one cell per lane][non-temporal stores][fused arithmetic].
+using StepKernel = void (*)(StepArgs);
+constexpr StepKernel kStepKernels[2][2][2] = {
+  {{&lbm_step_kernel<kCellsPerLane, false, false>, &lbm_step_kernel<kCellsPerLane, false, true>},
+   {&lbm_step_kernel<kCellsPerLane, true, false>, &lbm_step_kernel<kCellsPerLane, true, true>}},
+  {{&lbm_step_kernel<1, false, false>, &lbm_step_kernel<1, false, true>},
+   {&lbm_step_kernel<1, true, false>, &lbm_step_kernel<1, true, true>}},
+};
+
 void launch_step(lbm_ctx* c, const StepArgs& a, int blocks, hipStream_t s)
 {
-  const dim3 grid(blocks + 1), block(kBlock);   // + the fold block
-#if !LBM_EXPERIMENTS
-  if (c->fused) {                   // LBM_FLAG_FUSED_ARITH
-    if (c->lane_cells == 1) {
-      if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_narrow_fused<true>, grid, block, 0, s, a);
-      else hipLaunchKernelGGL(lbm_step_kernel_narrow_fused<false>, grid, block, 0, s, a);
-    } else {
-      if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_fused<true>, grid, block, 0, s, a);
-      else hipLaunchKernelGGL(lbm_step_kernel_fused<false>, grid, block, 0, s, a);
-    }
-    return;
-  }
-#endif
-  if (c->lane_cells == 1) {
-    if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_narrow<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(lbm_step_kernel_narrow<false>, grid, block, 0, s, a);
-#if LBM_EXPERIMENTS
-  } else if (c->lds_kernel && a.quad_begin2 >= a.quad_end2) {
-    if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel_lds<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(lbm_step_kernel_lds<false>, grid, block, 0, s, a);
-#endif
-  } else {
-    if (c->nt_stores) hipLaunchKernelGGL(lbm_step_kernel<true>, grid, block, 0, s, a);
-    else hipLaunchKernelGGL(lbm_step_kernel<false>, grid, block, 0, s, a);
-  }
+  kStepKernels[c->lane_cells == 1][c->nt_stores][c->fused]<<<dim3(blocks + 1), dim3(kBlock), 0, s>>>(a);   // + the fold block
 }
 
 // Every instantiation of lbm_multi_kernel a context may launch, one row per (geometry, steps, terms, launch form) with what a launch
 // of it needs.  Rows of the tall geometry with K < 4 name the standard kernels (geom_for): no instantiation of their own.
-// The terms index of a row: the three forms of the sum|u| terms, then (index kMultiTermsFused, not in the experiment build) the fused arithmetic
+// The terms index of a row: the three forms of the sum|u| terms, then (index kMultiTermsFused) the fused arithmetic
 // with lbm_multi_kernel's default form of them: the instantiation <K, kTermsCompensated + kTermsFused, GEOM, PART>.
 struct MultiKernel { void (*fn)(MultiArgs); int lanes; size_t lds_bytes; };
 constexpr int kMultiTermsFused = 3;
-constexpr int kMultiTerms = LBM_EXPERIMENTS ? 3 : 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
+constexpr int kMultiTerms = 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
 static_assert(kTermsDouble == 0 && kTermsFloat == 1 && kTermsCompensated == 2 && kPartPlain == 0 && kPartTile == 3 && kGeomTall == 2, "the values index the table");
 constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
 template <int ROW>
@@ -321,17 +304,22 @@ template <size_t... ROW>
 constexpr std::array<MultiKernel, sizeof...(ROW)> multi_kernel_rows(std::index_sequence<ROW...>) { return {{multi_kernel_row<static_cast<int>(ROW)>()...}}; }
 constexpr auto kMultiKernels = multi_kernel_rows(std::make_index_sequence<kMultiGeoms * kMultiRowsPerGeom>{});
 
-// Frames above the default limit of dynamic LDS (the tall geometry: 79 KB) need the limit raised — per DEVICE (a function attribute
-// belongs to the device's copy of the code object): called from lbm_create on the context's device, not from the first launch of a process.
-hipError_t raise_multi_lds_limits_for(int geom)          // every instantiation a context of this geometry may launch (K = 3 tails of the tall one: standard)
+// Kernels whose dynamic LDS is above the default limit (lbm_multi_kernel's tall geometry: 79 KB; lbm_tile_kernel<16, 8>: 74 KB) need the limit
+// raised — per DEVICE (a function attribute belongs to the device's copy of the code object): called from lbm_create on the context's
+// device, not from the first launch of a process.  Rows [first, end) of a kernel table.
+template <typename Table>
+hipError_t raise_lds_limits(const Table& rows, int first, int end)
 {
-  for (int r = geom * kMultiRowsPerGeom; r < (geom + 1) * kMultiRowsPerGeom; ++r) {
-    const MultiKernel& k = kMultiKernels[r];
-    if (k.lds_bytes <= 65536) continue;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k.lds_bytes));
+  for (int r = first; r < end; ++r) {
+    if (rows[r].lds_bytes <= 65536) continue;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rows[r].fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(rows[r].lds_bytes));
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+hipError_t raise_multi_lds_limits_for(int geom)          // every instantiation a context of this geometry may launch (K = 3 tails of the tall one: standard)
+{
+  return raise_lds_limits(kMultiKernels, geom * kMultiRowsPerGeom, (geom + 1) * kMultiRowsPerGeom);
 }
 
 // Tiles of a launch that makes `k` steps on the owned rows and `ext` more rows on each side (ext > 0: a launch of a partitioned
@@ -391,65 +379,28 @@ void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int 
   k.fn<<<dim3(blocks + 1), dim3(k.lanes), k.lds_bytes, s>>>(a);
 }
 
-#if LBM_EXPERIMENTS
-// One launch of lbm_sweep_kernel: three steps of a whole periodic grid, strips of 64 columns swept upwards.
-template <int R, int MODE>
-void launch_sweep_r(lbm_ctx* c, bool accel_last, hipStream_t s)
+// Every instantiation of lbm_tile_kernel, one row per (geometry, FULL, terms) with what a launch of it needs.  The terms index of a
+// row: double-precision sum|u| terms, float ones (LBM_FLAG_FAST_AVVELS), the fused arithmetic (LBM_FLAG_FUSED_ARITH; never with the float terms: create_impl).
+struct TileKernel { void (*fn)(TileArgs); int block; size_t lds_bytes; };
+constexpr int kTileTermsFused = 2, kTileTerms = 3, kTileRows = 4 * 2 * kTileTerms;
+static_assert(kTermsDouble == 0 && kTermsFloat == 1, "the values index the table");
+constexpr int tile_row(int t, int h, bool full, int terms) { return (((t == 8 ? 2 : 0) + (h == 4 ? 1 : 0)) * 2 + (full ? 1 : 0)) * kTileTerms + terms; }
+template <int ROW>
+constexpr TileKernel tile_kernel_row()
 {
-  SweepArgs a{};
-  const float* src = c->grid[c->cur];
-  float* dst = c->grid[c->cur ^ 1];
-  for (int k = 0; k < 9; ++k) { a.srck[k] = src + k * c->ps; a.dstk[k] = dst + k * c->ps; }
-  a.ps = static_cast<uint32_t>(c->ps);
-  a.mask = c->mask; a.nx = c->p.nx; a.ny = c->nyl;
-  a.strips_x = c->p.nx / kSTX; a.nseg = c->sweep_nseg; a.seg_rows = c->sweep_seg_rows;
-  a.omega = c->p.omega; a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
-  a.accel_row = c->p.ny - 2; a.accel_last = accel_last ? 1 : 0;
-  a.partials_out = c->partials[c->parity];
-  a.prev_partials = c->partials[c->parity ^ 1];
-  a.n_prev = c->n_prev; a.n_prev_vecs = c->n_prev > 0 ? c->n_prev_vecs : 0;
-  a.sums = c->sums; a.counter = c->counter;
-  const int blocks = a.strips_x * a.nseg;
-  using G = SweepGeom<R, MODE>;
-  if (c->fast_avvels) lbm_sweep_kernel<R, true, MODE><<<dim3(blocks + 1), dim3(G::lanes), G::lds_bytes, s>>>(a);
-  else lbm_sweep_kernel<R, false, MODE><<<dim3(blocks + 1), dim3(G::lanes), G::lds_bytes, s>>>(a);
+  constexpr int TERMS = ROW % kTileTerms, H = ROW / (2 * kTileTerms) % 2 ? 4 : 8, T = ROW / (4 * kTileTerms) ? 8 : 16;
+  constexpr bool FULL = ROW / kTileTerms % 2 != 0;
+  static_assert(tile_row(T, H, FULL, TERMS) == ROW, "tile_row and its inverse");
+  return {&lbm_tile_kernel<T, H, FULL, TERMS == kTileTermsFused ? (kTermsDouble | kTermsFused) : TERMS>, TileGeom<T, H>::block, TileGeom<T, H>::lds_bytes};
 }
+template <size_t... ROW>
+constexpr std::array<TileKernel, sizeof...(ROW)> tile_kernel_rows(std::index_sequence<ROW...>) { return {{tile_kernel_row<static_cast<int>(ROW)>()...}}; }
+constexpr auto kTileKernels = tile_kernel_rows(std::make_index_sequence<kTileRows>{});
 
-template <int MODE>
-void launch_sweep_m(lbm_ctx* c, bool accel_last, hipStream_t s)
+void launch_tile(lbm_ctx* c, const TileArgs& a, hipStream_t s)
 {
-  if (c->sweep_R == 4) launch_sweep_r<4, MODE>(c, accel_last, s);      // (R = 3 was measured too: 488 us/step at 8192 x 8192; not kept)
-  else launch_sweep_r<5, MODE>(c, accel_last, s);
-}
-
-void launch_sweep(lbm_ctx* c, bool accel_last, hipStream_t s)
-{
-  if (c->sweep_mode == 0) launch_sweep_m<0>(c, accel_last, s);
-  else if (c->sweep_mode == 1) launch_sweep_m<1>(c, accel_last, s);
-  else launch_sweep_m<2>(c, accel_last, s);
-}
-
-#endif   // LBM_EXPERIMENTS
-
-template <int T, int H>
-void launch_tile(dim3 grid, hipStream_t s, const TileArgs& a, bool fast, bool fused)
-{
-  using G = TileGeom<T, H>;
-#if !LBM_EXPERIMENTS
-  if (fused) {                      // LBM_FLAG_FUSED_ARITH (never with `fast`: create_impl)
-    if (a.ksteps == H) lbm_tile_kernel_fused<T, H, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-    else lbm_tile_kernel_fused<T, H, false><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-    return;
-  }
-#endif
-  (void)fused;
-  if (fast) {
-    if (a.ksteps == H) lbm_tile_kernel<T, H, true, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-    else lbm_tile_kernel<T, H, false, true><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-  } else {
-    if (a.ksteps == H) lbm_tile_kernel<T, H, true, false><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-    else lbm_tile_kernel<T, H, false, false><<<grid, dim3(G::block), G::lds_bytes, s>>>(a);
-  }
+  const TileKernel& k = kTileKernels[tile_row(c->tile_T, c->tile_H, a.ksteps == c->tile_H, c->fused ? kTileTermsFused : c->fast_avvels ? kTermsFloat : kTermsDouble)];
+  k.fn<<<dim3(c->n_tiles + 1), dim3(k.block), k.lds_bytes, s>>>(a);   // + the fold block
 }
 
 // Profile mode of lbm_run (lbm_set_profile): a pooled timing event recorded on `s`; nullptr when off.
@@ -680,6 +631,28 @@ static void pack_obstacle_bits(std::vector<uint32_t>& bits, int rows, int nx, Ro
 // (lbm_create_global); >= 0: decided by the caller for the whole run (lbm_rank_layout).
 struct TileSpec { int px, py, rx, ry, x0, nxl, ghost_x, nx_global, ghost_rows; };    // lbm_create_tile: `p->nx` is then the storage row width nxl + 2 ghost_x
 
+// Launch geometry of a context that runs lbm_multi_kernel (K-step partitions and whole grids alike): the geometry by size, its tile width,
+// the raised LDS limit of its kernels, and room for the partials of its longest launch (no ghost rows where the rows wrap).
+static int setup_multi(lbm_ctx* c, bool tile_rank)
+{
+  const Knobs& knobs = c->knobs;
+  const int ny_local = c->nyl;
+  c->multi_geom = pick_geom(knobs, c->ncells);
+  if (tile_rank && c->ghost_rows == 0 && c->multi_geom == kGeomTall && knobs.multi_geom < 0) {
+    // A column block's launches all cover exactly its ny rows: where 23-row tiles fit them badly the last tile row is mostly waste — 256 rows: 12
+    // tile rows cover 276 (7.8 % over) against 260 on 13-row tiles; 128 rows: 138 against 130 — and the standard geometry wins by 10 % (us/step
+    // tall / standard: 4096 x 256 8.96 / 8.11, 8192 x 128 9.40 / 8.37; 512 and 1024 rows fit: 2048 x 512 7.82 / 8.25, 1024 x 1024 8.20 / 8.60, 2048 x 1024
+    // 13.8 / 14.1; profiles/r04/ab_column_block_geometry.txt).  Row blocks and whole grids compute different row counts from launch to launch (no rule).
+    auto over = [&](int ty) { return static_cast<double>((ny_local + ty - 1) / ty * ty) / ny_local; };
+    if (over(kMTY4Tall) - over(kMTY4) > 0.03) c->multi_geom = kGeomStd;
+  }
+  c->multi_tx = geom_tx(c->multi_geom);
+  HIP_TRY(raise_multi_lds_limits_for(c->multi_geom));
+  c->multi_tiles_x = (c->p.nx + c->multi_tx - 1) / c->multi_tx;
+  if (c->multi_K > 0) c->partials_cap = std::max(c->partials_cap, kMaxMultiSteps * c->multi_tiles_x * ((ny_local + 2 * c->ghost_rows + kMinMultiTY - 1) / kMinMultiTY) + 1);
+  return 0;
+}
+
 static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, int free_cells, const int* obstacles_rows,
                        const int* obstacles_global, const int* obstacles_window, int forced_k, int forced_ghost, int y0, int ny_local,
                        int device, unsigned flags, const TileSpec* tile = nullptr)
@@ -696,10 +669,6 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
       lbm_internal::set_error("lbm_create: LBM_FLAG_FUSED_ARITH cannot be combined with LBM_FLAG_FAST_AVVELS or LBM_FLAG_EXACT_AVVELS (the fused kernels carry each family's default sum|u| terms only)");
       return 1;
     }
-#if LBM_EXPERIMENTS
-    lbm_internal::set_error("lbm_create: LBM_FLAG_FUSED_ARITH is not built into the experiment library (-DLBM_EXPERIMENTS=1)");
-    return 1;
-#endif
   }
   const bool self_periodic = (ny_local == p->ny) && !(flags & LBM_FLAG_FORCE_HALO);
   const int accel_global = p->ny - 2;
@@ -765,15 +734,11 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
   // (128x128: 3.5 vs 4.4 us/step, 256x256: 4.1 vs 4.6, 512x512: 7.3 vs 6.2 -> cross-over at 64 K cells)
   const size_t narrow_max = static_cast<size_t>(knobs.narrow_max);
   c->lane_cells = (p->nx % kCellsPerLane != 0 || c->ncells <= narrow_max) ? 1 : kCellsPerLane;
-#if LBM_EXPERIMENTS
-  c->lds_kernel = (flags & LBM_FLAG_KERNEL_LDS) != 0 && c->lane_cells == kCellsPerLane;
-#else
   if (flags & LBM_FLAG_KERNEL_LDS) {
-    lbm_internal::set_error("lbm_create: LBM_FLAG_KERNEL_LDS needs a library built with -DLBM_EXPERIMENTS=1 (the LDS-staged one-step kernel is never faster and is not shipped)");
+    lbm_internal::set_error("lbm_create: LBM_FLAG_KERNEL_LDS is retired (the LDS-staged one-step kernel was never faster and is no longer built)");
     delete c;
     return 1;
   }
-#endif
   // hipGraph replay of 64-step blocks is opt-in: measured on MI355X it changes nothing (128x128:
   // 4.47 vs 4.33 us/step) because even the smallest grids are bound by the device-side kernel
   // boundary + kernel latency, not by the host's launch rate
@@ -858,19 +823,7 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
       for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack_x[i], sizeof(float) * pack_floats_x));
     }
     c->tile_kernel = false;
-    c->multi_geom = pick_geom(knobs, c->ncells);
-    if (tile && c->ghost_rows == 0 && c->multi_geom == kGeomTall && knobs.multi_geom < 0) {
-      // A column block's launches all cover exactly its ny rows: where 23-row tiles fit them badly the last tile row is mostly waste — 256 rows: 12
-      // tile rows cover 276 (7.8 % over) against 260 on 13-row tiles; 128 rows: 138 against 130 — and the standard geometry wins by 10 % (us/step
-      // tall / standard: 4096 x 256 8.96 / 8.11, 8192 x 128 9.40 / 8.37; 512 and 1024 rows fit: 2048 x 512 7.82 / 8.25, 1024 x 1024 8.20 / 8.60, 2048 x 1024
-      // 13.8 / 14.1; profiles/r04/ab_column_block_geometry.txt).  Row blocks and whole grids compute different row counts from launch to launch (no rule).
-      auto over = [&](int ty) { return static_cast<double>((ny_local + ty - 1) / ty * ty) / ny_local; };
-      if (over(kMTY4Tall) - over(kMTY4) > 0.03) c->multi_geom = kGeomStd;
-    }
-    c->multi_tx = geom_tx(c->multi_geom);
-    HIP_TRY_C(raise_multi_lds_limits_for(c->multi_geom));
-    c->multi_tiles_x = (p->nx + c->multi_tx - 1) / c->multi_tx;
-    c->partials_cap = std::max(c->partials_cap, kMaxMultiSteps * c->multi_tiles_x * ((ny_local + 2 * c->ghost_rows + kMinMultiTY - 1) / kMinMultiTY) + 1);
+    if (setup_multi(c, tile != nullptr)) return fail();
   } else if (!c->tile_kernel && self_periodic && fits_u32 && p->nx < (1 << 23) &&      // (24-bit row multiplies in lbm_multi_kernel)
              ((p->nx % kMTX == 0 && ny_local % kMTY == 0) || (p->nx % 2 == 0 && p->nx >= 2 * kMTX && ny_local >= 2 * kMTY))) {
     // grids tiled exactly by 64x16, or any even nx >= 128 with ny >= 32, where the last tile column / row
@@ -883,43 +836,11 @@ static int create_impl(lbm_ctx** out, const Knobs& knobs, const lbm_params* p, i
     // 1536x1536 14.2 / 13.8, 1024x1024 8.16 / 7.07, 768x768 5.39 / 4.63, 1024x512 4.51 / 4.72, 512x1024 4.39 / 4.62, 640x640 4.01 / 4.13,
     // 512x512 3.11 / 3.45 -> K = 4 from 768 x 768 cells up (profiles/r03/ab_k3_k4.txt, ab_k3_k4_threshold.txt)
     c->multi_K = std::min(std::max(knob_or(knobs.multi_k, c->ncells >= size_t(768) * 768 ? 4 : 3), 0), kMaxMultiSteps);
-    c->multi_geom = pick_geom(knobs, c->ncells);
-    c->multi_tx = geom_tx(c->multi_geom);
-    HIP_TRY_C(raise_multi_lds_limits_for(c->multi_geom));
-    c->multi_tiles_x = (p->nx + c->multi_tx - 1) / c->multi_tx;
-    if (c->multi_K > 0) c->partials_cap = std::max(c->partials_cap, kMaxMultiSteps * c->multi_tiles_x * ((ny_local + kMinMultiTY - 1) / kMinMultiTY) + 1);
-#if LBM_EXPERIMENTS
-    // streaming form of the 3-step launch (kernels/sweep.h): strips of 64 columns, segments of rows so that the launch is
-    // about one round of two blocks per CU (8192 x 8192: 128 strips x 4 segments of 2048 rows = 512 blocks).
-    // LBM_TUNE_SWEEP = R (rows per tick: 4 or 5); 0 = off (the default: measured 10-20 % slower than lbm_multi_kernel<3>)
-    const int want = knobs.sweep;
-    if (want > 0 && c->multi_K >= 3 && p->nx % kSTX == 0 && ny_local >= 64) {
-      c->multi_K = 3;                                        // the sweep makes 3-step launches; tails are lbm_multi_kernel's
-      const int strips = p->nx / kSTX;
-      c->sweep_mode = std::min(std::max(knobs.sweep_mode, 0), 2);
-      const int target_blocks = knob_or(knobs.sweep_blocks, c->sweep_mode == 0 ? 512 : 768);
-      int nseg = std::max(1, (target_blocks + strips / 2) / strips);
-      int seg_rows = (ny_local + nseg - 1) / nseg;
-      seg_rows = std::max(seg_rows, 32);
-      nseg = (ny_local + seg_rows - 1) / seg_rows;
-      c->sweep_R = want == 4 ? 4 : 5;
-      c->sweep_nseg = nseg; c->sweep_seg_rows = seg_rows;
-      c->partials_cap = std::max(c->partials_cap, 3 * strips * nseg + 1);
-    }
-#endif   // LBM_EXPERIMENTS
+    if (setup_multi(c, false)) return fail();
   } else if (c->tile_kernel) {
     c->partials_cap = std::max(c->partials_cap, kMaxTileSteps * c->n_tiles + 1);
     // up to 74 KB of dynamic LDS per block (two 9 x R x R float buffers): above the 64 KB default limit
-    {
-      using G168 = TileGeom<16, 8>;
-      const void* big[4] = {reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, true, false>), reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, false, false>),
-                            reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, true, true>), reinterpret_cast<const void*>(&lbm_tile_kernel<16, 8, false, true>)};
-      for (const void* k : big) HIP_TRY_C(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G168::lds_bytes)));
-#if !LBM_EXPERIMENTS
-      const void* big_fused[2] = {reinterpret_cast<const void*>(&lbm_tile_kernel_fused<16, 8, true>), reinterpret_cast<const void*>(&lbm_tile_kernel_fused<16, 8, false>)};
-      for (const void* k : big_fused) HIP_TRY_C(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(G168::lds_bytes)));
-#endif
-    }
+    HIP_TRY_C(raise_lds_limits(kTileKernels, 0, kTileRows));
   }
   for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * c->partials_cap));
   HIP_TRY_C(hipMalloc(&c->fold_scratch, sizeof(double) * kFoldSlices * 8));
@@ -1152,26 +1073,17 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
   c->prof_launches.clear();
   if (begin_run(c, n_steps, s)) return 1;
   int tile_launches = 0;
-  const bool multi = c->multi_K > 0 && c->self_periodic;
-  for (int t = 0; multi && t < n_steps;) {
+  const KernelFamily family = family_of(c);
+  for (int t = 0; family == kFamilyMulti && t < n_steps;) {
     // up to multi_K steps per pass over HBM (lbm_multi_kernel).  A step count that 3 does not divide is split into 3s
     // and 4s where that avoids the K = 2 / K = 1 launch at the end (8192 x 8192, us per launch: K = 1 870, K = 2 1000,
     // K = 3 1050, K = 4 1460): n = 3a + 4 for n mod 3 = 1, n = 3a + 8 for n mod 3 = 2 (next_multi_k; row partitions
     // with four ghost rows split the same way).
     const int k = next_multi_k(c, n_steps - t);
     hipEvent_t pb = prof_stamp(c, s);
-#if LBM_EXPERIMENTS
-    const bool sweep = c->sweep_R > 0 && k == 3;
-    if (sweep) launch_sweep(c, /*accel_last=*/t + k < n_steps, s);
-    else
-#endif
     launch_multi(c, k, 0, /*accel_last=*/t + k < n_steps, 0, multi_tiles_for(c, k), 0, 0, /*fold=*/true, s);
     if (c->profile) c->prof_launches.push_back({k, pb, prof_stamp(c, s)});
-#if LBM_EXPERIMENTS
-    c->n_prev = sweep ? (c->p.nx / kSTX) * c->sweep_nseg : multi_tiles_for(c, k);
-#else
     c->n_prev = multi_tiles_for(c, k);
-#endif
     c->n_prev_vecs = k;
     c->parity ^= 1;
     c->cur ^= 1;
@@ -1179,7 +1091,7 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
     ++tile_launches;
     if (t >= n_steps) c->ev_tile_launches = tile_launches;
   }
-  for (int t = 0; !multi && c->tile_kernel && t < n_steps;) {
+  for (int t = 0; family == kFamilyTile && t < n_steps;) {
     // up to tile_H steps per launch (lbm_tile_kernel); every launch of such a run has this form
     const int k = std::min(c->tile_H, n_steps - t);
     TileArgs a{};
@@ -1195,10 +1107,7 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
     a.sums = c->sums; a.counter = c->counter;
     const dim3 grid(c->n_tiles + 1);
     hipEvent_t pb = prof_stamp(c, s);
-    if (c->tile_T == 16 && c->tile_H == 8) launch_tile<16, 8>(grid, s, a, c->fast_avvels, c->fused);
-    else if (c->tile_T == 16) launch_tile<16, 4>(grid, s, a, c->fast_avvels, c->fused);
-    else if (c->tile_H == 8) launch_tile<8, 8>(grid, s, a, c->fast_avvels, c->fused);
-    else launch_tile<8, 4>(grid, s, a, c->fast_avvels, c->fused);
+    launch_tile(c, a, s);
     if (c->profile) c->prof_launches.push_back({k, pb, prof_stamp(c, s)});
     ++tile_launches;
     c->n_prev = c->n_tiles; c->n_prev_vecs = k;
@@ -1207,7 +1116,7 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
     t += k;
     if (t >= n_steps) c->ev_tile_launches = tile_launches;
   }
-  for (int t = 0; !multi && !c->tile_kernel && t < n_steps;) {
+  for (int t = 0; family == kFamilyStep && t < n_steps;) {
     // launch-bound grids: replay a captured block of kGraphSteps steps while at least one more
     // step follows it (the last step of a run is launched directly: it must not accelerate)
     if (c->use_graph && c->n_prev > 0 && n_steps - t > kGraphSteps) {
@@ -1223,7 +1132,7 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev_end, s));
-  c->ev_launches = (multi || c->tile_kernel) ? c->ev_tile_launches : n_steps;
+  c->ev_launches = family != kFamilyStep ? c->ev_tile_launches : n_steps;
   c->ev_valid = true;
   if (fold_last(c, s, /*final=*/true)) return 1;
   c->run_done = n_steps;
@@ -1835,21 +1744,18 @@ int lbm_describe(const lbm_ctx* c, char* kernel_name, size_t len, long long* cel
 {
   if (!c) { lbm_internal::set_error("lbm_describe: null context"); return 1; }
   if (kernel_name && len) {
-#if LBM_EXPERIMENTS
-    if (c->sweep_R > 0 && c->self_periodic) std::snprintf(kernel_name, len, c->fast_avvels ? "lbm_sweep_kernel<%d, fast av_vels>" : "lbm_sweep_kernel<%d>", c->sweep_R);
-    else if (c->lds_kernel && !(c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) && !(c->tile_kernel && c->self_periodic) && c->lane_cells != 1)
-      std::snprintf(kernel_name, len, "lbm_step_kernel_lds<%s>", c->nt_stores ? "true" : "false");
-    else
-#endif
-    if (c->fused) {                 // LBM_FLAG_FUSED_ARITH, named as a profiler prints them: lbm_multi_kernel<K, 6, GEOM, PART> (6 = kTermsCompensated + kTermsFused), lbm_tile_kernel_fused, lbm_step_kernel*_fused
-      if (c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) std::snprintf(kernel_name, len, "lbm_multi_kernel<%d, 6> (fused arithmetic)", c->multi_K);
-      else if (c->tile_kernel && c->self_periodic) std::snprintf(kernel_name, len, "lbm_tile_kernel_fused<%d, %d>", c->tile_T, c->tile_H);
-      else std::snprintf(kernel_name, len, c->lane_cells == 1 ? "lbm_step_kernel_narrow_fused<%s>" : "lbm_step_kernel_fused<%s>", c->nt_stores ? "true" : "false");
-    } else
-    if (c->multi_K > 0 && (c->self_periodic || c->ghost > 0)) std::snprintf(kernel_name, len, c->multi_terms == kTermsFloat ? "lbm_multi_kernel<%d, fast av_vels>" : c->multi_terms == kTermsDouble ? "lbm_multi_kernel<%d, double-precision av_vels terms>" : "lbm_multi_kernel<%d>", c->multi_K);
-    else if (c->tile_kernel && c->self_periodic) std::snprintf(kernel_name, len, c->fast_avvels ? "lbm_tile_kernel<%d, %d, fast av_vels>" : "lbm_tile_kernel<%d, %d>", c->tile_T, c->tile_H);
-    else if (c->lane_cells == 1) std::snprintf(kernel_name, len, "lbm_step_kernel_narrow<%s>", c->nt_stores ? "true" : "false");
-    else std::snprintf(kernel_name, len, "lbm_step_kernel<%s>", c->nt_stores ? "true" : "false");
+    // the library's names for the families (a profiler prints the instantiations: lbm_multi_kernel<K, 6, GEOM, PART> with 6 = kTermsCompensated + kTermsFused,
+    // lbm_tile_kernel<T, H, FULL, TERMS>, lbm_step_kernel<CELLS, NT, FUSED>)
+    const KernelFamily family = family_of(c);
+    const char* nt = c->nt_stores ? "true" : "false";
+    if (c->fused) {                 // LBM_FLAG_FUSED_ARITH
+      if (family == kFamilyMulti) std::snprintf(kernel_name, len, "lbm_multi_kernel<%d, 6> (fused arithmetic)", c->multi_K);
+      else if (family == kFamilyTile) std::snprintf(kernel_name, len, "lbm_tile_kernel_fused<%d, %d>", c->tile_T, c->tile_H);
+      else std::snprintf(kernel_name, len, c->lane_cells == 1 ? "lbm_step_kernel_narrow_fused<%s>" : "lbm_step_kernel_fused<%s>", nt);
+    }
+    else if (family == kFamilyMulti) std::snprintf(kernel_name, len, c->multi_terms == kTermsFloat ? "lbm_multi_kernel<%d, fast av_vels>" : c->multi_terms == kTermsDouble ? "lbm_multi_kernel<%d, double-precision av_vels terms>" : "lbm_multi_kernel<%d>", c->multi_K);
+    else if (family == kFamilyTile) std::snprintf(kernel_name, len, c->fast_avvels ? "lbm_tile_kernel<%d, %d, fast av_vels>" : "lbm_tile_kernel<%d, %d>", c->tile_T, c->tile_H);
+    else std::snprintf(kernel_name, len, c->lane_cells == 1 ? "lbm_step_kernel_narrow<%s>" : "lbm_step_kernel<%s>", nt);
   }
   if (cells_per_launch) *cells_per_launch = static_cast<long long>(c->ncells);
   if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->ncells * sizeof(float) + c->ncells / 8);

@@ -39,9 +39,6 @@ inline int knob_or(int v, int fallback) { return v == kKnobUnset ? fallback : v;
   X(LBM_TUNE_TERMS,             terms,             -1,         std::atoi)                   \
   X(LBM_TUNE_FOLD_SLICED_MIN,   fold_sliced_min,   1024,       std::atoi)                   \
   X(LBM_TUNE_OBS_CHUNK_CELLS,   obs_chunk_cells,   16 << 20,   std::atoi)                   \
-  X(LBM_TUNE_SWEEP,             sweep,             0,          std::atoi)                   \
-  X(LBM_TUNE_SWEEP_MODE,        sweep_mode,        2,          std::atoi)                   \
-  X(LBM_TUNE_SWEEP_BLOCKS,      sweep_blocks,      kKnobUnset, std::atoi)                   \
   X(LBM_DEBUG_ADDR,             debug_addr,        0,          std::atoi)                   \
   /* the layout rule: contexts, and every call of the layout functions */                  \
   X(LBM_TUNE_MACRO_K,           macro_k,           4,          std::atoi)                   \

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build the CURRENT source tree's liblbm_d2q9.so as lib/variants/<name>.so (for scripts/ab_libs.py).
-# Usage: bash scripts/build_variant.sh <name> [extra hipcc flags, e.g. -DLBM_EXPERIMENT=1]
+# Usage: bash scripts/build_variant.sh <name> [extra hipcc flags, e.g. -DLBM_TILE_STAMPS=1]
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; shift

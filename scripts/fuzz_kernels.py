@@ -100,7 +100,7 @@ def run_partitions(p, obst, size, steps, kstep):
 
 
 KNOBS = ["LBM_TUNE_MULTI_K", "LBM_TUNE_TILE_MAX", "LBM_TUNE_TILE_GEOM", "LBM_TUNE_MACRO_K", "LBM_TUNE_NARROW_MAX", "LBM_TUNE_MULTI_TILE",
-         "LBM_TUNE_TILE_SINGLE_MAX", "LBM_P2P_SCHEDULE", "LBM_TUNE_MACRO_GHOST", "LBM_TUNE_MACRO_GROUP", "LBM_TUNE_TILE_GHOST_ROWS", "LBM_TUNE_SWEEP", "LBM_TUNE_SWEEP_MODE", "LBM_TUNE_SWEEP_BLOCKS"]
+         "LBM_TUNE_TILE_SINGLE_MAX", "LBM_P2P_SCHEDULE", "LBM_TUNE_MACRO_GHOST", "LBM_TUNE_MACRO_GROUP", "LBM_TUNE_TILE_GHOST_ROWS"]
 
 
 def main(argv=None) -> int:
@@ -120,9 +120,6 @@ def main(argv=None) -> int:
             os.environ.pop(k, None)
             if v is not None:
                 os.environ[k] = v
-
-
-EXPERIMENTS = os.environ.get("LBM_LIBRARY", "").endswith("experiments.so")
 
 
 def tiles_case(c) -> int:
@@ -159,17 +156,13 @@ def fuzz(a) -> int:
     rng = np.random.default_rng(a.seed)
     bad = 0
     for case in range(a.cases):
-        kind = rng.choice(["multi", "tile", "ring", "parts", "parts1", "forms", "sweep", "tiles"])
-        if kind == "sweep" and not EXPERIMENTS:      # lbm_sweep_kernel lives in the experiment build only (LBM_LIBRARY=.../lib/variants/experiments.so)
-            kind = "parts"
+        kind = rng.choice(["multi", "tile", "ring", "parts", "parts1", "forms", "parts", "tiles"])      # (weights: "parts" twice, "vector" twice below)
         flags_fast = 0
         if kind == "forms":
-            # the one-step kernels among themselves: one cell per lane / four cells per lane / LDS-staged, with and
+            # the one-step kernels among themselves: one cell per lane / four cells per lane, with and
             # without non-temporal stores, any nx (odd too) and ny >= 3
             nx, ny = int(rng.integers(1, 300)), int(rng.integers(3, 120))
-            form = rng.choice(["narrow", "vector", "lds", "nt", "no_nt"])
-            if form == "lds" and not EXPERIMENTS:    # (the LDS-staged one-step kernel too)
-                form = "vector"
+            form = rng.choice(["narrow", "vector", "vector", "nt", "no_nt"])
             env = {"LBM_TUNE_TILE_MAX": "0", "LBM_TUNE_MULTI_K": "0"}
             if form == "narrow":
                 env["LBM_TUNE_NARROW_MAX"] = str(1 << 30)
@@ -177,12 +170,7 @@ def fuzz(a) -> int:
                 env["LBM_TUNE_NARROW_MAX"] = "0"
             else:
                 env["LBM_TUNE_NARROW_MAX"] = "0"
-                flags_fast = {"lds": lbm._capi.FLAG_KERNEL_LDS, "nt": lbm._capi.FLAG_NT_STORES, "no_nt": lbm._capi.FLAG_NO_NT_STORES}[form]
-        elif kind == "sweep":
-            # lbm_sweep_kernel<R> in its three storage modes: strips of 64 columns, any ny >= 64, any number of segments
-            nx, ny = 64 * int(rng.integers(1, 9 * a.scale)), int(rng.integers(64, 300 * a.scale))
-            env = {"LBM_TUNE_TILE_MAX": "0", "LBM_TUNE_SWEEP": str(rng.choice([4, 5])), "LBM_TUNE_SWEEP_MODE": str(rng.choice([0, 1, 2])),
-                   "LBM_TUNE_SWEEP_BLOCKS": str(int(rng.integers(1, 40)))}
+                flags_fast = {"nt": lbm._capi.FLAG_NT_STORES, "no_nt": lbm._capi.FLAG_NO_NT_STORES}[form]
         elif kind == "tile":
             T = int(rng.choice([8, 16]))
             nx, ny = T * int(rng.integers(1, 20)), T * int(rng.integers(1, 20))

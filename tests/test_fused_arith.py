@@ -89,6 +89,72 @@ def test_every_kernel_family_gives_the_restatement_bits(lbm, oracle, digests, ca
     part.close()
 
 
+# ---- every row of the library's kernel tables that no case above launches --------------------------------------------------------
+# lbm_tile_kernel: one row per (geometry, full-H launch or shorter, form of the terms).  A 32 x 32 grid is the smallest that all four
+# geometries tile into more than one block; geometry 88 is the default of the 128 x 128 cases.  Runs of 11 then 5 steps: launches of
+# 8 + 3, then 5 steps at H = 8 and of 4 + 4 + 3, then 4 + 1 at H = 4 — a full-H launch and a shorter one each.
+TILE_GEOMS = ["168", "164", "84"]
+AV_EXACT_RTOL = 1e-6      # av_vels against the oracle's exact per-step sums, as tests/test_gpu_parity.py holds LBM_FLAG_FAST_AVVELS to
+
+
+@pytest.fixture(scope="module")
+def tile_deck(lbm, oracle):
+    """The 32 x 32 deck with both references for 16 steps, computed once: (p, obst, fused_ref's (cells, sums), the oracle's (cells, exact av_vels))."""
+    p, obst = synthetic(lbm, 32, 32, 16, block_accel_row=True)
+    ref_cells, _, ref_exact = oracle.run(p, obst, 16)
+    return p, obst, fused_ref.run(p, obst, 16, mode="fused"), (ref_cells, ref_exact)
+
+
+@pytest.mark.parametrize("geom", TILE_GEOMS)
+def test_tile_geometries_with_the_fused_arithmetic(lbm, tile_deck, monkeypatch, geom):
+    monkeypatch.setenv("LBM_TUNE_TILE_GEOM", geom)     # T*10 + H: owned tile edge, ghost ring / steps per launch
+    p, obst, ref, _ = tile_deck
+    part = fused_context(lbm, p, obst)
+    assert part.describe()["kernel"] == f"lbm_tile_kernel_fused<{int(geom) // 10}, {int(geom) % 10}>"
+    assert_equals_restatement(part, p, obst, [11, 5], ref=ref)
+    part.close()
+
+
+@pytest.mark.parametrize("geom", TILE_GEOMS)
+def test_tile_geometries_with_float_av_vels_terms(lbm, tile_deck, monkeypatch, geom):
+    """LBM_FLAG_FAST_AVVELS on the same grid and geometries: the exact arithmetic's populations bit for bit, av_vels to 1e-6."""
+    monkeypatch.setenv("LBM_TUNE_TILE_GEOM", geom)
+    p, obst, _, (ref_cells, ref_exact) = tile_deck
+    sim = lbm.Simulation(p, obst, flags=lbm._capi.FLAG_FAST_AVVELS)
+    assert sim.partition.describe()["kernel"] == f"lbm_tile_kernel<{int(geom) // 10}, {int(geom) % 10}, fast av_vels>"
+    av = np.concatenate([sim.run(11), sim.run(5)])
+    cells = sim.local_cells()
+    sim.close()
+    rel = float(np.max(np.abs(av - ref_exact) / ref_exact))
+    differing = int(np.count_nonzero(bits(cells) != bits(ref_cells)))
+    print(f"geometry {geom}: {differing} differing population words, av_vels off by {rel:.3e}")
+    assert differing == 0
+    assert rel < AV_EXACT_RTOL
+
+
+# The one-step kernels with non-temporal stores (LBM_FLAG_NT_STORES; by default only grids beyond the Infinity Cache take them): one
+# cell per lane at 126 x 40, four at 100 x 700, in both arithmetics.
+NT_SHAPES = [("narrow", 126, 40, "lbm_step_kernel_narrow"), ("quad", 100, 700, "lbm_step_kernel")]
+
+
+@pytest.mark.parametrize("shape", NT_SHAPES, ids=[s[0] for s in NT_SHAPES])
+def test_non_temporal_one_step_kernels_in_both_arithmetics(lbm, oracle, shape):
+    _, nx, ny, family = shape
+    p, obst = synthetic(lbm, nx, ny, 5, block_accel_row=True)
+    exact = lbm.Partition(p, lbm.count_free_cells(obst), obst, flags=lbm._capi.FLAG_NT_STORES)
+    assert exact.describe()["kernel"] == f"{family}<true>"
+    exact.run(5)
+    ref_cells, _, _ = oracle.run(p, obst, 5)
+    differing = int(np.count_nonzero(bits(exact.get_cells()) != bits(ref_cells)))
+    print(f"{family}<true>: {differing} population words differ from the oracle's")
+    assert differing == 0
+    exact.close()
+    fused = fused_context(lbm, p, obst, flags=lbm._capi.FLAG_NT_STORES)
+    assert fused.describe()["kernel"] == f"{family}_fused<true>"
+    assert_equals_restatement(fused, p, obst, [5])
+    fused.close()
+
+
 def test_set_cells_of_a_random_state_then_four_fused_steps(lbm):
     rng = np.random.default_rng(11)
     p, obst = synthetic(lbm, 256, 128, 4, seed=9, block_accel_row=True)
