@@ -12,7 +12,7 @@ import os as _os
 # initialises (harmless elsewhere).  Respect a value the caller has chosen.
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
-from . import _capi, checker, decks  # noqa: E402
+from . import _capi, checker, decks, f64  # noqa: E402
 from ._capi import EXPORTS, LIB_PATH, LIB_RCCL_PATH, P2P_EXPORTS, RCCL_EXPORTS, LbmError, load_library, load_rccl_library
 from .build import CLI as CLI_PATH
 from .build import build
@@ -25,5 +25,5 @@ __all__ = [
     "EXPORTS", "RCCL_EXPORTS", "P2P_EXPORTS", "P2PRing", "av_velocity_obs", "obstacle_window", "plan_groups", "plan_steps", "rank_layout", "tile_layout", "tile_neighbours", "choose_rank_grid", "write_final_state_obs", "LIB_PATH", "LIB_RCCL_PATH", "load_rccl_library", "CLI_PATH", "LbmError", "load_library", "build", "Params", "synthetic_obstacles",
     "write_obstacles", "write_synthetic_deck", "NORTH", "SOUTH", "HaloExchange", "Partition", "RcclRing", "Simulation",
     "av_velocity_host", "count_free_cells", "decompose", "read_obstacles", "read_params", "reynolds",
-    "run_partitioned", "write_av_vels", "write_final_state", "checker", "decks",
+    "run_partitioned", "write_av_vels", "write_final_state", "checker", "decks", "f64",
 ]

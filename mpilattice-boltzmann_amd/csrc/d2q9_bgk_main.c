@@ -13,6 +13,10 @@
  * LBM_FLAGS=256, LBM_FLAG_FUSED_ARITH, selects the fused arithmetic of the cell update: final_state.dat and av_vels.dat then differ
  * from the reference's in the last digits — 2e-4 / 4e-4 relative at most on the 128x128 deck — and `make check` still passes).
  *
+ * LBM_PRECISION=double runs the double-precision mode (include/lbm_d2q9_f64.h): the reference's arithmetic with every float object a double,
+ * which is what the reference's shipped results and README were produced with; the same five lines and two files.  One GPU only
+ * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES) and has no other default.
+ *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
  * the reference's rule (d2q9-bgk.c:834-862), rank r lives on device LBM_DEVICES[r] (a comma list; default r), one host
  * thread per rank drives its device, and the halos travel as direct peer-to-peer stores over xGMI
@@ -31,6 +35,7 @@
 #include <sys/time.h>
 
 #include "lbm_d2q9.h"
+#include "lbm_d2q9_f64.h"
 #include "lbm_d2q9_p2p.h"
 
 static void die(const char* message, const int line, const char* file)   /* d2q9-bgk.c:1145-1151 */
@@ -86,6 +91,57 @@ static void* rank_main(void* arg)
   return NULL;
 }
 
+/* LBM_PRECISION=double: main() below with lbm64_* in place of lbm_* and doubles in place of floats. */
+static int main_double(char* argv[])
+{
+  lbm64_params params;
+  lbm64_ctx* ctx = NULL;
+  int* obstacles;
+  int free_cells = 0;
+  double* av_vels;
+  double* obs;                   /* u_x, u_y, u, pressure per cell of the whole grid */
+  double tic, toc, usrtim, systim, mlups, av;
+  struct rusage ru;
+  size_t nx;
+
+  if (env_int("LBM_GPUS", 1) > 1) die("LBM_PRECISION=double: double precision runs on one GPU (unset LBM_GPUS)", __LINE__, __FILE__);
+  if (lbm64_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);
+  if (params.nx <= 0 || params.ny <= 0 || params.max_iters < 0) die("could not read param file: nx", __LINE__, __FILE__);
+  nx = (size_t)params.nx;
+  obstacles = (int*)xmalloc(sizeof(int) * nx * (size_t)params.ny);
+  if (lbm_read_obstacles(argv[2], params.nx, params.ny, obstacles, &free_cells)) die(lbm_last_error(), __LINE__, __FILE__);
+  av_vels = (double*)xmalloc(sizeof(double) * ((size_t)params.max_iters + 1));
+  obs = (double*)xmalloc(sizeof(double) * nx * (size_t)params.ny * 4);
+
+  if (lbm64_create(&ctx, &params, free_cells, obstacles, env_int("LBM_DEVICE", 0), (unsigned)env_int("LBM_FLAGS", 0)))
+    die(lbm_last_error(), __LINE__, __FILE__);
+  tic = wall_seconds();                                                    /* :278-279 */
+  if (lbm64_run(ctx, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
+  toc = wall_seconds();                                                    /* :397-398 */
+  if (lbm64_get_observables(ctx, obs)) die(lbm_last_error(), __LINE__, __FILE__);
+  lbm64_destroy(ctx);
+  getrusage(RUSAGE_SELF, &ru);                                             /* :399-403 */
+  usrtim = ru.ru_utime.tv_sec + ru.ru_utime.tv_usec / 1000000.0;
+  systim = ru.ru_stime.tv_sec + ru.ru_stime.tv_usec / 1000000.0;
+
+  av = lbm64_av_velocity_obs(&params, obs, obstacles, params.ny) * (1.0 / free_cells);   /* :753, :950 */
+  printf("==done==\n");                                                    /* :411-415 */
+  printf("Reynolds number:\t\t%.12E\n", lbm64_reynolds(&params, av));
+  printf("Elapsed time:\t\t\t%.6lf (s)\n", toc - tic);
+  printf("Elapsed user CPU time:\t\t%.6lf (s)\n", usrtim);
+  printf("Elapsed system CPU time:\t%.6lf (s)\n", systim);
+  mlups = (double)params.nx * params.ny * params.max_iters / (toc - tic) / 1e6;
+  printf("MLUPS:\t\t\t\t%.1f (1 GPU, double precision)\n", mlups);
+  printf("HBM roofline (144 B/cell-step @ 8.0 TB/s = 55556 MLUPS per GPU):\t%.1f %%\n", 100.0 * mlups / (8.0e12 / 144.0 / 1e6));
+
+  if (!env_int("LBM_NO_OUTPUT", 0)) {                                      /* :419-421 */
+    if (lbm64_write_final_state_obs("final_state.dat", &params, obs, obstacles, params.ny, 0, 0)) die(lbm_last_error(), __LINE__, __FILE__);
+    if (lbm64_write_av_vels("av_vels.dat", av_vels, params.max_iters)) die(lbm_last_error(), __LINE__, __FILE__);
+  }
+  free(obs); free(av_vels); free(obstacles);
+  return EXIT_SUCCESS;                                                     /* :439 */
+}
+
 int main(int argc, char* argv[])
 {
   lbm_params params;
@@ -101,6 +157,11 @@ int main(int argc, char* argv[])
   size_t nx;
 
   if (argc != 3) usage(argv[0]);                                          /* :197-200 */
+  {
+    const char* precision = getenv("LBM_PRECISION");
+    if (precision && strcmp(precision, "double") == 0) return main_double(argv);
+    if (precision && *precision && strcmp(precision, "float") != 0) die("LBM_PRECISION: expected float or double", __LINE__, __FILE__);
+  }
 
   if (lbm_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);
   if (params.nx <= 0 || params.ny <= 0 || params.max_iters < 0) die("could not read param file: nx", __LINE__, __FILE__);

@@ -1,0 +1,383 @@
+// lbm_f64.hip — the double-precision mode of liblbm_d2q9.so: the device entry points of include/lbm_d2q9_f64.h and, through
+// kernels/step64.h, its gfx950 kernels.  A translation unit of its own: the float path's code objects (lbm_kernels.hip) do not
+// change with it.  The host-only half (parser, end-of-run reductions, writers) is in lbm_host.cpp.
+//
+// What one step does is what lbm_kernels.hip's header lists, with every float object a double (the contract: lbm_d2q9_f64.h):
+// pull-stream, moments + equilibrium, BGK relaxation / bounce-back, the sum|u| terms into per-block partials, accelerate_flow as an
+// epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  One kernel, lbm_step_kernel_f64<CELLS, NT>,
+// one step per launch: whole periodic grids on one GPU only (no partitions, no several steps per launch, no fused arithmetic, no
+// hipGraph, no state digest).
+//
+// Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (plane_stride_doubles), two grids
+// swapped per launch, the obstacle map as the float path's bitfield.  Compiled with -ffp-contract=off like the rest of the library:
+// the post-step populations are the bits gcc -std=c99 gives the same statements (tests/f64_ref.c).
+//
+// gfx950 only: 64-wide wavefronts (block_sum).
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+#include "lbm_d2q9_f64.h"
+#include "lbm_internal.h"
+#include "lbm_knobs.h"
+#include "kernels/step64.h"
+
+namespace {
+
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
+      return 1;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+// Plane stride in doubles — the float path's plane_stride_floats rule (lbm_kernels.hip), this unit's own copy of it, in elements:
+// ny*nx + guard for the shifted loads at both ends, rounded to 64 elements (512 B), an odd number of such units, then skewed by `skew`
+// units for large grids so that the 9 planes (and the two grids) do not all start on the same HBM channel when ny*nx is a large
+// power of two.  Always even: the pair form's aligned 16-byte accesses.
+size_t plane_stride_doubles(size_t ncells, int skew)
+{
+  size_t s = (ncells + 64 + 63) / 64 * 64;
+  if ((s / 64) % 2 == 0) s += 64;
+  if (ncells >= (1u << 20)) s += 64 * static_cast<size_t>(skew);
+  return s;
+}
+
+// the float path's rule (pick_iters, lbm_kernels.hip): at most max_blocks work blocks (LBM_TUNE_MAXBLOCKS, 16384), each with a
+// power-of-two number of 256-unit chunks
+int pick_iters(long long units, int max_blocks)
+{
+  const long long chunks = (units + kBlock - 1) / kBlock;
+  int iters = 1;
+  while (chunks / iters > max_blocks && iters < 1024) iters *= 2;
+  return iters;
+}
+
+}  // namespace
+
+struct lbm64_ctx {
+  Knobs knobs;                       // the environment knobs as lbm64_create read them (lbm_knobs.h)
+  lbm64_params p{};
+  int free_cells = 0;
+  double free_cells_inv = 0.0;
+  int device = 0;
+  bool nt_stores = false;
+  int lane_cells = kPairCells;       // 2 (nx even) or 1
+  size_t ncells = 0, ps = 0, grid_doubles = 0;
+  double* grid_alloc[2] = {nullptr, nullptr};
+  double* grid[2] = {nullptr, nullptr};      // plane 0 row 0 (after the front guard)
+  int cur = 0;
+  uint32_t* mask = nullptr;
+  uint32_t units = 0;
+  int iters = 1, blocks = 0;         // work blocks of a step launch
+  double* partials[2] = {nullptr, nullptr};
+  double* sums = nullptr;
+  int sums_cap = 0;
+  int* counter = nullptr;
+  double accel_w1 = 0.0, accel_w2 = 0.0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  int ev_launches = 0;
+  bool ev_valid = false;
+};
+
+namespace {
+
+using Step64Kernel = void (*)(Step64Args);
+// every instantiation of the one-step kernel, by [one cell per lane][non-temporal stores]
+constexpr Step64Kernel kStep64Kernels[2][2] = {
+  {&lbm_step_kernel_f64<kPairCells, false>, &lbm_step_kernel_f64<kPairCells, true>},
+  {&lbm_step_kernel_f64<1, false>, &lbm_step_kernel_f64<1, true>},
+};
+const char* const kStep64Names[2][2] = {
+  {"lbm_step_kernel_f64<2>", "lbm_step_kernel_f64<2,nt>"},
+  {"lbm_step_kernel_f64<1>", "lbm_step_kernel_f64<1,nt>"},
+};
+
+int ensure_sums(lbm64_ctx* c, int n)
+{
+  if (n <= c->sums_cap) return 0;
+  n = std::max(n, std::max(c->p.max_iters, 4096));
+  double* dev = nullptr;
+  HIP_TRY(hipMalloc(&dev, sizeof(double) * static_cast<size_t>(n)));
+  if (c->sums) (void)hipFree(c->sums);         // between runs: the stream is idle
+  c->sums = dev;
+  c->sums_cap = n;
+  return 0;
+}
+
+// cells of whole rows that the chunked copies (cells, observables) move at a time
+size_t chunk_cells(const lbm64_ctx* c)
+{
+  const size_t nx = static_cast<size_t>(c->p.nx);
+  return std::min(c->ncells, std::max<size_t>(1, static_cast<size_t>(std::max(c->knobs.obs_chunk_cells, 1)) / nx) * nx);
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbm64_destroy(lbm64_ctx* c)
+{
+  if (!c) return 0;
+  (void)hipSetDevice(c->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  for (int g = 0; g < 2; ++g) if (c->grid_alloc[g]) (void)hipFree(c->grid_alloc[g]);
+  if (c->mask) (void)hipFree(c->mask);
+  for (int i = 0; i < 2; ++i) if (c->partials[i]) (void)hipFree(c->partials[i]);
+  if (c->sums) (void)hipFree(c->sums);
+  if (c->counter) (void)hipFree(c->counter);
+  if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
+  if (c->ev_end) (void)hipEventDestroy(c->ev_end);
+  if (c->stream) (void)hipStreamDestroy(c->stream);
+  delete c;
+  return 0;
+}
+
+int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const int* obstacles, int device, unsigned flags)
+{
+  if (!out || !p || !obstacles) { lbm_internal::set_error("lbm64_create: null argument"); return 1; }
+  *out = nullptr;
+  if (p->nx < 1) { lbm_internal::set_error("lbm64_create: nx must be positive"); return 1; }
+  if (p->ny < 3) { lbm_internal::set_error("lbm64_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
+  if (free_cells <= 0) { lbm_internal::set_error("lbm64_create: free_cells must be positive"); return 1; }
+  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES)) != 0u) {
+    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only (whole grids, one step per launch, exact arithmetic)");
+    return 1;
+  }
+  if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { lbm_internal::set_error("lbm64_create: grid too large for 32-bit cell indices"); return 1; }
+
+  HIP_TRY(hipSetDevice(device));
+  lbm64_ctx* c = new lbm64_ctx();
+  c->knobs = knobs_from_env();
+  c->p = *p;
+  c->free_cells = free_cells;
+  c->free_cells_inv = 1.0 / free_cells;                                      // d2q9-bgk.c:950 in double
+  c->device = device;
+  c->accel_w1 = p->density * p->accel * 0.111111111111111111111111;         // d2q9-bgk.c:445
+  c->accel_w2 = p->density * p->accel * 0.0277777777777777777777778;        // d2q9-bgk.c:446
+  c->ncells = static_cast<size_t>(p->nx) * p->ny;
+  c->ps = plane_stride_doubles(c->ncells, c->knobs.skew);
+  c->grid_doubles = 9 * c->ps + 128;
+  // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache (the float path's rule and flags)
+  const size_t state_bytes = 2 * 9 * c->ncells * sizeof(double);
+  c->nt_stores = state_bytes > (192u << 20);
+  if (flags & LBM_FLAG_NT_STORES) c->nt_stores = true;
+  if (flags & LBM_FLAG_NO_NT_STORES) c->nt_stores = false;
+  c->lane_cells = (p->nx % kPairCells == 0) ? kPairCells : 1;
+  c->units = static_cast<uint32_t>(c->ncells / c->lane_cells);
+  c->iters = pick_iters(c->units, std::max(c->knobs.maxblocks, 1));
+  c->blocks = static_cast<int>((static_cast<long long>(c->units) + static_cast<long long>(kBlock) * c->iters - 1) / (static_cast<long long>(kBlock) * c->iters));
+
+  auto fail = [&](void) { lbm64_destroy(c); return 1; };
+#define HIP_TRY_C(expr)                                                                      \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
+      return fail();                                                                         \
+    }                                                                                        \
+  } while (0)
+
+  HIP_TRY_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIP_TRY_C(hipEventCreate(&c->ev_begin));
+  HIP_TRY_C(hipEventCreate(&c->ev_end));
+  for (int g = 0; g < 2; ++g) {
+    HIP_TRY_C(hipMalloc(&c->grid_alloc[g], sizeof(double) * c->grid_doubles));
+    HIP_TRY_C(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(double) * c->grid_doubles, c->stream));
+    c->grid[g] = c->grid_alloc[g] + 64;
+  }
+  // obstacle bitfield: bit c of the cell index, as the float path's
+  const size_t mwords = (c->ncells + 31) / 32 + 4;
+  {
+    std::vector<uint32_t> bits(mwords, 0u);
+    for (size_t i = 0; i < c->ncells; ++i)
+      if (obstacles[i]) bits[i >> 5] |= 1u << (i & 31);
+    HIP_TRY_C(hipMalloc(&c->mask, sizeof(uint32_t) * mwords));
+    HIP_TRY_C(hipMemcpy(c->mask, bits.data(), sizeof(uint32_t) * mwords, hipMemcpyHostToDevice));
+  }
+  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * (c->blocks + 1)));
+  HIP_TRY_C(hipMalloc(&c->counter, sizeof(int)));
+  HIP_TRY_C(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream));
+  if (ensure_sums(c, 1)) return fail();
+  {
+    const double w0 = p->density * 4.0 / 9.0, w1 = p->density / 9.0, w2 = p->density / 36.0;   // d2q9-bgk.c:880-882
+    const unsigned blocks = static_cast<unsigned>((c->ncells + 255) / 256);
+    hipLaunchKernelGGL(lbm64_init_kernel, dim3(blocks), dim3(256), 0, c->stream, c->grid[0], c->ps, c->ncells, w0, w1, w2);
+    HIP_TRY_C(hipGetLastError());
+  }
+  HIP_TRY_C(hipStreamSynchronize(c->stream));
+#undef HIP_TRY_C
+  *out = c;
+  return 0;
+}
+
+int lbm64_run(lbm64_ctx* c, int n_steps, double* av_vels)
+{
+  if (!c) { lbm_internal::set_error("lbm64_run: null context"); return 1; }
+  if (n_steps < 0) { lbm_internal::set_error("lbm64_run: negative step count"); return 1; }
+  if (n_steps == 0) return 0;
+  HIP_TRY(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  if (ensure_sums(c, n_steps)) return 1;
+  // accelerate_flow of the first step (d2q9-bgk.c:345-348): every later one is the epilogue of the step before it
+  const uint32_t nx = static_cast<uint32_t>(c->p.nx), ny = static_cast<uint32_t>(c->p.ny);
+  hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, s, c->grid[c->cur], c->ps, c->mask, nx, ny - 2, c->accel_w1, c->accel_w2);
+  HIP_TRY(hipGetLastError());
+  Step64Args a{};
+  a.mask = c->mask;
+  a.ps = c->ps;
+  a.nx = nx; a.ny = ny;
+  a.units = c->units;
+  a.iters = c->iters;
+  a.omega = c->p.omega;
+  a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+  a.sums = c->sums;
+  a.counter = c->counter;
+  const Step64Kernel kernel = kStep64Kernels[c->lane_cells == 1][c->nt_stores];
+  HIP_TRY(hipEventRecord(c->ev_begin, s));
+  int parity = 0;
+  for (int t = 0; t < n_steps; ++t) {
+    a.src = c->grid[c->cur];
+    a.dst = c->grid[c->cur ^ 1];
+    a.accel_row = t + 1 < n_steps ? static_cast<int>(ny) - 2 : -1;
+    a.partials_out = c->partials[parity];
+    a.prev_partials = c->partials[parity ^ 1];
+    a.n_prev = t > 0 ? c->blocks : 0;
+    kernel<<<dim3(c->blocks + 1), dim3(kBlock), 0, s>>>(a);               // + the fold block
+    parity ^= 1;
+    c->cur ^= 1;
+  }
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(c->ev_end, s));
+  c->ev_launches = n_steps;
+  c->ev_valid = true;
+  hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, s, c->partials[parity ^ 1], c->blocks, c->sums, c->counter);
+  HIP_TRY(hipGetLastError());
+  if (av_vels) {
+    HIP_TRY(hipMemcpyAsync(av_vels, c->sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int t = 0; t < n_steps; ++t) av_vels[t] = av_vels[t] * c->free_cells_inv;          // d2q9-bgk.c:367
+  } else {
+    HIP_TRY(hipStreamSynchronize(s));
+  }
+  return 0;
+}
+
+int lbm64_get_cells(lbm64_ctx* c, double* cells_aos)
+{
+  if (!c || !cells_aos) { lbm_internal::set_error("lbm64_get_cells: null argument"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t chunk = chunk_cells(c);
+  unsigned long long* tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
+  hipError_t e = hipSuccess;
+  for (size_t c0 = 0; c0 < c->ncells && e == hipSuccess; c0 += chunk) {
+    const size_t n = std::min(chunk, c->ncells - c0);
+    hipLaunchKernelGGL(lbm64_soa_to_aos_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, c->stream,
+                       reinterpret_cast<const unsigned long long*>(c->grid[c->cur] + c0), tmp, c->ps, n);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(cells_aos + 9 * c0, tmp, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  (void)hipFree(tmp);
+  HIP_TRY(e);
+  return 0;
+}
+
+int lbm64_set_cells(lbm64_ctx* c, const double* cells_aos)
+{
+  if (!c || !cells_aos) { lbm_internal::set_error("lbm64_set_cells: null argument"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t chunk = chunk_cells(c);
+  unsigned long long* tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
+  hipError_t e = hipSuccess;
+  for (size_t c0 = 0; c0 < c->ncells && e == hipSuccess; c0 += chunk) {
+    const size_t n = std::min(chunk, c->ncells - c0);
+    e = hipMemcpyAsync(tmp, cells_aos + 9 * c0, sizeof(double) * 9 * n, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(lbm64_aos_to_soa_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, c->stream,
+                         tmp, reinterpret_cast<unsigned long long*>(c->grid[c->cur] + c0), c->ps, n);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  (void)hipFree(tmp);
+  HIP_TRY(e);
+  return 0;
+}
+
+int lbm64_get_observables(lbm64_ctx* c, double* obs)
+{
+  if (!c || !obs) { lbm_internal::set_error("lbm64_get_observables: null argument"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  const size_t chunk = chunk_cells(c);
+  double* tmp = nullptr;
+  HIP_TRY(hipMalloc(&tmp, sizeof(double) * 4 * chunk));
+  hipError_t e = hipSuccess;
+  for (size_t c0 = 0; c0 < c->ncells && e == hipSuccess; c0 += chunk) {
+    const size_t n = std::min(chunk, c->ncells - c0);
+    hipLaunchKernelGGL(lbm64_observables_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, c->stream,
+                       c->grid[c->cur] + c0, c->ps, n, tmp);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(obs + 4 * c0, tmp, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  }
+  (void)hipFree(tmp);
+  HIP_TRY(e);
+  return 0;
+}
+
+int lbm64_av_velocity_sum(lbm64_ctx* c, double* tot_u)
+{
+  if (!c || !tot_u) { lbm_internal::set_error("lbm64_av_velocity_sum: null argument"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  const int blocks = static_cast<int>(std::min<size_t>((c->ncells + kBlock - 1) / kBlock, 1024));
+  double* part = nullptr;
+  HIP_TRY(hipMalloc(&part, sizeof(double) * blocks));
+  hipLaunchKernelGGL(lbm64_av_velocity_kernel, dim3(blocks), dim3(kBlock), 0, c->stream, c->grid[c->cur], c->ps, c->mask, c->ncells, part);
+  std::vector<double> host(blocks);
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess) e = hipMemcpyAsync(host.data(), part, sizeof(double) * blocks, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(part);
+  HIP_TRY(e);
+  double s = 0.0;
+  for (double v : host) s += v;
+  *tot_u = s;
+  return 0;
+}
+
+int lbm64_last_run_kernel_ms(lbm64_ctx* c, double* ms, int* launches)
+{
+  if (!c || !ms) { lbm_internal::set_error("lbm64_last_run_kernel_ms: null argument"); return 1; }
+  if (!c->ev_valid) { lbm_internal::set_error("lbm64_last_run_kernel_ms: no run yet"); return 1; }
+  HIP_TRY(hipSetDevice(c->device));
+  float t = 0.f;
+  HIP_TRY(hipEventElapsedTime(&t, c->ev_begin, c->ev_end));
+  *ms = t;
+  if (launches) *launches = c->ev_launches;
+  return 0;
+}
+
+int lbm64_describe(const lbm64_ctx* c, char* kernel_name, size_t len, long long* blocks, long long* cells_per_block, long long* state_bytes)
+{
+  if (!c) { lbm_internal::set_error("lbm64_describe: null context"); return 1; }
+  if (kernel_name && len > 0) std::snprintf(kernel_name, len, "%s", kStep64Names[c->lane_cells == 1][c->nt_stores]);
+  if (blocks) *blocks = c->blocks;
+  if (cells_per_block) *cells_per_block = static_cast<long long>(kBlock) * c->iters * c->lane_cells;
+  if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->ncells * sizeof(double));
+  return 0;
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "lbm_d2q9.h"
+#include "lbm_d2q9_f64.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 
@@ -243,19 +244,16 @@ float lbm_reynolds(const lbm_params* p, float av_velocity)
 // glibc prints too) over row blocks formatted in parallel and written in order: at 8192x8192 the file
 // is 5.8 GB of text and formatting it dominates the run if done through stdio.
 // `fluid(c, u_x, u_y, u, pressure)` supplies the four values of a non-obstacle cell (:1084-1111).
+// Real = float (promoted to double by the format, as the reference's are) or double (the double-precision mode, lbm_d2q9_f64.h).
 }  // extern "C"
 
 namespace {
-template <typename Fluid>
-int write_final_state_impl(const char* path, const lbm_params* p, const int* obstacles, int rows, int displ, int append, Fluid fluid)
+template <typename Real, typename Fluid>
+int write_final_state_impl(const char* path, int nx, Real obstacle_pressure, const int* obstacles, int rows, int displ, int append, Fluid fluid)
 {
   std::FILE* fp = std::fopen(path, append ? "a" : "w");                        // :1054-1057
   if (!fp) { set_error("could not open file output file"); return 1; }         // :1061
-  const int nx = p->nx;
-  const float c_sq = 1.0f / 3.0f;                                              // :1040
-  const float obstacle_pressure = p->density * c_sq;                           // :1079
-
-  auto put_float = [](char* out, float v) -> char* {                          // "%.12E" of a float promoted to double
+  auto put_float = [](char* out, Real v) -> char* {                           // "%.12E" of a double, or of a float promoted to double
     const double d = static_cast<double>(v);
     if (std::isnan(d)) { const char* t = std::signbit(d) ? "-NAN" : "NAN"; while (*t) *out++ = *t++; return out; }
     if (std::isinf(d)) { const char* t = d < 0 ? "-INF" : "INF"; while (*t) *out++ = *t++; return out; }
@@ -273,9 +271,9 @@ int write_final_state_impl(const char* path, const lbm_params* p, const int* obs
     for (int y = y0; y < y1; ++y) {
       for (int x = 0; x < nx; ++x) {
         const size_t c = static_cast<size_t>(y) * nx + x;
-        float u_x, u_y, u, pressure;
+        Real u_x, u_y, u, pressure;
         if (obstacles[c]) {                                                    // :1076-1080
-          u_x = u_y = u = 0.0f;
+          u_x = u_y = u = Real(0);
           pressure = obstacle_pressure;
         } else {
           fluid(c, u_x, u_y, u, pressure);
@@ -327,8 +325,8 @@ int lbm_write_final_state(const char* path, const lbm_params* p, const float* ce
                           int rows, int displ, int append)
 {
   if (!path || !p || !cells || !obstacles) { set_error("lbm_write_final_state: null argument"); return 1; }
-  const float c_sq = 1.0f / 3.0f;
-  return write_final_state_impl(path, p, obstacles, rows, displ, append, [=](size_t c, float& u_x, float& u_y, float& u, float& pressure) {
+  const float c_sq = 1.0f / 3.0f;                                              // :1040
+  return write_final_state_impl<float>(path, p->nx, p->density * c_sq /* :1079 */, obstacles, rows, displ, append, [=](size_t c, float& u_x, float& u_y, float& u, float& pressure) {
     const float* f = cells + c * LBM_NSPEEDS;
     float rho = 0.0f;
     for (int k = 0; k < LBM_NSPEEDS; ++k) rho += f[k];                       // :1084-1090
@@ -344,7 +342,8 @@ int lbm_write_final_state_obs(const char* path, const lbm_params* p, const float
                               int rows, int displ, int append)
 {
   if (!path || !p || !obs || !obstacles) { set_error("lbm_write_final_state_obs: null argument"); return 1; }
-  return write_final_state_impl(path, p, obstacles, rows, displ, append, [=](size_t c, float& u_x, float& u_y, float& u, float& pressure) {
+  const float c_sq = 1.0f / 3.0f;                                              // :1040
+  return write_final_state_impl<float>(path, p->nx, p->density * c_sq /* :1079 */, obstacles, rows, displ, append, [=](size_t c, float& u_x, float& u_y, float& u, float& pressure) {
     const float* o = obs + 4 * c;
     u_x = o[0]; u_y = o[1]; u = o[2]; pressure = o[3];
   });
@@ -353,6 +352,74 @@ int lbm_write_final_state_obs(const char* path, const lbm_params* p, const float
 // d2q9-bgk.c:1127-1139.
 int lbm_write_av_vels(const char* path, const float* av_vels, int n)
 {
+  std::FILE* fp = std::fopen(path, "w");
+  if (!fp) { set_error("could not open file output file"); return 1; }         // :1131
+  for (int i = 0; i < n; ++i) std::fprintf(fp, "%d:\t%.12E\n", i, av_vels[i]); // :1136
+  std::fclose(fp);
+  return 0;
+}
+
+// ---- the double-precision mode (include/lbm_d2q9_f64.h): the same host pieces with every float object a double ----------------
+
+int lbm64_abi_version(void) { return LBM64_ABI_VERSION; }
+
+// d2q9-bgk.c:772-803 with %lf.
+int lbm64_read_params(const char* paramfile, lbm64_params* out)
+{
+  if (!paramfile || !out) { set_error("lbm64_read_params: null argument"); return 1; }
+  std::FILE* fp = std::fopen(paramfile, "r");
+  if (!fp) { set_error(std::string("could not open input parameter file: ") + paramfile); return 1; }   // :776
+  struct Field { const char* name; const char* fmt; void* dst; };
+  const Field fields[7] = {
+      {"nx", "%d\n", &out->nx},            {"ny", "%d\n", &out->ny},
+      {"maxIters", "%d\n", &out->max_iters}, {"reynolds_dim", "%d\n", &out->reynolds_dim},
+      {"density", "%lf\n", &out->density}, {"accel", "%lf\n", &out->accel},
+      {"omega", "%lf\n", &out->omega}};
+  for (const Field& f : fields) {
+    if (std::fscanf(fp, f.fmt, f.dst) != 1) {                                                             // :781-800
+      std::fclose(fp);
+      set_error(std::string("could not read param file: ") + f.name);
+      return 1;
+    }
+  }
+  std::fclose(fp);
+  return 0;
+}
+
+// d2q9-bgk.c:716-751 from device-computed u_x, u_y: a double accumulator, the reference's cell order.
+double lbm64_av_velocity_obs(const lbm64_params* p, const double* obs, const int* obstacles, int rows)
+{
+  double tot_u = 0.0;
+  const size_t n = static_cast<size_t>(rows) * static_cast<size_t>(p->nx);
+  for (size_t c = 0; c < n; ++c) {
+    if (obstacles[c]) continue;                                                 // :721
+    const double ux = obs[4 * c], uy = obs[4 * c + 1];
+    tot_u += std::sqrt((ux * ux) + (uy * uy));                                  // :748
+  }
+  return tot_u;
+}
+
+// d2q9-bgk.c:1005-1007.
+double lbm64_reynolds(const lbm64_params* p, double av_velocity)
+{
+  const double viscosity = 1.0 / 6.0 * (2.0 / p->omega - 1.0);
+  return av_velocity * p->reynolds_dim / viscosity;
+}
+
+int lbm64_write_final_state_obs(const char* path, const lbm64_params* p, const double* obs, const int* obstacles, int rows, int displ, int append)
+{
+  if (!path || !p || !obs || !obstacles) { set_error("lbm64_write_final_state_obs: null argument"); return 1; }
+  const double c_sq = 1.0 / 3.0;                                                // :1040
+  return write_final_state_impl<double>(path, p->nx, p->density * c_sq /* :1079 */, obstacles, rows, displ, append, [=](size_t c, double& u_x, double& u_y, double& u, double& pressure) {
+    const double* o = obs + 4 * c;
+    u_x = o[0]; u_y = o[1]; u = o[2]; pressure = o[3];
+  });
+}
+
+// d2q9-bgk.c:1127-1139.
+int lbm64_write_av_vels(const char* path, const double* av_vels, int n)
+{
+  if (!path || (!av_vels && n > 0)) { set_error("lbm64_write_av_vels: null argument"); return 1; }
   std::FILE* fp = std::fopen(path, "w");
   if (!fp) { set_error("could not open file output file"); return 1; }         // :1131
   for (int i = 0; i < n; ++i) std::fprintf(fp, "%d:\t%.12E\n", i, av_vels[i]); // :1136

@@ -1,0 +1,188 @@
+"""The double-precision mode: ctypes binding of include/lbm_d2q9_f64.h (same library, liblbm_d2q9.so) and its host mirror.
+
+    from mpilattice_boltzmann_amd import f64
+    p = f64.read_params64("input_128x128.params")
+    obst, free = lbm.read_obstacles("obstacles_128x128.dat", p.nx, p.ny)
+    with f64.Grid64(p, obst) as g:
+        av_vels = g.run(p.max_iters)
+        print(g.reynolds())
+        g.write_values("final_state.dat", "av_vels.dat", av_vels)
+
+The reference's arithmetic with every float object a double (the contract is in the header): whole periodic grids on one GPU, one
+step per launch of lbm_step_kernel_f64.  There is no CPU fallback: a missing library or symbol raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+import numpy as np
+
+from . import _capi
+from ._capi import LbmError, check
+from .decks import Params
+
+ABI_VERSION = 1
+FLAG_NT_STORES, FLAG_NO_NT_STORES = _capi.FLAG_NT_STORES, _capi.FLAG_NO_NT_STORES
+
+
+class CParams64(C.Structure):
+    """struct lbm64_params."""
+
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("max_iters", C.c_int), ("reynolds_dim", C.c_int),
+                ("density", C.c_double), ("accel", C.c_double), ("omega", C.c_double)]
+
+
+_P = C.POINTER
+_ctx = C.c_void_p
+_SIGNATURES = {
+    "lbm64_abi_version": (C.c_int, []),
+    "lbm64_read_params": (C.c_int, [C.c_char_p, _P(CParams64)]),
+    "lbm64_av_velocity_obs": (C.c_double, [_P(CParams64), _P(C.c_double), _P(C.c_int), C.c_int]),
+    "lbm64_reynolds": (C.c_double, [_P(CParams64), C.c_double]),
+    "lbm64_write_final_state_obs": (C.c_int, [C.c_char_p, _P(CParams64), _P(C.c_double), _P(C.c_int), C.c_int, C.c_int, C.c_int]),
+    "lbm64_write_av_vels": (C.c_int, [C.c_char_p, _P(C.c_double), C.c_int]),
+    "lbm64_create": (C.c_int, [_P(_ctx), _P(CParams64), C.c_int, _P(C.c_int), C.c_int, C.c_uint]),
+    "lbm64_destroy": (C.c_int, [_ctx]),
+    "lbm64_run": (C.c_int, [_ctx, C.c_int, _P(C.c_double)]),
+    "lbm64_get_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm64_set_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm64_get_observables": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm64_av_velocity_sum": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm64_last_run_kernel_ms": (C.c_int, [_ctx, _P(C.c_double), _P(C.c_int)]),
+    "lbm64_describe": (C.c_int, [_ctx, C.c_char_p, C.c_size_t, _P(C.c_longlong), _P(C.c_longlong), _P(C.c_longlong)]),
+}
+EXPORTS = tuple(_SIGNATURES)
+
+_typed = None
+
+
+def load_library() -> C.CDLL:
+    """liblbm_d2q9.so with the lbm64_* prototypes set.  Raises if the library or one of the symbols is absent."""
+    global _typed
+    if _typed is None:
+        lib = _capi.load_library()
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(lib, name)           # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
+        if lib.lbm64_abi_version() != ABI_VERSION:
+            raise RuntimeError(f"liblbm_d2q9.so double-precision ABI {lib.lbm64_abi_version()} != binding {ABI_VERSION}: rebuild")
+        _typed = lib
+    return _typed
+
+
+def _cparams(p) -> CParams64:
+    return CParams64(int(p.nx), int(p.ny), int(p.max_iters), int(p.reynolds_dim), float(p.density), float(p.accel), float(p.omega))
+
+
+def read_params64(paramfile: str) -> Params:
+    """`initialise()`'s parameter-file half (`d2q9-bgk.c:772-803`) with density, accel and omega read as doubles (`%lf`);
+    LbmError carries the die() text."""
+    lib = load_library()
+    cp = CParams64()
+    check(lib.lbm64_read_params(os.fsencode(paramfile), C.byref(cp)))
+    return Params(cp.nx, cp.ny, cp.max_iters, cp.reynolds_dim, cp.density, cp.accel, cp.omega)
+
+
+def write_av_vels64(path: str, av_vels: np.ndarray) -> None:
+    """av_vels.dat (`d2q9-bgk.c:1127-1139`) from doubles."""
+    av = np.ascontiguousarray(av_vels, dtype=np.float64)
+    check(load_library().lbm64_write_av_vels(os.fsencode(path), _capi.as_double_ptr(av), av.size))
+
+
+def write_final_state_obs64(path: str, params, obs: np.ndarray, obstacles: np.ndarray) -> None:
+    """final_state.dat (`d2q9-bgk.c:1054-1120`) from `Grid64.get_observables()` output."""
+    obs = np.ascontiguousarray(obs, dtype=np.float64)
+    obst = np.ascontiguousarray(obstacles, dtype=np.int32)
+    cp = _cparams(params)
+    check(load_library().lbm64_write_final_state_obs(os.fsencode(path), C.byref(cp), _capi.as_double_ptr(obs), _capi.as_int_ptr(obst), int(params.ny), 0, 0))
+
+
+class Grid64:
+    """Device state of a whole periodic grid in double precision — one `lbm64_ctx`."""
+
+    def __init__(self, params, obstacles: np.ndarray, device: int = 0, flags: int = 0):
+        self._lib = load_library()
+        self.params = params
+        self.obstacles = np.ascontiguousarray(obstacles, dtype=np.int32)
+        if self.obstacles.shape != (params.ny, params.nx):
+            raise ValueError("obstacles must be (ny, nx)")
+        self.free_cells = int(self.obstacles.size - np.count_nonzero(self.obstacles))
+        self._cp = _cparams(params)
+        self._ctx = _ctx()
+        check(self._lib.lbm64_create(C.byref(self._ctx), C.byref(self._cp), self.free_cells, _capi.as_int_ptr(self.obstacles), device, flags))
+
+    def close(self) -> None:
+        if getattr(self, "_ctx", None):
+            self._lib.lbm64_destroy(self._ctx)
+            self._ctx = None
+
+    def __enter__(self) -> "Grid64":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, n_steps: Optional[int] = None) -> np.ndarray:
+        """n_steps iterations (default max_iters); returns av_vels, float64 (n_steps,)."""
+        n = self.params.max_iters if n_steps is None else int(n_steps)
+        av = np.zeros(max(n, 1), dtype=np.float64)
+        check(self._lib.lbm64_run(self._ctx, n, _capi.as_double_ptr(av)))
+        return av[:n]
+
+    def get_cells(self) -> np.ndarray:
+        """(ny, nx, 9) float64, the reference's AoS layout."""
+        cells = np.empty((self.params.ny, self.params.nx, 9), dtype=np.float64)
+        check(self._lib.lbm64_get_cells(self._ctx, _capi.as_double_ptr(cells)))
+        return cells
+
+    def set_cells(self, cells: np.ndarray) -> None:
+        cells = np.ascontiguousarray(cells, dtype=np.float64)
+        if cells.size != self.params.ny * self.params.nx * 9:
+            raise ValueError("cells must hold ny * nx * 9 doubles")
+        check(self._lib.lbm64_set_cells(self._ctx, _capi.as_double_ptr(cells)))
+
+    def get_observables(self) -> np.ndarray:
+        """(ny, nx, 4) float64 = {u_x, u_y, u, pressure} per cell, the fluid-cell formula for every cell."""
+        obs = np.empty((self.params.ny, self.params.nx, 4), dtype=np.float64)
+        check(self._lib.lbm64_get_observables(self._ctx, _capi.as_double_ptr(obs)))
+        return obs
+
+    def av_velocity_sum(self) -> float:
+        """av_velocity()'s sum over the free cells, summed on the device."""
+        tot = C.c_double(0.0)
+        check(self._lib.lbm64_av_velocity_sum(self._ctx, C.byref(tot)))
+        return tot.value
+
+    def reynolds(self) -> float:
+        """calc_reynolds (`d2q9-bgk.c:1005-1007`) of the current state, the sum taken in the reference's cell order on the host."""
+        obs = self.get_observables()
+        tot = self._lib.lbm64_av_velocity_obs(C.byref(self._cp), _capi.as_double_ptr(obs), _capi.as_int_ptr(self.obstacles), self.params.ny)
+        return self._lib.lbm64_reynolds(C.byref(self._cp), tot * (1.0 / self.free_cells))
+
+    def write_values(self, final_state_path: str, av_vels_path: str, av_vels: np.ndarray) -> None:
+        """write_values (`d2q9-bgk.c:1054-1139`): both output files."""
+        write_final_state_obs64(final_state_path, self.params, self.get_observables(), self.obstacles)
+        write_av_vels64(av_vels_path, av_vels)
+
+    def last_run_kernel_ms(self) -> tuple[float, int]:
+        """(device ms from the first to the last step kernel of the last run, number of step launches)."""
+        ms, n = C.c_double(0.0), C.c_int(0)
+        check(self._lib.lbm64_last_run_kernel_ms(self._ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def describe(self) -> dict:
+        name = C.create_string_buffer(256)
+        blocks, per_block, nbytes = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.lbm64_describe(self._ctx, name, 256, C.byref(blocks), C.byref(per_block), C.byref(nbytes)))
+        return {"kernel": name.value.decode(), "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
+
+
+__all__ = ["ABI_VERSION", "EXPORTS", "CParams64", "Grid64", "LbmError", "load_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]

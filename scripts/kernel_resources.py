@@ -2,7 +2,9 @@
 """Per-kernel register / scratch / LDS / occupancy table of liblbm_d2q9.so's device code, from
 `hipcc -Rpass-analysis=kernel-resource-usage` (compile-only: runs without a GPU).
 
-    python scripts/kernel_resources.py [--out profiles/r02/kernel_resources.txt]
+    python scripts/kernel_resources.py [--unit lbm_f64.hip] [--out profiles/r02/kernel_resources.txt]
+
+--unit: the translation unit under csrc/ (default lbm_kernels.hip; lbm_f64.hip: the double-precision mode).
 
 Exit status 1 if any kernel uses scratch (spills or runtime-indexed private arrays)."""
 import argparse
@@ -24,10 +26,11 @@ def demangle(names):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out")
+    ap.add_argument("--unit", default="lbm_kernels.hip")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-               "-I", CSRC, "-c", os.path.join(CSRC, "lbm_kernels.hip"), "-o", os.path.join(tmp, "k.o"),
+               "-I", CSRC, "-c", os.path.join(CSRC, args.unit), "-o", os.path.join(tmp, "k.o"),
                "-Rpass-analysis=kernel-resource-usage"]
         r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
