@@ -9,7 +9,7 @@ namespace {
 // launch that follows it).  One block per step vector when the vectors are short; long vectors (8192x8192:
 // 3 x 65 536 per-tile sums, which took one block 102 us) go through lbm_fold_slices_kernel first:
 // kFoldSlices blocks per vector, then this kernel over the kFoldSlices slice sums.  Fixed order, no atomics.
-constexpr int kFoldSlices = 64;
+// (kFoldSlices: lbm_geometry.h)
 
 __global__ void __launch_bounds__(kBlock) lbm_fold_slices_kernel(const double* partials, int n, double* slice_sums)
 {

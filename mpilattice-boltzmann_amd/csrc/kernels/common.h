@@ -1,13 +1,10 @@
 // common.h — constants, argument block of the one-step kernels, loads/stores, reductions, the cell arithmetic (relax_cell), source-row selection
 // Part of the single translation unit lbm_kernels.hip (device code of liblbm_d2q9.so, gfx950 only).
 #pragma once
+#include "../lbm_geometry.h"   // kBlock, kCellsPerLane, kHaloGuard, kTerms*: shared with the host-only planning unit
 #include "exact_math.h"      // f2, recip_exact, sqrt_of_float: the shortened exact sequences, enumerated by scripts/experiments/*_exhaustive.hip
 
 namespace {
-
-constexpr int kBlock = 256;          // 4 wavefronts
-constexpr int kCellsPerLane = 4;     // one 16-byte access per population per lane
-constexpr int kHaloGuard = 4;        // floats of guard on each side of a halo-buffer row
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // dword-aligned 16-byte access
@@ -410,22 +407,7 @@ __device__ __forceinline__ auto& at_byte(B* base, uint32_t byte_off)
 // ghost ring: they do not count, and the double-precision sqrt is a tenth of the cell's instructions).
 // tile_accel is block-uniform: false for the tiles whose frame does not meet row ny-2, which then skip
 // the accelerate_flow code instead of predicating it away in every pair.
-// TERMS: how the sum|u| term of a cell, sqrt((double)msq) * (double)rinv (:667), is formed.  Populations never depend on it.
-//   kTermsDouble (LBM_FLAG_EXACT_AVVELS; lbm_tile_kernel's default): in double precision, every term correctly
-//     rounded before the product: v_rsq_f64 + 9 double-precision instructions per CELL.
-//   kTermsCompensated (lbm_multi_kernel's default): without double-precision arithmetic.  The root as an unevaluated float
-//     sum s + c (s = msq * rsq(msq); c = the Newton correction of s from the residual msq - s*s, which a fused multiply-add
-//     delivers exactly), the product with rinv as p + lo (p = s * rinv, its rounding error by another fused multiply-add,
-//     plus c * rinv): relative error ~2^-44 per cell where the double form has 2^-53 — av_vels, a float, comes out bit for
-//     bit the same in every test here — in 7 packed float instructions and two v_rsq_f32 per PAIR.  Only p is widened per
-//     pair; the lo parts are summed per lane in float (a lane adds at most a few per launch) and widened once.  Why it
-//     matters: the launch runs AT the socket power limit (scripts/power_trace.py: 1380 of 1400 W, shader clock 2.2 of
-//     2.4 GHz); double-precision instructions it does not execute come back as clock.  A cell at rest (msq = 0) gives 0:
-//     the rsq argument is held at the smallest normal number.  msq = inf (a diverged run) gives NaN where the reference
-//     gives inf.
-//   kTermsFloat (LBM_FLAG_FAST_AVVELS): v_sqrt_f32 and one multiply; av_vels then agrees to ~1e-7 (an ulp of its float).
-// kTermsFused added to one of them (LBM_FLAG_FUSED_ARITH): the same terms from the msq and rinv of the fused arithmetic (relax_core).
-constexpr int kTermsDouble = 0, kTermsFloat = 1, kTermsCompensated = 2, kTermsFused = 4;
+// TERMS: how the sum|u| term of a cell is formed (kTermsDouble, kTermsCompensated, kTermsFloat, + kTermsFused: lbm_geometry.h).
 
 __device__ __forceinline__ f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }     // v_pk_fma_f32
 

@@ -32,48 +32,7 @@ namespace {
 // Rows outside the partition: `y_periodic` wraps (self-contained domain); otherwise the storage has
 // `ghost` extra rows below and above the owned rows, filled by the neighbours before the launch.
 // ------------------------------------------------------------------------------------------------
-#ifndef LBM_MTY            // experiment builds: -DLBM_MTY=24 -DLBM_MLANES=768 (taller tiles, two blocks per CU)
-#define LBM_MTY 16
-#define LBM_MLANES 512
-#endif
-#ifndef LBM_MWAVES         // most waves per SIMD the kernels are compiled for (register budget 512 / LBM_MWAVES)
-#define LBM_MWAVES 6
-#endif
-#ifndef LBM_MTY4           // tile height of the 4-step instantiation, standard and narrow geometry (512 lanes)
-#define LBM_MTY4 13
-#endif
-#ifndef LBM_MTY4T          // tile height and block size of the 4-step instantiation, tall geometry
-#define LBM_MTY4T 24
-#define LBM_MLANES4T 768
-#endif
-constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY4Tall = LBM_MTY4T, kMLanes = LBM_MLANES, kMLanes4Tall = LBM_MLANES4T,
-              kMaxMultiSteps = 4,
-              kMaxGhost = 32,      // most ghost rows / columns a K-step partition keeps per side: the steps of a group of launches between two halo exchanges (32: column blocks)
-              kMaxGroup = 8;       // most launches of such a group
-constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall) : (kMTY4 < kMTY4Tall ? kMTY4 : kMTY4Tall);
-// Geometry of a launch: tile width, and by steps per launch tile height and block size.
-//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4: 64 x 13 (72 x 19 frame,
-//                49.0 KB, three blocks per CU).
-//   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24 waves);
-//                the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.
-//   kGeomNarrow  32-wide tiles, heights as kGeomStd: partitions so small that a launch is one round of blocks (twice the tiles, each
-//                with half the dependent work — a 1024 x 128-row partition keeps 256 CUs busy instead of 128).
-// The measurements behind each choice, round by round: DESIGN_APPENDIX.md R8.1.
-constexpr int kGeomStd = 0, kGeomNarrow = 1, kGeomTall = 2;
-constexpr int geom_tx(int g) { return g == kGeomNarrow ? kMTXNarrow : kMTX; }
-constexpr int multi_ty(int k, int g) { return k >= 4 ? (g == kGeomTall ? kMTY4Tall : kMTY4) : kMTY; }
-constexpr int multi_lanes(int k, int g) { return (k >= 4 && g == kGeomTall) ? kMLanes4Tall : kMLanes; }
-constexpr int geom_for(int k, int g) { return (g == kGeomTall && k < 4) ? kGeomStd : g; }      // the instantiation a launch of k steps uses
-
-// Sub-step j of k (1-based) works on the owned tile grown by (k-j) rows and multi_ex(k-j) = 2 ceil((k-j)/2)
-// columns on each side: the column growth is rounded up to even so that every region starts on an even x
-// and a lane can own an x-PAIR of cells (8-byte accesses; the two cells' arithmetic is packed by the
-// compiler into v_pk_*_f32, which halves the instruction count - the one-cell form of this kernel was
-// VALU-bound).  Where k-j is odd the region's outermost column lies outside every owned cell's dependency
-// cone: it is computed from whatever the frame holds there (stale values of an earlier sub-step, always
-// inside the frame) and never kept or counted.  (Rounds 1 - 4 grew the columns by 2(k-j): K = 4 regions
-// 76 / 72 / 68 / 64 wide instead of 72 / 68 / 68 / 64, frames 12 columns wider than needed.)
-constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
+// Tile shapes, block sizes and the steps a launch can make (kMTX ... kMaxGroup, kGeom*, geom_tx, multi_ty, multi_lanes, geom_for, multi_ex): lbm_geometry.h.
 #if LBM_TILE_STAMPS      // diagnostic builds (tile.h, scripts/tile_stamps.py): stamps of one block in the middle of the launch, lane 0
 #define LBM_MSTAMP(i) do { if (blockIdx.x == (gridDim.x >> 1) && threadIdx.x == 0) g_tile_stamps[i] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -191,11 +150,7 @@ __device__ __forceinline__ void accelerate_pair(f2 (&out)[9], uint32_t mbits, bo
 // a launch that also computes ghost rows takes the counted form only in the tiles that hold such rows (its first and last tile rows),
 // chosen by a block-uniform branch; the ready words live in a third instantiation.  Whole grids: back to round 3's time; the 8192 x 1024-row
 // ring 43.4 -> 42.9 us/step beside 40.3 - 41.0 for the same rows as one periodic grid (profiles/r04/ab_part_template.txt).
-// PART = kPartPlain (whole periodic grids, and the launches of a partition that compute its owned rows only), kPartGhost (a launch that
-// also computes ghost rows: the counted test), kPartReady (owned rows only + the ready words in the fold block), kPartTile (every launch
-// of a rank of the 2-D decomposition: ghost rows AND ghost columns — the counted and kept tests in x as well, in the tiles on the rim of
-// the owned block only — and four ready words; the forms above do not change for it).
-constexpr int kPartPlain = 0, kPartGhost = 1, kPartReady = 2, kPartTile = 3;
+// PART = kPartPlain, kPartGhost, kPartReady or kPartTile (lbm_geometry.h; the forms above do not change for kPartTile).
 
 // The flag byte of an x-pair of the frame, written by sub-step 1 and read by the in-LDS sub-steps (which then need no grid
 // coordinates at all); bits 0-1 are the pair's obstacle bits.  0: the pair was not computed.

@@ -7,12 +7,12 @@
 
 namespace {
 
-constexpr int kPairCells = 2;        // one 16-byte access per population per lane
+// (kPairCells = 2, one 16-byte access per population per lane: lbm_geometry.h, through common.h)
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));   // 8-byte-aligned 16-byte access
 
-// Layout: nine planes of ny*nx doubles, plane stride `ps` doubles (plane_stride_doubles, lbm_f64.hip), two grids swapped per launch,
+// Layout: nine planes of ny*nx doubles, plane stride `ps` doubles (plane_stride_floats in elements, lbm_plan.cpp), two grids swapped per launch,
 // the obstacle map as the float path's bitfield (bit c of the cell index).  Cell indices are 32-bit (lbm64_create refuses grids of
 // 2^31 cells or more); every ADDRESS is formed in 64 bits: the nine planes of an 8192 x 8192 grid are 4.8 GB.
 struct Step64Args {

@@ -27,7 +27,7 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // Geometry is a template parameter pair: T = owned tile edge, H = ghost ring = max steps per launch
 // (both even); the block has R*R/2 lanes (the load phase: one aligned x-pair per lane).
-constexpr int kMaxTileSteps = 8;
+// (kMaxTileSteps = 8, the H of the widest ring: lbm_geometry.h)
 
 // Diagnostic builds only (scripts/build_variant.sh tile_stamps -DLBM_TILE_STAMPS=1, scripts/tile_stamps.py): shader-clock
 // stamps of block 1, lane 0 at the phase boundaries of a launch.  No stamp executes in the product build.

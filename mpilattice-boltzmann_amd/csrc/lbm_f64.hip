@@ -8,7 +8,7 @@
 // one step per launch: whole periodic grids on one GPU only (no partitions, no several steps per launch, no fused arithmetic, no
 // hipGraph, no state digest).
 //
-// Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (plane_stride_doubles), two grids
+// Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (the float path's rule in elements: lbm_plan.cpp plane_stride_floats), two grids
 // swapped per launch, the obstacle map as the float path's bitfield.  Compiled with -ffp-contract=off like the rest of the library:
 // the post-step populations are the bits gcc -std=c99 gives the same statements (tests/f64_ref.c).
 //
@@ -39,28 +39,6 @@ namespace {
       return 1;                                                                              \
     }                                                                                        \
   } while (0)
-
-// Plane stride in doubles — the float path's plane_stride_floats rule (lbm_kernels.hip), this unit's own copy of it, in elements:
-// ny*nx + guard for the shifted loads at both ends, rounded to 64 elements (512 B), an odd number of such units, then skewed by `skew`
-// units for large grids so that the 9 planes (and the two grids) do not all start on the same HBM channel when ny*nx is a large
-// power of two.  Always even: the pair form's aligned 16-byte accesses.
-size_t plane_stride_doubles(size_t ncells, int skew)
-{
-  size_t s = (ncells + 64 + 63) / 64 * 64;
-  if ((s / 64) % 2 == 0) s += 64;
-  if (ncells >= (1u << 20)) s += 64 * static_cast<size_t>(skew);
-  return s;
-}
-
-// the float path's rule (pick_iters, lbm_kernels.hip): at most max_blocks work blocks (LBM_TUNE_MAXBLOCKS, 16384), each with a
-// power-of-two number of 256-unit chunks
-int pick_iters(long long units, int max_blocks)
-{
-  const long long chunks = (units + kBlock - 1) / kBlock;
-  int iters = 1;
-  while (chunks / iters > max_blocks && iters < 1024) iters *= 2;
-  return iters;
-}
 
 }  // namespace
 
@@ -166,7 +144,7 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   c->accel_w1 = p->density * p->accel * 0.111111111111111111111111;         // d2q9-bgk.c:445
   c->accel_w2 = p->density * p->accel * 0.0277777777777777777777778;        // d2q9-bgk.c:446
   c->ncells = static_cast<size_t>(p->nx) * p->ny;
-  c->ps = plane_stride_doubles(c->ncells, c->knobs.skew);
+  c->ps = lbm_internal::plane_stride_floats(c->ncells, c->knobs.skew);   // the float path's rule, in elements: always even (the pair form's aligned 16-byte accesses)
   c->grid_doubles = 9 * c->ps + 128;
   // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache (the float path's rule and flags)
   const size_t state_bytes = 2 * 9 * c->ncells * sizeof(double);
@@ -175,7 +153,7 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   if (flags & LBM_FLAG_NO_NT_STORES) c->nt_stores = false;
   c->lane_cells = (p->nx % kPairCells == 0) ? kPairCells : 1;
   c->units = static_cast<uint32_t>(c->ncells / c->lane_cells);
-  c->iters = pick_iters(c->units, std::max(c->knobs.maxblocks, 1));
+  c->iters = lbm_internal::pick_iters(c->units, std::max(c->knobs.maxblocks, 1));
   c->blocks = static_cast<int>((static_cast<long long>(c->units) + static_cast<long long>(kBlock) * c->iters - 1) / (static_cast<long long>(kBlock) * c->iters));
 
   auto fail = [&](void) { lbm64_destroy(c); return 1; };

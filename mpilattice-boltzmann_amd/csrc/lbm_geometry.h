@@ -1,0 +1,89 @@
+// lbm_geometry.h — the numbers the kernels and the host agree on: block sizes, tile shapes, the steps a launch can make, the forms of
+// the sum|u| terms.  constexpr values and functions only: no device code, no HIP header, so that the host-only planning unit
+// (lbm_plan.cpp) and the device units (kernels/*.h) read one definition.  Not part of the ABI.
+#pragma once
+
+namespace {
+
+// ---- every kernel (kernels/common.h) ----
+constexpr int kBlock = 256;          // 4 wavefronts
+constexpr int kCellsPerLane = 4;     // one 16-byte access per population per lane
+constexpr int kHaloGuard = 4;        // floats of guard on each side of a halo-buffer row
+
+// TERMS: how the sum|u| term of a cell, sqrt((double)msq) * (double)rinv (:667), is formed.  Populations never depend on it.
+//   kTermsDouble (LBM_FLAG_EXACT_AVVELS; lbm_tile_kernel's default): in double precision, every term correctly
+//     rounded before the product: v_rsq_f64 + 9 double-precision instructions per CELL.
+//   kTermsCompensated (lbm_multi_kernel's default): without double-precision arithmetic.  The root as an unevaluated float
+//     sum s + c (s = msq * rsq(msq); c = the Newton correction of s from the residual msq - s*s, which a fused multiply-add
+//     delivers exactly), the product with rinv as p + lo (p = s * rinv, its rounding error by another fused multiply-add,
+//     plus c * rinv): relative error ~2^-44 per cell where the double form has 2^-53 — av_vels, a float, comes out bit for
+//     bit the same in every test here — in 7 packed float instructions and two v_rsq_f32 per PAIR.  Only p is widened per
+//     pair; the lo parts are summed per lane in float (a lane adds at most a few per launch) and widened once.  Why it
+//     matters: the launch runs AT the socket power limit (scripts/power_trace.py: 1380 of 1400 W, shader clock 2.2 of
+//     2.4 GHz); double-precision instructions it does not execute come back as clock.  A cell at rest (msq = 0) gives 0:
+//     the rsq argument is held at the smallest normal number.  msq = inf (a diverged run) gives NaN where the reference
+//     gives inf.
+//   kTermsFloat (LBM_FLAG_FAST_AVVELS): v_sqrt_f32 and one multiply; av_vels then agrees to ~1e-7 (an ulp of its float).
+// kTermsFused added to one of them (LBM_FLAG_FUSED_ARITH): the same terms from the msq and rinv of the fused arithmetic (relax_core).
+constexpr int kTermsDouble = 0, kTermsFloat = 1, kTermsCompensated = 2, kTermsFused = 4;
+
+// ---- lbm_tile_kernel (kernels/tile.h): most steps of one launch, the ghost ring of its widest geometry ----
+constexpr int kMaxTileSteps = 8;
+
+// ---- the end-of-run fold (kernels/aux.h): blocks per step vector of lbm_fold_slices_kernel ----
+constexpr int kFoldSlices = 64;
+
+// ---- the double-precision one-step kernel (kernels/step64.h) ----
+constexpr int kPairCells = 2;        // one 16-byte access per population per lane
+
+// ---- lbm_multi_kernel (kernels/multi.h) ----
+#ifndef LBM_MTY            // experiment builds: -DLBM_MTY=24 -DLBM_MLANES=768 (taller tiles, two blocks per CU)
+#define LBM_MTY 16
+#define LBM_MLANES 512
+#endif
+#ifndef LBM_MWAVES         // most waves per SIMD the kernels are compiled for (register budget 512 / LBM_MWAVES)
+#define LBM_MWAVES 6
+#endif
+#ifndef LBM_MTY4           // tile height of the 4-step instantiation, standard and narrow geometry (512 lanes)
+#define LBM_MTY4 13
+#endif
+#ifndef LBM_MTY4T          // tile height and block size of the 4-step instantiation, tall geometry
+#define LBM_MTY4T 24
+#define LBM_MLANES4T 768
+#endif
+constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY4Tall = LBM_MTY4T, kMLanes = LBM_MLANES, kMLanes4Tall = LBM_MLANES4T,
+              kMaxMultiSteps = 4,
+              kMaxGhost = 32,      // most ghost rows / columns a K-step partition keeps per side: the steps of a group of launches between two halo exchanges (32: column blocks)
+              kMaxGroup = 8;       // most launches of such a group
+constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall) : (kMTY4 < kMTY4Tall ? kMTY4 : kMTY4Tall);
+// Geometry of a launch: tile width, and by steps per launch tile height and block size.
+//   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4: 64 x 13 (72 x 19 frame,
+//                49.0 KB, three blocks per CU).
+//   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24 waves);
+//                the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.
+//   kGeomNarrow  32-wide tiles, heights as kGeomStd: partitions so small that a launch is one round of blocks (twice the tiles, each
+//                with half the dependent work — a 1024 x 128-row partition keeps 256 CUs busy instead of 128).
+// The measurements behind each choice, round by round: DESIGN_APPENDIX.md R8.1.
+constexpr int kGeomStd = 0, kGeomNarrow = 1, kGeomTall = 2;
+constexpr int geom_tx(int g) { return g == kGeomNarrow ? kMTXNarrow : kMTX; }
+constexpr int multi_ty(int k, int g) { return k >= 4 ? (g == kGeomTall ? kMTY4Tall : kMTY4) : kMTY; }
+constexpr int multi_lanes(int k, int g) { return (k >= 4 && g == kGeomTall) ? kMLanes4Tall : kMLanes; }
+constexpr int geom_for(int k, int g) { return (g == kGeomTall && k < 4) ? kGeomStd : g; }      // the instantiation a launch of k steps uses
+
+// Sub-step j of k (1-based) works on the owned tile grown by (k-j) rows and multi_ex(k-j) = 2 ceil((k-j)/2)
+// columns on each side: the column growth is rounded up to even so that every region starts on an even x
+// and a lane can own an x-PAIR of cells (8-byte accesses; the two cells' arithmetic is packed by the
+// compiler into v_pk_*_f32, which halves the instruction count - the one-cell form of this kernel was
+// VALU-bound).  Where k-j is odd the region's outermost column lies outside every owned cell's dependency
+// cone: it is computed from whatever the frame holds there (stale values of an earlier sub-step, always
+// inside the frame) and never kept or counted.  (Rounds 1 - 4 grew the columns by 2(k-j): K = 4 regions
+// 76 / 72 / 68 / 64 wide instead of 72 / 68 / 68 / 64, frames 12 columns wider than needed.)
+constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
+
+// PART of lbm_multi_kernel (the forms themselves: kernels/multi.h): kPartPlain (whole periodic grids, and the launches of a partition that
+// compute its owned rows only), kPartGhost (a launch that also computes ghost rows: the counted test), kPartReady (owned rows only + the
+// ready words in the fold block), kPartTile (every launch of a rank of the 2-D decomposition: ghost rows AND ghost columns — the counted
+// and kept tests in x as well, in the tiles on the rim of the owned block only — and four ready words).
+constexpr int kPartPlain = 0, kPartGhost = 1, kPartReady = 2, kPartTile = 3;
+
+}  // namespace

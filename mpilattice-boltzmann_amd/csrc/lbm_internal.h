@@ -1,11 +1,74 @@
-// lbm_internal.h — shared between the host (lbm_host.cpp) and device (lbm_kernels.hip) halves of
-// liblbm_d2q9.so.  Not part of the ABI.
+// lbm_internal.h — shared between the host-only (lbm_host.cpp, lbm_plan.cpp) and device (lbm_kernels.hip, lbm_f64.hip)
+// units of liblbm_d2q9.so.  Not part of the ABI.
 #pragma once
+#include <cstddef>
 #include <string>
+
+#include "lbm_d2q9.h"
+#include "lbm_knobs.h"
 
 namespace lbm_internal {
 // Sets the calling thread's lbm_last_error() message.
 void set_error(const std::string& msg);
+
+// ---- lbm_plan.cpp: what a context is, decided before anything is allocated ----------------------------------------------------
+// Everything lbm_create* decides that does not depend on a device pointer, written once by plan_whole / plan_rank / plan_tile and
+// only read afterwards (lbm_ctx::plan).  Plain data in this order — tests/test_plan.py mirrors it field for field and refuses a
+// library whose lbm_plan_sizeof() differs; flags that were bool in the context are 0 / 1 here.
+struct ContextPlan {
+  // the domain: storage row width (a tile rank's: owned + ghost columns), first owned row, owned rows, the LBM_FLAG_* of the context
+  int nx, y0, nyl;
+  unsigned flags;
+  int self_periodic, accel_row;      // a whole periodic grid; row ny-2 in owned-row coordinates (-1: another rank's)
+  int use_graph;                     // LBM_FLAG_GRAPH on a whole grid: hipGraph replay of the one-step launches
+  float accel_w1, accel_w2, free_cells_inv;
+  // K-step mode
+  int multi_K;                       // > 0: advanced K steps per launch by lbm_multi_kernel<K>
+  int ghost;                         // steps between two halo exchanges of a K-step partition (0: not one)
+  int ghost_rows;                    // storage rows kept below / above the owned rows: `ghost`, or 0 for a tile rank that owns ALL rows (a column
+                                     // block, py = 1), whose launches wrap in y as a whole grid's do: only columns are exchanged
+  int group_max;                     // most launches a partitioned run makes per halo exchange (a group: their steps add up to <= ghost)
+  // Tile (2-D) decomposition: the rank owns the columns [x0, x0 + nxl) of its rows as well.  Its storage rows hold ghost_x ghost columns on
+  // each side and nx is THEIR width (nxl + 2 * ghost_x): kernels, masks and row arithmetic all work on storage rows; nx_global is the
+  // grid's.  Everywhere else ghost_x = 0, nxl = nx_global = nx.
+  int ghost_x, x0, nxl, nx_global, tiles_px, tiles_py, tile_rx, tile_ry;
+  // sizes, in cells / floats / words
+  long long ncells, ncells_storage, ps, grid_floats;   // owned cells; cells incl. ghost rows; plane stride; one grid's allocation
+  int mask_words, nxp;               // obstacle bitfield; halo-buffer row (nx + guards): a halo message is 3 of them
+  // the one-step kernels
+  int nt_stores, lane_cells;         // non-temporal stores; cells per lane: 4 (vector form) or 1 (narrow form: tiny grids, nx % 4 != 0)
+  // arithmetic
+  int fast_avvels;                   // LBM_FLAG_FAST_AVVELS: float sum|u| terms in lbm_multi_kernel / lbm_tile_kernel
+  int fused;                         // LBM_FLAG_FUSED_ARITH: every launch takes the fused instantiation of its kernel
+  int multi_terms;                   // lbm_multi_kernel's form of the terms (kTerms*): LBM_FLAG_FAST_AVVELS / LBM_FLAG_EXACT_AVVELS
+  int multi_tail4;                   // lbm_run at K = 3: 4-step launches instead of a 1- or 2-step tail (LBM_TUNE_MULTI_TAIL4)
+  // lbm_tile_kernel: owned tile edge, ghost ring = max steps per launch; sub-steps with regions of at most tile_single_max cells deal one
+  // cell per lane; tile_kernel: lbm_run advances several steps per launch with it (small whole grids)
+  int tile_T, tile_H, tile_single_max, n_tiles, tile_kernel;
+  // lbm_multi_kernel's launches (kGeom*): standard, narrow (32-wide tiles), tall (K = 4 on 64 x 24); tile width; tiles per row
+  // (multi_tiles_x > 0: the context may launch it, and its kernels' LDS limit is raised)
+  int multi_geom, multi_tx, multi_tiles_x;
+  // the one-step launches: chunks per block and blocks (= partial sums) of the whole-grid, interior and boundary launch; room for the
+  // partial sums of the longest launch of any kernel
+  int iters_full, iters_interior, n_part_full, n_part_interior, n_part_boundary, partials_cap;
+  // packed messages of a K-step partition, in floats: one row message, one column message, one row-message buffer (both directions)
+  long long pack_floats, pack_floats_x, pack_alloc_floats;
+};
+static_assert(sizeof(ContextPlan) == 44 * sizeof(int) + 7 * sizeof(long long), "no padding: the order above is the layout");
+
+enum { kPlanOk = 0, kPlanRefused = 1, kPlanRefusedLate = 2 };   // Late: lbm_create* checked it after hipSetDevice, whose failure reports first
+// One per way of creating a context: lbm_create / lbm_create_global, lbm_create_rank (by way of the row layout), lbm_create_tile (by
+// way of the tile layout).  On a refusal lbm_last_error() holds the message.
+int plan_whole(const Knobs& knobs, const lbm_params* p, int free_cells, int y0, int ny_local, unsigned flags, bool has_global_map, ContextPlan* out);
+int plan_rank(const Knobs& knobs, const lbm_params* p, int free_cells, int nranks, int rank, unsigned flags, ContextPlan* out);
+int plan_tile(const Knobs& knobs, const lbm_params* p, int free_cells, int px, int py, int rank, unsigned flags, ContextPlan* out);
+enum KernelFamily { kFamilyMulti, kFamilyTile, kFamilyStep };
+KernelFamily family_of(const ContextPlan& plan);
+void plan_kernel_name(const ContextPlan& plan, char* kernel_name, size_t len);
+// Sizing rules the double-precision unit shares, stated in elements.
+size_t plane_stride_floats(size_t ncells, int skew);
+int pick_iters(long long quads, int max_blocks);
+int blocks_for(long long quads, int iters);
 }  // namespace lbm_internal
 
 // Steps of the next launch of the K-step kernels when `left` steps remain (lbm_host.cpp; lbm_plan_steps is its public
@@ -14,3 +77,9 @@ extern "C" int lbm_plan_next(int K, int four_rows, int tail4, int left);
 // The launches of the next group (one halo exchange) of a partitioned run; public form in lbm_d2q9.h (four_rows = ghost >= 4, tail4 on).
 extern "C" int lbm_plan_group_for(int K, int four_rows, int tail4, int ghost, int group_max, int left, int* steps, int cap);
 extern "C" int lbm_plan_group(int K, int ghost, int group_max, int left, int* steps, int cap);
+// The plan a context of these arguments would get, for tests (lbm_plan.cpp); the knobs are read from the environment per call.
+extern "C" int lbm_plan_sizeof(void);
+extern "C" int lbm_plan_whole(const lbm_params* p, int free_cells, int y0, int ny_local, unsigned flags, int has_global_map, lbm_internal::ContextPlan* out);
+extern "C" int lbm_plan_rank(const lbm_params* p, int free_cells, int nranks, int rank, unsigned flags, lbm_internal::ContextPlan* out);
+extern "C" int lbm_plan_tile(const lbm_params* p, int free_cells, int px, int py, int rank, unsigned flags, lbm_internal::ContextPlan* out);
+extern "C" int lbm_plan_kernel_name(const lbm_internal::ContextPlan* plan, char* kernel_name, size_t len);

@@ -177,9 +177,9 @@ int p2p_push_cols(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s)
   lbm_ctx* c = t->ctx;
   const P2PPeer& pw = t->peers[t->west];
   const P2PPeer& pe = t->peers[t->east];
-  const int g = c->cur, gx = c->ghost_x;
+  const int g = c->cur, gx = c->plan.ghost_x;
   P2PPushColsArgs a{};
-  a.src = c->grid[g]; a.ps = c->ps; a.src_w = c->p.nx;
+  a.src = c->grid[g]; a.ps = c->plan.ps; a.src_w = c->p.nx;
   // west neighbour: the first k of its EAST ghost columns; east neighbour: the last k of its west ghost columns (its rows are mine:
   // the same y0, the same ghost rows)
   a.dst[0] = pw.grid_alloc[g] + 64 + static_cast<size_t>(pw.blob.ghost_rows) * pw.blob.w + (pw.blob.ghost_x + pw.blob.nxl);
@@ -187,8 +187,8 @@ int p2p_push_cols(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s)
   a.dst_ps[0] = pw.blob.ps; a.dst_ps[1] = pe.blob.ps;
   a.dst_w[0] = pw.blob.w; a.dst_w[1] = pe.blob.w;
   a.src_col[0] = gx;                    // my first k owned columns
-  a.src_col[1] = gx + c->nxl - k;       // my last k owned columns
-  a.row0 = c->ghost_rows; a.nrows = c->nyl; a.k = k;
+  a.src_col[1] = gx + c->plan.nxl - k;       // my last k owned columns
+  a.row0 = c->plan.ghost_rows; a.nrows = c->plan.nyl; a.k = k;
   a.flag[0] = &header_of(pw.window)->halo_flag_x[1];      // my columns arrive from the west neighbour's EAST
   a.flag[1] = &header_of(pe.window)->halo_flag_x[0];
   a.parity_word[0] = &header_of(pw.window)->halo_parity_x[2 * 1 + (epoch & 1ull)];
@@ -199,11 +199,11 @@ int p2p_push_cols(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s)
   a.wait_parity = header_of(t->window)->halo_parity_x;
   a.timeout_ticks = t->timeout_ticks; a.err = t->err;
   auto all_mult = [&](int m) {
-    return k % m == 0 && gx % m == 0 && c->nxl % m == 0 && c->p.nx % m == 0 && c->ps % m == 0 && pw.blob.w % m == 0 && pe.blob.w % m == 0 &&
+    return k % m == 0 && gx % m == 0 && c->plan.nxl % m == 0 && c->p.nx % m == 0 && c->plan.ps % m == 0 && pw.blob.w % m == 0 && pe.blob.w % m == 0 &&
            pw.blob.ps % m == 0 && pe.blob.ps % m == 0 && pw.blob.nxl % m == 0 && pw.blob.ghost_x % m == 0 && pe.blob.ghost_x % m == 0;
   };
   const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
-  const int work = 18 * c->nyl * (k / per);
+  const int work = 18 * c->plan.nyl * (k / per);
   const dim3 grid(std::max(1, std::min(kP2PPushBlocks, (work + 1023) / 1024)));
   if (per == 4) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f4>, grid, dim3(256), 0, s, a);
   else if (per == 2) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f2>, grid, dim3(256), 0, s, a);
@@ -216,21 +216,21 @@ int p2p_push(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s, bool ex
 {
   lbm_ctx* c = t->ctx;
   if (t->tiles && p2p_push_cols(t, epoch, k, s)) return 1;
-  if (c->ghost_rows == 0) return 0;      // a column block (px x 1 tiling): its rows wrap inside the launch, the column push is the whole exchange
+  if (c->plan.ghost_rows == 0) return 0;      // a column block (px x 1 tiling): its rows wrap inside the launch, the column push is the whole exchange
   const P2PPeer& ps = t->peers[t->south];
   const P2PPeer& pn = t->peers[t->north];
   const int nx = c->p.nx, g = c->cur;
   P2PPushArgs a{};
   a.src = c->grid[g];
-  a.ps = c->ps;
+  a.ps = c->plan.ps;
   // south neighbour: the first k of its TOP ghost rows (storage row ghost + nyl of ITS layout); north neighbour: the
   // last k of its bottom ghost rows (storage rows ghost - k .. ghost - 1)
   a.dst[0] = ps.grid_alloc[g] + 64 + static_cast<size_t>(ps.blob.ghost_rows + ps.blob.nyl) * nx;
   a.dst[1] = pn.grid_alloc[g] + 64 + static_cast<size_t>(pn.blob.ghost_rows - k) * nx;
   a.dst_ps[0] = ps.blob.ps;
   a.dst_ps[1] = pn.blob.ps;
-  a.src_row[0] = static_cast<size_t>(c->ghost_rows);             // my first k owned rows
-  a.src_row[1] = static_cast<size_t>(c->ghost_rows + c->nyl - k);   // my last k owned rows
+  a.src_row[0] = static_cast<size_t>(c->plan.ghost_rows);             // my first k owned rows
+  a.src_row[1] = static_cast<size_t>(c->plan.ghost_rows + c->plan.nyl - k);   // my last k owned rows
   a.nfloats = k * nx;
   a.flag[0] = &header_of(ps.window)->halo_flag[1];       // my rows arrive from the south neighbour's NORTH
   a.flag[1] = &header_of(pn.window)->halo_flag[0];
@@ -243,7 +243,7 @@ int p2p_push(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s, bool ex
   a.wait_parity = header_of(t->window)->halo_parity;
   a.timeout_ticks = t->timeout_ticks;
   a.err = t->err;
-  const bool wide = nx % 4 == 0 && ps.blob.ps % 4 == 0 && pn.blob.ps % 4 == 0 && c->ps % 4 == 0;    // 16-byte accesses (rows and planes 16-byte aligned on both sides)
+  const bool wide = nx % 4 == 0 && ps.blob.ps % 4 == 0 && pn.blob.ps % 4 == 0 && c->plan.ps % 4 == 0;    // 16-byte accesses (rows and planes 16-byte aligned on both sides)
   const int work = 18 * (a.nfloats / (wide ? 4 : 2));
   // at most 64 blocks (every block ends with an L2 write-back towards the peers), each lane moving up to four
   // float2's per pass
@@ -320,7 +320,7 @@ int p2p_run_one_step(lbm_p2p* t, int n_steps, double* tot_u_per_step)
 {
   lbm_ctx* c = t->ctx;
   hipStream_t cs = t->compute;
-  const int nxp = c->nxp;
+  const int nxp = c->plan.nxp;
   P2PPeer& ps = t->peers[t->south];
   P2PPeer& pn = t->peers[t->north];
   auto bind = [&](unsigned long long e_recv, unsigned long long e_send) {
@@ -376,7 +376,7 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
 {
   if (!out || !ctx || nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks) { lbm_internal::set_error("lbm_p2p_create: bad argument (1..64 ranks)"); return 1; }
   *out = nullptr;
-  if (ctx->self_periodic) {
+  if (ctx->plan.self_periodic) {
     lbm_internal::set_error("lbm_p2p_create: the context is a self-contained periodic domain (create it with lbm_create_rank, or with LBM_FLAG_FORCE_HALO)");
     return 1;
   }
@@ -388,8 +388,8 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   t->rank = rank;
   t->south = (rank + nranks - 1) % nranks;   // `top`    d2q9-bgk.c:245-246
   t->north = (rank + 1) % nranks;            // `bottom` d2q9-bgk.c:247
-  if (ctx->ghost_x > 0) {                    // tile decomposition: rank = ry * px + rx, periodic in both directions
-    const int px = ctx->tiles_px, py = ctx->tiles_py, rx = ctx->tile_rx, ry = ctx->tile_ry;
+  if (ctx->plan.ghost_x > 0) {                    // tile decomposition: rank = ry * px + rx, periodic in both directions
+    const int px = ctx->plan.tiles_px, py = ctx->plan.tiles_py, rx = ctx->plan.tile_rx, ry = ctx->plan.tile_ry;
     if (nranks != px * py || rank != ry * px + rx) { lbm_internal::set_error("lbm_p2p_create: the context is rank " + std::to_string(ry * px + rx) + " of " + std::to_string(px * py) + " tiles"); delete t; return 1; }
     t->tiles = true;
     int nb[4];
@@ -402,12 +402,12 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   t->timeout_ticks = static_cast<long long>(knobs.p2p_timeout_ms) * 100000LL;   // wall_clock64: 100 MHz
   // default by size, as the RCCL loop: an own stream for the edge rows pays once the interior launch is long
   // enough to cover two cross-queue waits
-  t->edge_stream = ctx->ncells >= (size_t(1) << 21);
+  t->edge_stream = ctx->plan.ncells >= (size_t(1) << 21);
   // Tile ranks: the interior is the rectangle of tiles inside the rim of tile rows AND tile columns that read exchanged cells (macro_rects).
   // That rim is a round of blocks by itself (a 2048 x 4096 block: 422 of its 5874 tiles, 46 us) where a row block's is two tile rows, and the
   // exchange it hides is short (31 us per 8 steps): 1-rank rings, us/step serial / edge stream: 2048 x 4096 45.5 / 46.5, 4096 x 4096 82.0 / 82.4,
   // 4096 x 8192 158.0 / 155.5 (profiles/r04/tile_ring_*_{serial,edge_stream}.json) — from 2^25 cells up
-  if (t->tiles) t->edge_stream = ctx->ncells >= (size_t(1) << 25);
+  if (t->tiles) t->edge_stream = ctx->plan.ncells >= (size_t(1) << 25);
   if (knobs.p2p_schedule != kKnobUnset) t->edge_stream = knobs.p2p_schedule == kScheduleEdge;
   // beside the interior launch the push has a whole macro-step to finish, and every block of it takes a CU slot and
   // an L2 write-back away from that launch: us/step on a 1-rank ring of 8192 x 1024 rows for 8 / 12 / 16 / 32 / 64
@@ -431,7 +431,7 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   t->reduce_cap = static_cast<size_t>(std::max(ctx->p.max_iters, 4096));
   // (the one-step mode's halo slots; the reduce slots behind them must lie at the same offset in EVERY rank's window: tile ranks — always
   // K-step mode, storage rows of different widths where the column blocks are uneven — keep none)
-  t->halo_bytes = t->tiles ? 0 : round_up(sizeof(float) * 2 * 2 * 3 * static_cast<size_t>(ctx->nxp), 256);
+  t->halo_bytes = t->tiles ? 0 : round_up(sizeof(float) * 2 * 2 * 3 * static_cast<size_t>(ctx->plan.nxp), 256);
   t->window_bytes = kP2PHeaderBytes + t->halo_bytes + sizeof(double) * 2 * nranks * t->reduce_cap;
   // The protocol needs a window whose flags a running kernel sees change and whose one-step halo slots need no
   // cache maintenance on the reader's side: uncached, or fine-grained as the fall-back.  Ordinary (coarse-grained)
@@ -473,10 +473,10 @@ int lbm_p2p_handle(lbm_p2p* t, void* blob_out)
   P2PBlob b{};
   b.magic = kP2PMagic; b.version = LBM_ABI_VERSION;
   b.pid = static_cast<int32_t>(getpid()); b.device = c->device; b.nranks = t->nranks; b.rank = t->rank;
-  b.nx = c->nx_global; b.ny = c->p.ny; b.y0 = c->y0; b.nyl = c->nyl; b.ghost = c->ghost; b.K = c->multi_K; b.cur = c->cur; b.group = c->group_max;
-  b.ghost_rows = c->ghost_rows;
-  b.w = c->p.nx; b.x0 = c->x0; b.nxl = c->nxl; b.ghost_x = c->ghost_x; b.px = t->tiles ? c->tiles_px : 1; b.py = t->tiles ? c->tiles_py : t->nranks;
-  b.ps = c->ps; b.window_bytes = t->window_bytes; b.reduce_cap = t->reduce_cap;
+  b.nx = c->plan.nx_global; b.ny = c->p.ny; b.y0 = c->plan.y0; b.nyl = c->plan.nyl; b.ghost = c->plan.ghost; b.K = c->plan.multi_K; b.cur = c->cur; b.group = c->plan.group_max;
+  b.ghost_rows = c->plan.ghost_rows;
+  b.w = c->p.nx; b.x0 = c->plan.x0; b.nxl = c->plan.nxl; b.ghost_x = c->plan.ghost_x; b.px = t->tiles ? c->plan.tiles_px : 1; b.py = t->tiles ? c->plan.tiles_py : t->nranks;
+  b.ps = c->plan.ps; b.window_bytes = t->window_bytes; b.reduce_cap = t->reduce_cap;
   // IPC handles serve peers in OTHER processes; contexts of one process use the raw pointers, so a
   // runtime that cannot export a handle only rules out the multi-process form (checked at connect)
   b.ipc_ok = 1;
@@ -515,12 +515,12 @@ int lbm_p2p_connect(lbm_p2p* t, const void* blobs)
       lbm_internal::set_error("lbm_p2p_connect: handle " + std::to_string(r) + " is not rank " + std::to_string(r) + " of this run");
       return 1;
     }
-    if (b.nx != c->nx_global || b.ny != c->p.ny || b.K != c->multi_K || b.ghost != c->ghost || b.group != c->group_max || b.cur != c->cur || b.reduce_cap != t->reduce_cap ||
-        b.ghost_x != c->ghost_x || b.ghost_rows != c->ghost_rows || b.px != (t->tiles ? c->tiles_px : 1) || b.py != (t->tiles ? c->tiles_py : t->nranks)) {
+    if (b.nx != c->plan.nx_global || b.ny != c->p.ny || b.K != c->plan.multi_K || b.ghost != c->plan.ghost || b.group != c->plan.group_max || b.cur != c->cur || b.reduce_cap != t->reduce_cap ||
+        b.ghost_x != c->plan.ghost_x || b.ghost_rows != c->plan.ghost_rows || b.px != (t->tiles ? c->plan.tiles_px : 1) || b.py != (t->tiles ? c->plan.tiles_py : t->nranks)) {
       lbm_internal::set_error("lbm_p2p_connect: rank " + std::to_string(r) + " runs a different layout (nx " + std::to_string(b.nx) + ", ny " +
                               std::to_string(b.ny) + ", K " + std::to_string(b.K) + ", " + std::to_string(b.ghost) + " ghost rows, " + std::to_string(b.group) +
-                              " launches per exchange) than rank " + std::to_string(t->rank) + " (K " + std::to_string(c->multi_K) + ", " + std::to_string(c->ghost) +
-                              ", " + std::to_string(c->group_max) + "): create every rank with lbm_create_rank");
+                              " launches per exchange) than rank " + std::to_string(t->rank) + " (K " + std::to_string(c->plan.multi_K) + ", " + std::to_string(c->plan.ghost) +
+                              ", " + std::to_string(c->plan.group_max) + "): create every rank with lbm_create_rank");
       return 1;
     }
     if (std::strncmp(b.host, host, sizeof host) != 0) {
@@ -529,7 +529,7 @@ int lbm_p2p_connect(lbm_p2p* t, const void* blobs)
     }
     cells += static_cast<long long>(b.nyl) * b.nxl;
   }
-  if (cells != static_cast<long long>(c->p.ny) * c->nx_global) { lbm_internal::set_error("lbm_p2p_connect: the ranks' blocks do not add up to the grid"); return 1; }
+  if (cells != static_cast<long long>(c->p.ny) * c->plan.nx_global) { lbm_internal::set_error("lbm_p2p_connect: the ranks' blocks do not add up to the grid"); return 1; }
   for (int r = 0; r < t->nranks; ++r) {
     P2PPeer& p = t->peers[r];
     const P2PBlob& b = p.blob;
@@ -573,7 +573,7 @@ int lbm_p2p_connect(lbm_p2p* t, const void* blobs)
   }
   // the edge stream exists only where the schedule uses it: every stream takes a share of the process's few
   // hardware queues, and ranks of one process on one device must not share a queue (see above)
-  if (c->ghost == 0) t->edge_stream = false;               // one-step mode runs on the compute stream
+  if (c->plan.ghost == 0) t->edge_stream = false;               // one-step mode runs on the compute stream
   if (t->edge_stream && !t->edge) HIP_TRY(hipStreamCreateWithFlags(&t->edge, hipStreamNonBlocking));
   // device tables for the reduce kernels: where my sums go in every rank's window, and my flag there
   std::vector<double*> slots(static_cast<size_t>(2) * t->nranks);
@@ -639,7 +639,7 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
   t->ev_used = 0;
   t->phases_valid = false;
   t->ev_reduce_end = nullptr;
-  if (c->ghost == 0) return p2p_run_one_step(t, n_steps, tot_u_per_step);
+  if (c->plan.ghost == 0) return p2p_run_one_step(t, n_steps, tot_u_per_step);
   hipStream_t cs = t->compute, es = t->edge_stream ? t->edge : t->compute;
   // error exits leave both streams drained: events recorded on one may be pending on the other
   auto bail = [&]() {
@@ -741,8 +741,8 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
       if (t->edge_stream) {
         // the rows to push are the last launch's: its edge rows when the group was one launch and those tile rows hold all
         // next.total rows of either side (then the push need not wait for the interior launch); else the compute stream's
-        const bool edge_rows_suffice = g.n == 1 && !t->tiles && (c->ghost_rows - g.ext(0)) + rows.bottom_edge_rows * multi_ty(g.k[0], c->multi_geom) >= c->ghost_rows + next.total &&
-                                       (c->ghost_rows - g.ext(0)) + (rows.bottom_edge_rows + rows.interior_rows) * multi_ty(g.k[0], c->multi_geom) <= c->ghost_rows + c->nyl - next.total;
+        const bool edge_rows_suffice = g.n == 1 && !t->tiles && (c->plan.ghost_rows - g.ext(0)) + rows.bottom_edge_rows * multi_ty(g.k[0], c->plan.multi_geom) >= c->plan.ghost_rows + next.total &&
+                                       (c->plan.ghost_rows - g.ext(0)) + (rows.bottom_edge_rows + rows.interior_rows) * multi_ty(g.k[0], c->plan.multi_geom) <= c->plan.ghost_rows + c->plan.nyl - next.total;
         if (!edge_rows_suffice) { P2P_RUN_TRY(hipStreamWaitEvent(es, t->interior_done, 0)); es_has_waited = true; }
       }
       P2PSpan sp;
@@ -823,15 +823,15 @@ int lbm_p2p_describe(const lbm_p2p* t, char* text, size_t len)
     if (t->tiles) ipc = ipc || (t->connected && (t->peers[t->west].ipc || t->peers[t->east].ipc));   // (a 2 x 1 grid: north and south are the rank itself)
     reach = ipc ? "ipc" : "in-process";
   }
-  if (t->ctx->ghost == 0) {
+  if (t->ctx->plan.ghost == 0) {
     std::snprintf(text, len, "window %s; neighbours %s; one-step mode", t->window_kind, reach);
     return 0;
   }
   int n = std::snprintf(text, len, "window %s; neighbours %s; schedule %s; K %d; ghost rows %d; launches per exchange %d", t->window_kind, reach,
-                        t->edge_stream ? "edge stream" : "serial", t->ctx->multi_K, t->ctx->ghost, t->ctx->group_max);
+                        t->edge_stream ? "edge stream" : "serial", t->ctx->plan.multi_K, t->ctx->plan.ghost, t->ctx->plan.group_max);
   if (t->tiles && n > 0 && static_cast<size_t>(n) < len)
-    std::snprintf(text + n, len - n, "; tiles %d x %d; ghost columns %d%s", t->ctx->tiles_px, t->ctx->tiles_py, t->ctx->ghost_x,
-                  t->ctx->ghost_rows == 0 ? "; rows wrap in the launch" : "");
+    std::snprintf(text + n, len - n, "; tiles %d x %d; ghost columns %d%s", t->ctx->plan.tiles_px, t->ctx->plan.tiles_py, t->ctx->plan.ghost_x,
+                  t->ctx->plan.ghost_rows == 0 ? "; rows wrap in the launch" : "");
   return 0;
 }
 

@@ -1,0 +1,520 @@
+// lbm_plan.cpp — the host-only planning unit of liblbm_d2q9.so: which kernel, which geometry and which buffer sizes a context
+// gets.  No HIP call and no device pointer anywhere in this file, so every rule here can be read, called and tested on a CPU
+// (tests/test_plan.py, through the lbm_plan_* exports at the end).
+//
+//   the rules        macro_eligible, macro_k_for, macro_ghost_for, macro_group_for, pick_geom, plane_stride_floats, pick_iters,
+//                    blocks_for — each with the measurements behind it
+//   the layouts      rank_layout (row blocks), tile_layout_of (tiles), lbm_choose_rank_grid (which of the two): one answer for all
+//                    ranks of a run, from global quantities only
+//   the plan         plan_context fills a ContextPlan (lbm_internal.h): everything lbm_create* decides that does not depend on
+//                    a device pointer.  plan_whole / plan_rank / plan_tile are its three callers, one per way of creating a
+//                    context; lbm_kernels.hip allocates, uploads and launches by the plan and never writes it
+//   the names        family_of(plan) and plan_kernel_name(plan): the only place the kernel families' names are spelled
+//
+// Refusals keep the words and the order lbm_create* always had: what was checked before the device was touched returns
+// kPlanRefused, what was checked after it kPlanRefusedLate (the caller lets a bad device speak first).
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "lbm_d2q9.h"
+#include "lbm_geometry.h"
+#include "lbm_internal.h"
+#include "lbm_knobs.h"
+
+using lbm_internal::ContextPlan;
+using lbm_internal::set_error;
+
+namespace lbm_internal {
+
+// Plane stride, in elements (floats here, doubles in lbm_f64.hip: the same rule): rows*nx elements + guard for the dword-shifted loads at both ends, rounded to 64 elements (256 B of floats),
+// then skewed by an odd number of such units so the 9 planes (and the two grids) do not all start
+// on the same HBM channel when rows*nx is a large power of two.
+size_t plane_stride_floats(size_t ncells, int skew)
+{
+  size_t s = (ncells + 64 + 63) / 64 * 64;
+  if ((s / 64) % 2 == 0) s += 64;
+  // Skew between planes for large grids (planes of 8192 x 8192 floats are 2^28 bytes: nine streams on the same channels without one).
+  // 24 x 256 B = 6 KiB.  Rounds 1-2 used 34 (tuned on the K = 3 launch, 64 x 16 tiles); scanned again on the K = 4 launch on 64 x 23 tiles,
+  // 8192 x 8192, us/step for skews 0 / 8 / 16 / 24 / 33 / 34 / 40 / 48 / 68: K = 4 286.7 / 284.6 / 285.8 / 284.7 / 314.3 / 307.8 & 295.3 / 289.0 /
+  // 285.1 / 286.6; K = 3 (the tails) 384.6 & 329.5 / 341.1 / 324.0 / 317.9 / 339.8 / 339.7 & 348.5 / 323.5 / 335.4 / 333.7 — 33 and 34 are the
+  // two bad values for the tall tiles, 24 is best for both; other sizes (4096 x 4096 ... 16384 x 4096, partitions) do not care
+  // (profiles/r03/ab_skew_scan.txt, ab_skew_sizes.txt).
+  if (ncells >= (1u << 20)) s += 64 * static_cast<size_t>(skew);
+  return s;
+}
+
+// max_blocks (LBM_TUNE_MAXBLOCKS): measured on 8192x8192, 16384 blocks x 4 chunks ~7 % faster than 4096 x 16
+int pick_iters(long long quads, int max_blocks)
+{
+  // keep the grid at <= ~4096 blocks (16 per CU): fewer, longer blocks and a short partial vector
+  long long chunks = (quads + kBlock - 1) / kBlock;
+  int iters = 1;
+  while (chunks / iters > max_blocks && iters < 1024) iters *= 2;
+  return iters;
+}
+
+int blocks_for(long long quads, int iters)
+{
+  const long long per_block = static_cast<long long>(kBlock) * iters;
+  return static_cast<int>((quads + per_block - 1) / per_block);
+}
+
+}  // namespace lbm_internal
+
+namespace {
+
+// What every launch of lbm_multi_kernel needs of the rows it works on, whole grid or partition: a plane addressed with 32-bit byte
+// offsets (< 2^30 storage cells, the deepest ghost rows included) and 24-bit row multiplies (nx < 2^23).
+bool multi_addressable(int nx, int rows)
+{
+  return static_cast<size_t>(nx) * (rows + 2 * kMaxGhost) < (size_t(1) << 30) && nx < (1 << 23);
+}
+
+// Is a row partition of `rows` rows eligible for K-step mode (lbm_multi_kernel with ghost rows) ?  At least 32 rows, and rows of whole
+// 64-wide tiles or of any even width from 128 cells.
+bool macro_eligible(const lbm_params* p, int rows, unsigned flags)
+{
+  return !(flags & LBM_FLAG_ONE_STEP) && rows >= 2 * kMTY && multi_addressable(p->nx, rows) && (p->nx % kMTX == 0 || (p->nx % 2 == 0 && p->nx >= 2 * kMTX));
+}
+
+// Does lbm_multi_kernel tile a whole periodic grid ?  Grids tiled exactly by 64x16, or any even nx >= 128 with ny >= 32, where the last
+// tile column / row sticks out of the grid (periodic images: computed, not kept).  Not the partitions' rule: a whole grid of fewer than
+// 32 rows that 64 x 16 tiles exactly is taken.
+bool whole_grid_tiled(int nx, int ny)
+{
+  return multi_addressable(nx, ny) && ((nx % kMTX == 0 && ny % kMTY == 0) || (nx % 2 == 0 && nx >= 2 * kMTX && ny >= 2 * kMTY));
+}
+
+// K of the K-step partitions, whatever their size (LBM_TUNE_MACRO_K overrides).  Measured on a 1-rank ring with the packed exchange,
+// us/step for K = 2 / 3 / 4 (one-step loop):
+//   8192x4096 rows 243 / 182 / 199   8192x2048 rows 122 / 92.6 / 103   8192x1024 rows 66.2 / 52.5 / 55.9 (116)
+//   1024x128 rows 26.1 / 18.8 / 14.7 (37)
+// Round 3: with the 4-step launch on 64 x 13 tiles (three blocks per CU, kernels/multi.h) K = 4 wins at every size — 1-rank
+// p2p rings, us/step for K = 3 / K = 4: 8192x4096 178.9 / 166.2, 8192x1024 51.3 / 48.5, 1024x128 4.40 / 4.04.
+int macro_k_for(const Knobs& knobs)
+{
+  return std::min(std::max(knobs.macro_k, 0), kMaxMultiSteps);
+}
+
+// Ghost rows kept on each side of a K-step partition, and with them how often it exchanges: the launches between two exchanges (a
+// GROUP) make at most `ghost` steps together.  Round 4: the first launch of a group also advances `ext` = (steps of the later ones)
+// ghost rows on each side from the exchanged rows, so the later ones are launches over all tiles that read no exchanged row: no
+// interior / edge split, no push, no wait, no join.  Rounds 1-3 kept K rows (4 at K = 3) and exchanged before every launch.
+//   partitions that run the edge-stream schedule (>= 2 M cells): 2 K rows (8 at K = 3: 3 + 4, 4 + 4, 3 + 3), two launches per exchange —
+//     1-rank ring of 8192 x 1024 rows, us/step at 20 / 200 steps per run for K, 8, 12, 16 rows: 48.1 / 45.7, 46.8 / 43.8, 46.5 / 43.7, 47.2 / 43.9
+//     (profiles/r04/rings_p2p_final_build.txt: past two launches per exchange nothing more is gained, so the fewest ghost rows stay);
+//   smaller ones (everything on one stream: each exchange is an exposed push + wait): as deep as their rows carry — 16 rows (four
+//     launches per exchange) from 128 rows per rank, 8 from 64, K below (a 32-row rank would compute 56 rows in a group's first launch) —
+//     1024 x 128 rows: 4.85 (K rows), 4.23 (8), 3.85 (12), 3.84 (16) us/step at 200 steps, 6.40 / 6.12 / 5.87 / 5.65 at 20
+//     (profiles/r04/rings_p2p_small.txt; with the neighbours' "ready" awaited inside the push kernel, by every block or by block 0 with a
+//     go word for the rest, 8 rows were no faster than K: 4.95 - 5.76 — the wait now sits in the fold block of the group's last launch).
+// One answer for all ranks: from nx and the smallest / largest row count of the run.  LBM_TUNE_MACRO_GHOST overrides (0 or anything
+// below K: K rows, one launch per exchange).  The exchange moves the rows the NEXT group needs (peer-to-peer loop) or all `ghost`
+// rows (RCCL loop).
+int macro_ghost_for(const Knobs& knobs, int k, int nx, int rows_min, int rows_max, bool row_blocks = true)
+{
+  if (k <= 0) return 0;
+  const int classic = k == 3 ? 4 : k, two = k == 3 ? 8 : 2 * k;
+  int by_size = two;
+  if (static_cast<size_t>(nx) * rows_max < (size_t(1) << 21)) by_size = rows_min >= 128 ? std::max(16 / k * k, two) : rows_min >= 64 ? two : classic;
+  // ... and deeper still for the smallest ranks (round 4, last: kMaxGhost 16 -> 32), whose launches are bound by latency, not by the rows they
+  // compute: us/step for 16 / 24 / 32 ghost rows — 1024 x 128 rows 3.30 / 3.14 / 3.10, 1024 x 256 3.97 / 3.82 / 3.76, 512 x 512 3.86 / 3.70 / 3.63,
+  // 2048 x 256 5.50 / 5.40 / 5.33; not for wider or larger ones: 4096 x 128 6.03 / 6.18 / 6.22, 8192 x 128 10.2 / 10.5 / 10.6, 2048 x 512 7.75 / 7.70 / 7.97,
+  // 1024 x 1024 7.4 / 7.3 / 7.4, and 1024 x 192 3.40 / 3.43 / 3.55 (profiles/r04/ab_row_block_ghost_depth.txt): 24 rows from 128 rows per rank, 32 from 256,
+  // for ranks of at most 2^19 cells in rows of at most 2048 cells
+  if (row_blocks && nx <= 2048 && static_cast<size_t>(nx) * rows_max <= (size_t(1) << 19) && rows_min >= 128)     // (tile ranks: lbm_tile_layout_of has its own rule)
+    by_size = std::max(by_size, std::min((rows_min >= 256 ? 32 : 24) / k * k, static_cast<int>(kMaxGhost)));
+  return std::min(std::max(knob_or(knobs.macro_ghost, by_size), k), kMaxGhost);
+}
+
+// Most launches per exchange: what the ghost rows allow (LBM_TUNE_MACRO_GROUP caps it; 1 = rounds 1-3's loop on any number of ghost rows).
+int macro_group_for(const Knobs& knobs, int k, int ghost)
+{
+  if (k <= 0) return 1;
+  return std::min(std::max(knob_or(knobs.macro_group, std::max(ghost / k, 1)), 1), kMaxGroup);
+}
+
+// Geometry of lbm_multi_kernel's launches by partition size.  Width: 64 x 16 tiles for the bandwidth-bound grids; 32 x 16 where 64 x 16
+// tiles would not even fill the chip once (256 CUs x 3 blocks), so that the launch is bound by one block's chain of
+// sub-steps: half the work per block, twice the blocks.  Measured us/step for 64 / 32 wide tiles (K = 3, one GPU):
+// 1024x128 3.22 / 2.53, 512x256 3.17 / 2.50, 512x512 3.42 / 3.44, 2048x256 4.94 / 5.05, 1024x1024 8.39 / 9.01.
+// LBM_TUNE_MULTI_TILE = 64 / 32 overrides the width; LBM_TUNE_MULTI_GEOM = 0 / 1 / 2 the whole choice.
+// The tall geometry (K = 4 on 64 x 24 tiles, 768-lane blocks, two per CU) from 2^20 cells up: where a launch is several rounds of
+// blocks it is 4 - 10 % faster, at one round or less its 512 slots lose to 768 (kernels/multi.h).
+// Row partitions (interior + edge launch per macro-step) follow the same rule.  Measured one ring per PROCESS, as ranks run (two rings in
+// one process can share a hardware queue, which made the tall geometry look 20 % worse in a same-process A/B): standard / tall, us/step
+// at 200 and 20 steps per run: 8192 x 1024 rows 46.5 / 45.5 and 48.2 / 48.1, 8192 x 2048 rows 86.9 / 82.4 and 88.9 / 84.2
+// (profiles/r03/ab_fused_schedule.txt).
+int pick_geom(const Knobs& knobs, size_t ncells)
+{
+  const int by_size = ncells <= static_cast<size_t>(knobs.narrow_tile_max) ? kMTXNarrow : kMTX;
+  const int t = knob_or(knobs.multi_tile, by_size);
+  int g = t == kMTXNarrow ? kGeomNarrow : ncells >= static_cast<size_t>(knobs.tall_tile_min) ? kGeomTall : kGeomStd;
+  if (knobs.multi_geom >= kGeomStd && knobs.multi_geom <= kGeomTall) g = knobs.multi_geom;
+  return g;
+}
+
+// One mode and one K for every rank of a run, from global quantities only (see the header).
+int rank_layout(const Knobs& knobs, const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
+{
+  if (!p || !out || nranks < 1 || rank < 0 || rank >= nranks) { set_error("lbm_rank_layout: bad argument"); return 1; }
+  if (p->nx < 1 || p->ny < 3 || p->ny < nranks) { set_error("lbm_rank_layout: grid too small for this many ranks"); return 1; }
+  std::vector<int> nyl(nranks), dis(nranks);
+  if (lbm_decompose(p->ny, nranks, nyl.data(), dis.data())) return 1;                 // d2q9-bgk.c:834-862
+  const int lo = *std::min_element(nyl.begin(), nyl.end()), hi = *std::max_element(nyl.begin(), nyl.end());
+  if (lo < 1) { set_error("lbm_rank_layout: a rank would own no rows"); return 1; }
+  out->y0 = dis[rank];
+  out->ny_local = nyl[rank];
+  out->macro_k = 0;
+  const bool partitioned = nranks > 1 || (flags & LBM_FLAG_FORCE_HALO);
+  if (partitioned && macro_eligible(p, lo, flags) && macro_eligible(p, hi, flags))
+    out->macro_k = macro_k_for(knobs);
+  out->ghost = macro_ghost_for(knobs, out->macro_k, p->nx, lo, hi);
+  out->group = macro_group_for(knobs, out->macro_k, out->ghost);
+  return 0;
+}
+
+// ---- tile (2-D) decomposition: px x py ranks, rank = ry * px + rx ------------------------------------------------------------
+// Rows by the reference's rule over py (d2q9-bgk.c:834-862), columns by lbm_decompose_columns over px.  Always K-step mode: ghost rows
+// as a row partition of the same cells would keep, ghost columns the same number rounded up to even (x-pairs).
+int tile_layout_of(const Knobs& knobs, const lbm_params* p, int px, int py, int rank, unsigned flags, lbm_tile_layout* out)
+{
+  if (!p || !out || px < 1 || py < 1 || rank < 0 || rank >= px * py) { set_error("lbm_tile_layout_of: bad argument"); return 1; }
+  if (p->nx < 1 || p->ny < 3 || p->ny < py) { set_error("lbm_tile_layout_of: grid too small for this many ranks"); return 1; }
+  std::vector<int> nyl(py), ydis(py), nxl(px), xdis(px);
+  if (lbm_decompose(p->ny, py, nyl.data(), ydis.data())) return 1;
+  if (lbm_decompose_columns(p->nx, px, nxl.data(), xdis.data())) return 1;
+  const int rlo = *std::min_element(nyl.begin(), nyl.end()), rhi = *std::max_element(nyl.begin(), nyl.end());
+  const int clo = *std::min_element(nxl.begin(), nxl.end()), chi = *std::max_element(nxl.begin(), nxl.end());
+  if (rlo < 1) { set_error("lbm_tile_layout_of: a rank would own no rows"); return 1; }
+  std::memset(out, 0, sizeof *out);
+  out->px = px; out->py = py; out->rx = rank % px; out->ry = rank / px;
+  out->x0 = xdis[out->rx]; out->nx_local = nxl[out->rx];
+  out->y0 = ydis[out->ry]; out->ny_local = nyl[out->ry];
+  const int k = macro_k_for(knobs);
+  int ghost = macro_ghost_for(knobs, k, chi, rlo, rhi, /*row_blocks=*/false);
+  // Column blocks (py = 1) below the edge-stream size: 32 ghost columns, eight launches per exchange.  Their ghost depth costs columns only (no
+  // launch advances ghost rows), and their launches are bound by latency, not by the cells they compute: us/step for 16 / 24 / 32 ghost columns
+  // 2048 x 512 8.05 / 8.00 / 7.85, 4096 x 256 8.40 / 8.21 / 8.18, 8192 x 128 8.77 / 8.58 / 8.46, 512 x 512 4.06 / 3.96 / 3.87, 256 x 512 3.32 / 3.20 / 3.14
+  // (profiles/r04/ab_column_block_ghost_depth.txt).  LBM_TUNE_MACRO_GHOST still overrides.
+  if (k > 0 && py == 1 && clo >= 256 && !knobs.tile_ghost_rows && static_cast<size_t>(chi) * rhi < (size_t(1) << 21) && knobs.macro_ghost < 0)   // (blocks of >= 256 columns: the measured range)
+    ghost = std::max(ghost, std::min(32 / k * k, static_cast<int>(kMaxGhost)));
+  int ghost_x = (ghost + 1) & ~1;
+  ghost_x = std::min(std::max(knob_or(knobs.tile_ghost_x, ghost_x) & ~1, ghost_x), kMaxGhost);
+  // every rank's storage rows (owned + ghost columns) must be ones the K-step kernels take, and its own columns at least the ghost
+  // columns its neighbours need from it
+  lbm_params narrow = *p, wide = *p;
+  narrow.nx = clo + 2 * ghost_x; wide.nx = chi + 2 * ghost_x;
+  if (k <= 0 || !macro_eligible(&narrow, rlo, flags) || !macro_eligible(&wide, rhi, flags) || !macro_eligible(&narrow, rhi, flags) || !macro_eligible(&wide, rlo, flags) ||
+      clo < ghost_x || (py > 1 && rlo < ghost)) {
+    set_error("lbm_tile_layout_of: the tile decomposition runs in K-step mode only: every rank needs >= 32 rows, an even number of columns with "
+                            "at least 128 storage columns (owned + ghost) and LBM_FLAG_ONE_STEP clear — use the row decomposition (lbm_rank_layout)");
+    return 1;
+  }
+  out->macro_k = k; out->ghost = ghost; out->ghost_x = ghost_x;
+  out->group = macro_group_for(knobs, k, ghost);
+  // column blocks (py = 1: every rank owns all rows) keep no ghost rows: their launches wrap in y like a whole grid's, and an exchange is the
+  // column push alone.  LBM_TUNE_TILE_GHOST_ROWS=1 keeps them (a 1 x 1 ring then stands for a block of ANY tiling: the rank is its own south
+  // and north neighbour through the row push, as it is its own west and east one)
+  out->ghost_y = (py == 1 && !knobs.tile_ghost_rows) ? 0 : ghost;
+  return 0;
+}
+
+// lbm_create_tile's part of a plan: `p->nx` is then the storage row width nxl + 2 ghost_x
+struct TileSpec { int px, py, rx, ry, x0, nxl, ghost_x, nx_global, ghost_rows; };
+
+// Launch geometry of a context that runs lbm_multi_kernel (K-step partitions and whole grids alike): the geometry by size, its tile width,
+// and room for the partials of its longest launch (no ghost rows where the rows wrap).
+void plan_multi(const Knobs& knobs, bool tile_rank, ContextPlan& c)
+{
+  c.multi_geom = pick_geom(knobs, static_cast<size_t>(c.ncells));
+  if (tile_rank && c.ghost_rows == 0 && c.multi_geom == kGeomTall && knobs.multi_geom < 0) {
+    // A column block's launches all cover exactly its ny rows: where 23-row tiles fit them badly the last tile row is mostly waste — 256 rows: 12
+    // tile rows cover 276 (7.8 % over) against 260 on 13-row tiles; 128 rows: 138 against 130 — and the standard geometry wins by 10 % (us/step
+    // tall / standard: 4096 x 256 8.96 / 8.11, 8192 x 128 9.40 / 8.37; 512 and 1024 rows fit: 2048 x 512 7.82 / 8.25, 1024 x 1024 8.20 / 8.60, 2048 x 1024
+    // 13.8 / 14.1; profiles/r04/ab_column_block_geometry.txt).  Row blocks and whole grids compute different row counts from launch to launch (no rule).
+    auto over = [&](int ty) { return static_cast<double>((c.nyl + ty - 1) / ty * ty) / c.nyl; };
+    if (over(kMTY4Tall) - over(kMTY4) > 0.03) c.multi_geom = kGeomStd;
+  }
+  c.multi_tx = geom_tx(c.multi_geom);
+  c.multi_tiles_x = (c.nx + c.multi_tx - 1) / c.multi_tx;
+  if (c.multi_K > 0) c.partials_cap = std::max(c.partials_cap, kMaxMultiSteps * c.multi_tiles_x * ((c.nyl + 2 * c.ghost_rows + kMinMultiTY - 1) / kMinMultiTY) + 1);
+}
+
+// The one function that decides: lbm_create / lbm_create_global / lbm_create_rank / lbm_create_tile all end here.  The obstacle flags of
+// the ghost rows that the K-step kernels need come either from the whole map (has_global_map, lbm_create_global) or from the rank's
+// window (has_window, lbm_create_rank / lbm_create_tile); neither = no ghost rows possible.  forced_k < 0: K-step mode and K decided
+// from this partition's own shape (lbm_create_global); >= 0: decided by the caller for the whole run (rank_layout, tile_layout_of).
+int plan_context(const Knobs& knobs, const lbm_params* p, int free_cells, bool has_global_map, bool has_window, int forced_k, int forced_ghost,
+                 int y0, int ny_local, unsigned flags, const TileSpec* tile, ContextPlan* out)
+{
+  if (!p || !out) { set_error("lbm_create: null argument"); return lbm_internal::kPlanRefused; }
+  if (p->nx < 1) { set_error("lbm_create: nx must be positive"); return lbm_internal::kPlanRefused; }
+  if (p->ny < 3) { set_error("lbm_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return lbm_internal::kPlanRefused; }
+  if (ny_local < 1 || y0 < 0 || y0 + ny_local > p->ny) { set_error("lbm_create: partition rows out of range"); return lbm_internal::kPlanRefused; }
+  if (free_cells <= 0) { set_error("lbm_create: free_cells must be positive"); return lbm_internal::kPlanRefused; }
+  if (flags & LBM_FLAG_FUSED_ARITH) {
+    // one form of the sum|u| terms per kernel family for the fused arithmetic (that family's default): the flags that ask for another are refused
+    if (flags & (LBM_FLAG_FAST_AVVELS | LBM_FLAG_EXACT_AVVELS)) {
+      set_error("lbm_create: LBM_FLAG_FUSED_ARITH cannot be combined with LBM_FLAG_FAST_AVVELS or LBM_FLAG_EXACT_AVVELS (the fused kernels carry each family's default sum|u| terms only)");
+      return lbm_internal::kPlanRefused;
+    }
+  }
+  const bool self_periodic = (ny_local == p->ny) && !(flags & LBM_FLAG_FORCE_HALO);
+  const int accel_global = p->ny - 2;
+  int accel_row = -1;
+  if (accel_global >= y0 && accel_global < y0 + ny_local) accel_row = accel_global - y0;
+  if (!self_periodic && accel_row >= 0 && (accel_row == 0 || accel_row == ny_local - 1)) {
+    set_error("lbm_create: the partition holding row ny-2 needs >= 3 rows (d2q9-bgk.c:848-849)");
+    return lbm_internal::kPlanRefused;
+  }
+  if (static_cast<long long>(p->nx) * ny_local > (1LL << 31) - 4096) { set_error("lbm_create: partition too large for 32-bit cell indices"); return lbm_internal::kPlanRefused; }
+
+  // ---- from here on lbm_create* has always had the device current: refusals are kPlanRefusedLate ----
+  ContextPlan c;
+  std::memset(&c, 0, sizeof c);
+  c.flags = flags;
+  c.nx = p->nx; c.y0 = y0; c.nyl = ny_local;
+  c.free_cells_inv = 1.0f / free_cells;                                    // d2q9-bgk.c:950
+  c.nxl = c.nx_global = p->nx;
+  c.tiles_px = c.tiles_py = 1;
+  if (tile) {
+    c.ghost_x = tile->ghost_x; c.x0 = tile->x0; c.nxl = tile->nxl; c.nx_global = tile->nx_global;
+    c.tiles_px = tile->px; c.tiles_py = tile->py; c.tile_rx = tile->rx; c.tile_ry = tile->ry;
+  }
+  c.self_periodic = self_periodic;
+  c.fast_avvels = (flags & LBM_FLAG_FAST_AVVELS) != 0;
+  c.fused = (flags & LBM_FLAG_FUSED_ARITH) != 0;
+  c.multi_terms = c.fast_avvels ? kTermsFloat : (flags & LBM_FLAG_EXACT_AVVELS) ? kTermsDouble : kTermsCompensated;
+  {
+    const int t = knobs.terms;                                // 0 double, 1 float, 2 compensated (A/B runs of the DEFAULT form:
+    if (t >= 0 && t <= 2 && !(flags & (LBM_FLAG_EXACT_AVVELS | LBM_FLAG_FAST_AVVELS))) c.multi_terms = t;   // a form asked for by flag stays)
+  }
+  c.accel_row = accel_row;
+  c.accel_w1 = p->density * p->accel * 0.111111111111111111111111f;        // d2q9-bgk.c:445
+  c.accel_w2 = p->density * p->accel * 0.0277777777777777777777778f;       // d2q9-bgk.c:446
+  c.ncells = static_cast<long long>(p->nx) * ny_local;
+  const size_t ncells = static_cast<size_t>(c.ncells);
+  // K-step mode of a row-partitioned run: K ghost rows on each side of the owned rows, refreshed by the
+  // neighbours every K steps, all steps done by lbm_multi_kernel (lbm_macro_* calls)
+  c.group_max = 1;
+  if (forced_k > 0) {
+    if (self_periodic || !has_window || forced_k > kMaxMultiSteps || forced_ghost < forced_k || forced_ghost > kMaxGhost ||
+        !macro_eligible(p, ny_local, flags)) {
+      set_error("lbm_create_rank: partition cannot run the K-step mode its layout asks for");
+      return lbm_internal::kPlanRefusedLate;
+    }
+    c.multi_K = forced_k; c.ghost = forced_ghost;
+    c.ghost_rows = (tile && !tile->ghost_rows) ? 0 : forced_ghost;
+    c.group_max = macro_group_for(knobs, forced_k, forced_ghost);
+  } else if (forced_k < 0 && !self_periodic && has_global_map && macro_eligible(p, ny_local, flags)) {
+    const int k = macro_k_for(knobs);
+    if (k > 0) { c.multi_K = k; c.ghost = c.ghost_rows = macro_ghost_for(knobs, k, p->nx, ny_local, ny_local); c.group_max = macro_group_for(knobs, k, c.ghost); }
+  }
+  c.multi_tail4 = knobs.multi_tail4 != 0;
+  c.ncells_storage = static_cast<long long>(p->nx) * (ny_local + 2 * c.ghost_rows);
+  c.ps = static_cast<long long>(lbm_internal::plane_stride_floats(static_cast<size_t>(c.ncells_storage), knobs.skew));
+  c.grid_floats = 9 * c.ps + 128;
+  // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache
+  const size_t state_bytes = 2 * 9 * ncells * sizeof(float);
+  c.nt_stores = state_bytes > (192u << 20);
+  if (flags & LBM_FLAG_NT_STORES) c.nt_stores = 1;
+  if (flags & LBM_FLAG_NO_NT_STORES) c.nt_stores = 0;
+  // narrow form for latency-bound grids (measured cross-over) and for nx % 4 != 0
+  // (128x128: 3.5 vs 4.4 us/step, 256x256: 4.1 vs 4.6, 512x512: 7.3 vs 6.2 -> cross-over at 64 K cells)
+  const size_t narrow_max = static_cast<size_t>(knobs.narrow_max);
+  c.lane_cells = (p->nx % kCellsPerLane != 0 || ncells <= narrow_max) ? 1 : kCellsPerLane;
+  if (flags & LBM_FLAG_KERNEL_LDS) {
+    set_error("lbm_create: LBM_FLAG_KERNEL_LDS is retired (the LDS-staged one-step kernel was never faster and is no longer built)");
+    return lbm_internal::kPlanRefusedLate;
+  }
+  // hipGraph replay of 64-step blocks is opt-in: measured on MI355X it changes nothing (128x128:
+  // 4.47 vs 4.33 us/step) because even the smallest grids are bound by the device-side kernel
+  // boundary + kernel latency, not by the host's launch rate
+  c.use_graph = self_periodic && (flags & LBM_FLAG_GRAPH);
+  // obstacle bitfield of the storage rows; halo buffers: 2 send + 2 recv, each [3][nxp]
+  c.mask_words = static_cast<int>((static_cast<size_t>(c.ncells_storage) + 31) / 32 + 4);
+  c.nxp = p->nx + 2 * kHaloGuard;
+  // launch geometry + partial buffers
+  const long long qrow = p->nx / c.lane_cells;
+  const long long qfull = qrow * ny_local;
+  c.iters_full = lbm_internal::pick_iters(qfull, knobs.maxblocks);
+  c.n_part_full = lbm_internal::blocks_for(qfull, c.iters_full);
+  const long long qint = ny_local > 2 ? qrow * (ny_local - 2) : 0;
+  c.iters_interior = lbm_internal::pick_iters(qint > 0 ? qint : 1, knobs.maxblocks);
+  c.n_part_interior = qint > 0 ? lbm_internal::blocks_for(qint, c.iters_interior) : 0;
+  c.n_part_boundary = lbm_internal::blocks_for(ny_local > 1 ? 2 * qrow : qrow, 1);
+  c.partials_cap = std::max(c.n_part_full, c.n_part_interior + c.n_part_boundary) + 1;
+  // temporally blocked form: whole periodic grids whose edges are multiples of the tile edge and
+  // that are small enough to be launch-latency-bound (measured cross-over)
+  {
+    // geometry by size, measured on MI355X (us/step for <8,4> / <8,8> / <16,4> / <16,8>; one-step kernels
+    // 3.4 / 3.5 / 4.0):  128x128 1.7 / 1.4 / 1.8 / 1.6 | 128x256 2.2 / 1.8 / 1.9 / 1.7 | 256x256 3.4 / 3.0 / 2.2 / 1.9
+    const int by_size = ncells <= 16384 ? 88 : 168;
+    const int geom = knob_or(knobs.tile_geom, by_size);   // T*10 + H
+    c.tile_T = geom / 10; c.tile_H = geom % 10;
+    if (!((c.tile_T == 16 || c.tile_T == 8) && (c.tile_H == 8 || c.tile_H == 4))) { c.tile_T = 16; c.tile_H = 4; }
+  }
+  // measured whole-deck times (s) for 0 / 256 / 512: 128x128 0.0648 / 0.0576 / 0.0565, 128x256 0.0746 / 0.0747 / 0.0712,
+  // 256x256 0.1598 / 0.1570 / 0.1532
+  c.tile_single_max = knobs.tile_single_max;
+  c.n_tiles = (p->nx % c.tile_T == 0 && ny_local % c.tile_T == 0) ? (p->nx / c.tile_T) * (ny_local / c.tile_T) : 0;
+  c.tile_kernel = self_periodic && c.n_tiles > 0 &&
+                  ncells <= static_cast<size_t>(knobs.tile_max);  // us/step here vs lbm_multi_kernel<3>: 256x256 1.9 / 3.1, 512x256 2.8 / 3.2, 384x384 3.6 / 3.2, 512x512 4.5 / 3.3
+  c.multi_geom = kGeomStd; c.multi_tx = kMTX;
+  if (c.ghost > 0) {
+    // the packed messages of a K-step partition: one row message is 9 planes of its ghost rows (a column block — a tile rank that owns
+    // every row, ghost_rows == 0 — has no row exchange: 0 floats, its buffers hold one row); a tile rank's column message 9 planes of
+    // ghost_x columns of its owned rows.  Each buffer holds both directions.
+    c.pack_floats = c.ghost_rows > 0 ? 9LL * c.ghost * p->nx : 0;
+    c.pack_alloc_floats = 2LL * 9 * std::max(c.ghost_rows, 1) * p->nx;
+    c.pack_floats_x = c.ghost_x > 0 ? 9LL * ny_local * c.ghost_x : 0;
+    c.tile_kernel = 0;
+    plan_multi(knobs, tile != nullptr, c);
+  } else if (!c.tile_kernel && self_periodic && whole_grid_tiled(p->nx, ny_local)) {
+    // K steps per pass over HBM (lbm_multi_kernel), measured us/step for K = 2 / 3 / 4 (one-step kernel):
+    //   8192x8192 500 / 360 / 405 (853-917)   2048x2048 33.5 / 25.5 / 27.4 (59)
+    //   1024x1024 11.2 / 8.3 / 8.5 (13.5)   512x512 3.7 / 3.4 / 3.3 (6.3; lbm_tile_kernel 5.2)
+    // K = 2 is HBM-bound, K = 4 instruction-bound at 2 blocks per CU (60 KB frames); K = 3 sits at both limits
+    // round 3, 4-step launch on 64 x 13 tiles: K = 3 / K = 4 8192x8192 346.6 / 324.0, 4096x4096 87.2 / 78.4, 2048x2048 24.0 / 21.6,
+    // 1536x1536 14.2 / 13.8, 1024x1024 8.16 / 7.07, 768x768 5.39 / 4.63, 1024x512 4.51 / 4.72, 512x1024 4.39 / 4.62, 640x640 4.01 / 4.13,
+    // 512x512 3.11 / 3.45 -> K = 4 from 768 x 768 cells up (profiles/r03/ab_k3_k4.txt, ab_k3_k4_threshold.txt)
+    c.multi_K = std::min(std::max(knob_or(knobs.multi_k, ncells >= size_t(768) * 768 ? 4 : 3), 0), kMaxMultiSteps);
+    plan_multi(knobs, false, c);
+  } else if (c.tile_kernel) {
+    c.partials_cap = std::max(c.partials_cap, kMaxTileSteps * c.n_tiles + 1);
+  }
+  *out = c;
+  return lbm_internal::kPlanOk;
+}
+
+}  // namespace
+
+namespace lbm_internal {
+
+int plan_whole(const Knobs& knobs, const lbm_params* p, int free_cells, int y0, int ny_local, unsigned flags, bool has_global_map, ContextPlan* out)
+{
+  return plan_context(knobs, p, free_cells, has_global_map, false, has_global_map ? -1 : 0, 0, y0, ny_local, flags, nullptr, out);
+}
+
+int plan_rank(const Knobs& knobs, const lbm_params* p, int free_cells, int nranks, int rank, unsigned flags, ContextPlan* out)
+{
+  lbm_layout lay;
+  if (rank_layout(knobs, p, nranks, rank, flags, &lay)) return kPlanRefused;
+  return plan_context(knobs, p, free_cells, false, true, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, flags, nullptr, out);
+}
+
+int plan_tile(const Knobs& knobs, const lbm_params* p, int free_cells, int px, int py, int rank, unsigned flags, ContextPlan* out)
+{
+  lbm_tile_layout lay;
+  if (tile_layout_of(knobs, p, px, py, rank, flags, &lay)) return kPlanRefused;
+  lbm_params local = *p;
+  local.nx = lay.nx_local + 2 * lay.ghost_x;                                           // the storage row: what every kernel works on
+  const TileSpec tile{px, py, lay.rx, lay.ry, lay.x0, lay.nx_local, lay.ghost_x, p->nx, lay.ghost_y};
+  return plan_context(knobs, &local, free_cells, false, true, lay.macro_k, lay.ghost, lay.y0, lay.ny_local, flags | LBM_FLAG_FORCE_HALO, &tile, out);
+}
+
+// Which kernel family advances a context: lbm_multi_kernel (whole grids it tiles and every K-step partition), lbm_tile_kernel (small whole
+// grids), or the one-step kernels (everything else).  lbm_run launches by it and lbm_describe names it.
+KernelFamily family_of(const ContextPlan& c)
+{
+  if (c.multi_K > 0 && (c.self_periodic || c.ghost > 0)) return kFamilyMulti;
+  return (c.tile_kernel && c.self_periodic) ? kFamilyTile : kFamilyStep;
+}
+
+// The library's names for the families (a profiler prints the instantiations: lbm_multi_kernel<K, 6, GEOM, PART> with 6 = kTermsCompensated + kTermsFused,
+// lbm_tile_kernel<T, H, FULL, TERMS>, lbm_step_kernel<CELLS, NT, FUSED>)
+void plan_kernel_name(const ContextPlan& c, char* kernel_name, size_t len)
+{
+  const KernelFamily family = family_of(c);
+  const char* nt = c.nt_stores ? "true" : "false";
+  if (c.fused) {                 // LBM_FLAG_FUSED_ARITH
+    if (family == kFamilyMulti) std::snprintf(kernel_name, len, "lbm_multi_kernel<%d, 6> (fused arithmetic)", c.multi_K);
+    else if (family == kFamilyTile) std::snprintf(kernel_name, len, "lbm_tile_kernel_fused<%d, %d>", c.tile_T, c.tile_H);
+    else std::snprintf(kernel_name, len, c.lane_cells == 1 ? "lbm_step_kernel_narrow_fused<%s>" : "lbm_step_kernel_fused<%s>", nt);
+  }
+  else if (family == kFamilyMulti) std::snprintf(kernel_name, len, c.multi_terms == kTermsFloat ? "lbm_multi_kernel<%d, fast av_vels>" : c.multi_terms == kTermsDouble ? "lbm_multi_kernel<%d, double-precision av_vels terms>" : "lbm_multi_kernel<%d>", c.multi_K);
+  else if (family == kFamilyTile) std::snprintf(kernel_name, len, c.fast_avvels ? "lbm_tile_kernel<%d, %d, fast av_vels>" : "lbm_tile_kernel<%d, %d>", c.tile_T, c.tile_H);
+  else std::snprintf(kernel_name, len, c.lane_cells == 1 ? "lbm_step_kernel_narrow<%s>" : "lbm_step_kernel<%s>", nt);
+}
+
+}  // namespace lbm_internal
+
+extern "C" {
+
+int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
+{
+  return rank_layout(knobs_from_env(), p, nranks, rank, flags, out);
+}
+
+int lbm_tile_layout_of(const lbm_params* p, int px, int py, int rank, unsigned flags, lbm_tile_layout* out)
+{
+  return tile_layout_of(knobs_from_env(), p, px, py, rank, flags, out);
+}
+
+// Row blocks or tiles, and which tiles, for `nranks` ranks: the decomposition whose ranks recompute the smallest share of cells they do not own.
+// A rank of R rows and C columns that keeps g ghost rows / columns advances, averaged over a group of launches, about 3/8 g ghost rows per
+// side (the first launch of a group g - k of them, the last none) and — tiles — all 2 g ghost columns in every launch:
+//     row blocks     0.75 g / R              + 0.1 below 128 rows (an exchange every 8 steps), + 0.2 below 64 (every 4), + 1 below 32 (one-step loop)
+//     column blocks  2 g / C + 0.02          (px x 1 tilings: no ghost rows, one exchange kernel; the margin: 128-row blocks against 320 / 384 /
+//                                            448 / 512-column blocks came out 4.58 / 5.06, 5.39 / 5.87, 5.80 / 5.61, 4.36 / 4.01 us/step)
+//     other tiles    0.75 g / R + 2 g / C + 0.05 (the second exchange kernel), thin blocks charged as thin row blocks are
+// The rule orders the 25 pairs measured on 1-rank rings as they came out (profiles/r04/{wide,tile,auto,column}_*.json), us/step
+// rows / tiles of the same cells: 8192 x 1024 43.8 / 46.0 as 1024 x 8192 column blocks and 45.5 as 2048 x 4096; 1024 x 128 3.28 / 4.05 as 128 x 1024,
+// 4.13 as 256 x 512; 1024 x 256 3.99 / 4.93; 2048 x 256 5.5 / 6.2; 1024 x 64 3.25 / 3.51 as 512 x 128 (rows: a second exchange kernel and ghost
+// columns cost more than the ghost rows of blocks this tall, or than a small block's frequent exchanges) — and 2048 x 128 4.36 / 4.01 as 512 x 512
+// column blocks, 4096 x 128 6.15 / 5.37, 2048 x 64 4.12 / 3.31, 4096 x 64 5.38 / 4.03, 8192 x 64 7.45 / 5.64, 16384 x 64 13.2 / 8.7, 32768 x 32 18.3 / 9.4,
+// 65536 x 16 21.8 / 9.5 (tiles: wide column blocks beat row blocks of up to 128 rows).  Every BASELINE.json config comes out as row blocks.
+// A function of p, nranks and flags only.  *px == 1 means ROW BLOCKS (lbm_create_rank: no ghost columns), anything else lbm_create_tile on *px x *py.
+int lbm_choose_rank_grid(const lbm_params* p, int nranks, unsigned flags, int* px, int* py)
+{
+  if (!p || !px || !py || nranks < 1) { set_error("lbm_choose_rank_grid: bad argument"); return 1; }
+  *px = 1; *py = nranks;
+  const Knobs knobs = knobs_from_env();
+  lbm_layout rows;
+  if (rank_layout(knobs, p, nranks, nranks - 1, flags, &rows)) return 1;
+  if (nranks == 1) return 0;
+  std::vector<int> nyl(nranks), dis(nranks);
+  if (lbm_decompose(p->ny, nranks, nyl.data(), dis.data())) return 1;
+  const int rmin = *std::min_element(nyl.begin(), nyl.end());
+  auto thin = [](int r) { return (r < 128 ? 0.1 : 0.0) + (r < 64 ? 0.2 : 0.0); };
+  double best = rows.macro_k > 0 ? 0.75 * rows.ghost / rmin + thin(rmin) : 1.0 + thin(rmin);
+  for (int qx = 2; qx <= nranks; ++qx) {
+    if (nranks % qx != 0) continue;
+    lbm_tile_layout t;
+    if (tile_layout_of(knobs, p, qx, nranks / qx, nranks - 1, flags, &t)) continue;      // a rank would fall out of K-step mode: not a candidate
+    // (the last rank holds the smallest column block and, by the reference's rule, not the largest row block)
+    // (a column block's 32 ghost columns count as 16 here: the rule was measured at 16, and the deeper halo only made the column blocks faster)
+    const double cost = t.ghost_y > 0 ? 0.75 * t.ghost_y / t.ny_local + 2.0 * t.ghost_x / t.nx_local + 0.05 + thin(t.ny_local)
+                                      : 2.0 * std::min(t.ghost_x, 16) / t.nx_local + 0.02;
+    if (cost < best) { best = cost; *px = qx; *py = nranks / qx; }
+  }
+  (void)lbm_last_error();
+  return 0;
+}
+
+// ---- the plan, for tests (lbm_internal.h; not part of the ABI): the knobs are read per call, as the layout functions read them ----
+int lbm_plan_sizeof(void) { return static_cast<int>(sizeof(ContextPlan)); }
+int lbm_plan_whole(const lbm_params* p, int free_cells, int y0, int ny_local, unsigned flags, int has_global_map, ContextPlan* out)
+{
+  return lbm_internal::plan_whole(knobs_from_env(), p, free_cells, y0, ny_local, flags, has_global_map != 0, out) ? 1 : 0;
+}
+int lbm_plan_rank(const lbm_params* p, int free_cells, int nranks, int rank, unsigned flags, ContextPlan* out)
+{
+  return lbm_internal::plan_rank(knobs_from_env(), p, free_cells, nranks, rank, flags, out) ? 1 : 0;
+}
+int lbm_plan_tile(const lbm_params* p, int free_cells, int px, int py, int rank, unsigned flags, ContextPlan* out)
+{
+  return lbm_internal::plan_tile(knobs_from_env(), p, free_cells, px, py, rank, flags, out) ? 1 : 0;
+}
+int lbm_plan_kernel_name(const ContextPlan* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan_kernel_name: null argument"); return 1; }
+  lbm_internal::plan_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+
+}  // extern "C"

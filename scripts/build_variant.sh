@@ -7,5 +7,5 @@ NAME=$1; shift
 OUT=$ROOT/mpilattice-boltzmann_amd/lib/variants
 mkdir -p $OUT
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -pthread -I $ROOT/include -I $ROOT/mpilattice-boltzmann_amd/csrc \
-  -fPIC -shared "$@" $ROOT/mpilattice-boltzmann_amd/csrc/lbm_kernels.hip $ROOT/mpilattice-boltzmann_amd/csrc/lbm_host.cpp -o $OUT/$NAME.so
+  -fPIC -shared "$@" $ROOT/mpilattice-boltzmann_amd/csrc/lbm_kernels.hip $ROOT/mpilattice-boltzmann_amd/csrc/lbm_host.cpp $ROOT/mpilattice-boltzmann_amd/csrc/lbm_plan.cpp -o $OUT/$NAME.so
 echo $OUT/$NAME.so

@@ -1,0 +1,46 @@
+// plan_table_main.cpp — the planning unit under the host sanitizers: the three plan functions over the table of tests/plan_cases.py and
+// over the refusals, printed one line per context.  Host-only code, no GPU and no Python:
+//   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I mpilattice-boltzmann_amd/csrc
+//       scripts/plan_table_main.cpp mpilattice-boltzmann_amd/csrc/lbm_plan.cpp mpilattice-boltzmann_amd/csrc/lbm_host.cpp -pthread -o plan_table && ./plan_table
+#include <cstdio>
+
+#include "lbm_d2q9.h"
+#include "lbm_internal.h"
+
+static int shown = 0;
+static void show(const char* what, int nx, int ny, int rc, const lbm_internal::ContextPlan& plan)
+{
+  char name[256] = "";
+  if (rc == 0) lbm_plan_kernel_name(&plan, name, sizeof name);
+  std::printf("%-5s %6d x %-6d %s\n", what, nx, ny, rc == 0 ? name : lbm_last_error());
+  ++shown;
+}
+
+int main()
+{
+  const int whole[][2] = {{128, 128}, {128, 256}, {256, 256}, {512, 256}, {512, 512}, {768, 768}, {1024, 1024}, {2048, 2048}, {64, 16}, {130, 100},
+                          {100, 100}, {127, 64}, {96, 2048}, {100, 40000}, {65536, 40000}, {1, 3}, {0, 0}};
+  const unsigned flags[] = {0, LBM_FLAG_FAST_AVVELS, LBM_FLAG_EXACT_AVVELS, LBM_FLAG_FUSED_ARITH, LBM_FLAG_ONE_STEP, LBM_FLAG_NT_STORES, LBM_FLAG_KERNEL_LDS,
+                            LBM_FLAG_FUSED_ARITH | LBM_FLAG_FAST_AVVELS, LBM_FLAG_GRAPH};
+  lbm_internal::ContextPlan plan;
+  for (const auto& g : whole)
+    for (unsigned f : flags) {
+      const lbm_params p{g[0], g[1], 11, 10, 0.1f, 0.005f, 1.85f};
+      show("whole", g[0], g[1], lbm_plan_whole(&p, 1000, 0, g[1], f, 0, &plan), plan);
+      if (g[1] > 40) show("part", g[0], g[1], lbm_plan_whole(&p, 1000, 3, g[1] - 7, f, 1, &plan), plan);     // lbm_create_global's rows [3, ny - 4)
+    }
+  const int rings[][2] = {{1024, 128}, {1024, 64}, {1024, 31}, {2048, 1024}, {64, 2}};
+  for (const auto& g : rings)
+    for (int nranks : {1, 2, 8}) {
+      const lbm_params p{g[0], g[1], 11, 10, 0.1f, 0.005f, 1.85f};
+      for (int r = 0; r < nranks; ++r) show("rank", g[0], g[1], lbm_plan_rank(&p, 1000, nranks, r, LBM_FLAG_FORCE_HALO, &plan), plan);
+    }
+  const int tiles[][4] = {{512, 512, 1, 1}, {512, 512, 2, 1}, {1024, 512, 2, 2}, {8192, 128, 8, 1}, {100, 100, 2, 2}};
+  for (const auto& t : tiles) {
+    const lbm_params p{t[0], t[1], 11, 10, 0.1f, 0.005f, 1.85f};
+    for (int r = 0; r < t[2] * t[3]; ++r) show("tile", t[0], t[1], lbm_plan_tile(&p, 1000, t[2], t[3], r, 0, &plan), plan);
+  }
+  show("null", 0, 0, lbm_plan_whole(nullptr, 1, 0, 1, 0, 0, &plan), plan);
+  std::printf("%d plans, clean\n", shown);
+  return 0;
+}

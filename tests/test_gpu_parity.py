@@ -898,7 +898,7 @@ def test_groups_of_launches_per_exchange_on_a_ring_of_one(lbm, oracle, monkeypat
     obst = lbm.synthetic_obstacles(nx, ny, 0.03, nx * 5 + ny, False)
     sim = lbm.Simulation(p, obst, flags=lbm._capi.FLAG_FORCE_HALO, exchange=exchange, strict=True)
     lay = sim.layout
-    two = 8 if K == 3 else 2 * K                         # the default: by the rank's size (lbm_kernels.hip macro_ghost_for)
+    two = 8 if K == 3 else 2 * K                         # the default: by the rank's size (lbm_plan.cpp macro_ghost_for)
     by_size = two if nx * ny >= 1 << 21 else max(16 // K * K, two) if ny >= 128 else two if ny >= 64 else (4 if K == 3 else K)
     if nx <= 2048 and nx * ny <= 1 << 19 and ny >= 128:         # the smallest ranks: 24 rows from 128 rows per rank, 32 from 256
         by_size = max(by_size, (32 if ny >= 256 else 24) // K * K)
@@ -1119,7 +1119,7 @@ P2P_CASES = {
         dict(nx=512, ny=256, K=0, schedule="", runs=[20, 11], grid=[2, 2], scatter=True), dict(nx=1024, ny=64, K=0, schedule="", runs=[9, 8], grid=[4, 1]),
         dict(nx=384, ny=200, K=3, schedule="", runs=[31], grid=[2, 2], walls=True),
         dict(nx=1024, ny=512, K=0, schedule="edge", runs=[20, 11], grid=[2, 2], scatter=True)],
-    # the driver's eight row ranks (BASELINE configs 4 and 5) at each boundary of the ghost-row rule (lbm_kernels.hip macro_ghost_for):
+    # the driver's eight row ranks (BASELINE configs 4 and 5) at each boundary of the ghost-row rule (lbm_plan.cpp macro_ghost_for):
     # 128 rows per rank -> 24 rows, six launches per exchange; a rank below 128 rows -> every rank drops to 8 / 2; 256 rows at nx * rows =
     # 2^19 -> 32 / 8; just below 256 rows -> 24 / 6; nx * rows above 2^19 -> 16 / 4.  "want" pins the shape each case is named for
     8: [dict(nx=1024, ny=1024, K=0, schedule="", runs=[50, 23], want=[24, 6]),

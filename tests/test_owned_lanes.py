@@ -121,7 +121,7 @@ def test_per_step_sums_against_the_double_form(lbm, oracle, tall):
 
 
 # ---- the row-pass dealing (k_substeps): every launch but the tall K = 4 one.  The library does not report the geometry of its
-# launches; LBM_TUNE_MULTI_GEOM overrides its whole choice (pick_geom in lbm_kernels.hip), so a case names the geometry it runs
+# launches; LBM_TUNE_MULTI_GEOM overrides its whole choice (pick_geom in lbm_plan.cpp), so a case names the geometry it runs
 # and the guard checks what can be seen: the kernel's name and the steps of every launch.
 STD, NARROW = "0", "1"
 
