@@ -86,4 +86,15 @@ constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
 // and kept tests in x as well, in the tiles on the rim of the owned block only — and four ready words).
 constexpr int kPartPlain = 0, kPartGhost = 1, kPartReady = 2, kPartTile = 3;
 
+// ---- the host's tables of instantiations (lbm_kernels.hip kMultiKernels, kTileKernels): which row a launch takes ----
+// lbm_multi_kernel: one row per (geometry, steps, terms, launch form).  The terms index of a row: the three forms of the sum|u| terms,
+// then (index kMultiTermsFused) the fused arithmetic with lbm_multi_kernel's default form of them.
+constexpr int kMultiTermsFused = 3;
+constexpr int kMultiTerms = 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
+constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
+// lbm_tile_kernel: one row per (geometry, FULL, terms).  The terms index of a row: double-precision sum|u| terms, float ones
+// (LBM_FLAG_FAST_AVVELS), the fused arithmetic (LBM_FLAG_FUSED_ARITH; never with the float terms: plan_context).
+constexpr int kTileTermsFused = 2, kTileTerms = 3, kTileRows = 4 * 2 * kTileTerms;
+constexpr int tile_row(int t, int h, bool full, int terms) { return (((t == 8 ? 2 : 0) + (h == 4 ? 1 : 0)) * 2 + (full ? 1 : 0)) * kTileTerms + terms; }
+
 }  // namespace

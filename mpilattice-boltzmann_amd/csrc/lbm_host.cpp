@@ -136,49 +136,6 @@ int lbm_tile_neighbours(int px, int py, int rank, int out[4])
   return 0;
 }
 
-int lbm_plan_next(int K, int four_rows, int tail4, int left)
-{
-  int k = left < K ? left : K;
-  if (!four_rows || !tail4) return k;
-  if (K == 3 && ((left % 3 == 1 && left >= 4) || (left % 3 == 2 && left >= 8))) k = 4;
-  if (K == 4 && ((left % 4 == 3) || (left % 4 == 2 && left >= 6) || (left % 4 == 1 && left >= 9))) k = 3;
-  return k;
-}
-
-// The launches between two halo exchanges of a partitioned run ("a group"): the next launches by lbm_plan_next for as long as their
-// steps add up to at most `ghost` (the first launch of a group advances the ghost rows the later ones read), `group_max` launches at most.
-// The first launch is always taken.  One implementation for the loops (plan_group in lbm_kernels.hip, with the context's four_rows / tail4)
-// and for the public lbm_plan_group that bench.py and the tests plan with, so that the two cannot disagree.
-int lbm_plan_group_for(int K, int four_rows, int tail4, int ghost, int group_max, int left, int* steps, int cap)
-{
-  int n = 0, used = 0;
-  while (left > 0 && n < group_max) {
-    const int k = lbm_plan_next(K, four_rows, tail4, left);
-    if (n > 0 && used + k > ghost) break;
-    if (n < cap) steps[n] = k;
-    ++n; used += k; left -= k;
-  }
-  return n;
-}
-
-int lbm_plan_group(int K, int ghost, int group_max, int left, int* steps, int cap)
-{
-  if (K < 1 || K > 4 || ghost < K || group_max < 1 || left < 0 || cap < 0 || (cap > 0 && !steps)) { lbm_internal::set_error("lbm_plan_group: bad argument"); return -1; }
-  return lbm_plan_group_for(K, ghost >= 4 ? 1 : 0, 1, ghost, group_max, left, steps, cap);
-}
-
-int lbm_plan_steps(int K, int four_rows, int n_steps, int* steps, int cap)
-{
-  if (K < 1 || K > 4 || n_steps < 0 || cap < 0 || (cap > 0 && !steps)) { lbm_internal::set_error("lbm_plan_steps: bad argument"); return -1; }
-  int n = 0;
-  for (int left = n_steps; left > 0; ++n) {
-    const int k = lbm_plan_next(K, four_rows, 1, left);
-    if (n < cap) steps[n] = k;
-    left -= k;
-  }
-  return n;
-}
-
 // d2q9-bgk.c:716-751 (without the MPI_Reduce): float accumulator, double sqrt.
 float lbm_av_velocity_host(const lbm_params* p, const float* cells, const int* obstacles, int rows)
 {

@@ -69,9 +69,54 @@ void plan_kernel_name(const ContextPlan& plan, char* kernel_name, size_t len);
 size_t plane_stride_floats(size_t ncells, int skew);
 int pick_iters(long long quads, int max_blocks);
 int blocks_for(long long quads, int iters);
+
+// ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
+// The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
+// up to at most the ghost rows, group_max at most.  Launch i of a group advances, besides the owned rows, ext(i) = the steps of the
+// launches AFTER it in the group ghost rows on each side: what those launches read in place of exchanged rows.
+constexpr int kGroupCap = 8;         // kMaxGroup (lbm_geometry.h)
+struct GroupPlan {
+  int n = 0, total = 0;
+  int k[kGroupCap] = {};
+  int ext(int i) const { int e = 0; for (int j = i + 1; j < n; ++j) e += k[j]; return e; }
+};
+int next_multi_k(const ContextPlan& plan, int left);
+GroupPlan plan_group(const ContextPlan& plan, int left);
+
+// One launch of lbm_multi_kernel: every geometric argument (MultiArgs of the same names, kernels/multi.h), its grid and its row of the
+// kernel table (lbm_kernels.hip kMultiKernels).  Plain data, no HIP type and no pointer; tests/test_launch_plan.py mirrors it field for
+// field and refuses a library whose lbm_plan_launch_sizeof() differs.  The launch adds what only the context knows: grids, plane
+// bases, mask, partials, sums, counter and ready words.
+// A launch of lbm_tile_kernel (plan_tile_launch) uses k, full, tiles_x, ntiles_total = tile_count = nblocks = launched_blocks and row
+// (of kTileKernels, whose block size and LDS bytes the launch takes); the rest is 0.
+enum LaunchWhich { kLaunchWhole = 0, kLaunchInterior = 1, kLaunchEdge = 2 };
+struct LaunchPlan {
+  int k, ext;                        // steps; ghost rows (and kept ghost columns) advanced on each side besides the owned cells
+  int row_first, rows_compute, rows_storage, count_first, count_end;
+  int cx0, cx1, keep_x0, keep_x1;
+  int y_periodic, y0_global, tiles_x, ntiles_total;
+  int tile_begin, tile_count, tile_begin2, tile_count2;      // the launch's tiles as two ranges, or (nrect > 0, tile ranks) as rectangles
+  int nrect;
+  struct Rect { int ty0, tx0, ntx, count; } rect[4];
+  int nblocks, launched_blocks, xcd_remap;                   // tiles; blocks of the grid (+ 1: the fold block) after padding; tile order
+  int part, row, lanes;                                      // kPart*; index into the kernel table; block size
+  int full;                                                  // lbm_tile_kernel only: the launch makes exactly tile_H steps
+};
+void plan_launch(const ContextPlan& plan, const Knobs& knobs, int k, int ext, int which, bool says_ready, LaunchPlan* out);
+void plan_tile_launch(const ContextPlan& plan, int left, LaunchPlan* out);
+// Tile rows of a launch of k steps + ext: the first / last read exchanged rows, the interior rows between them do not (tile ranks: nor do
+// the tile columns between left_cols and right_cols).  The rule and its comment: lbm_plan.cpp.
+struct MacroRows { int bottom_edge_rows, interior_rows, top_edge_rows, left_cols, right_cols; };
+MacroRows macro_rows(const ContextPlan& plan, int k, int ext);
+// May the push for the next group (next_total rows per side) start before the interior launch of group `g`, whose first launch splits as `rows`, has finished ?
+bool edge_rows_suffice(const ContextPlan& plan, const GroupPlan& g, const MacroRows& rows, int next_total);
+// Access width (4, 2 or 1 floats) and blocks of a tile rank's column messages of `cols` columns per side: packed (lbm_macro_pack_x: no peer)
+// or pushed into the neighbours' grids (peer: their storage widths, plane strides, owned and ghost columns, which every access must divide too).
+struct ColumnMessagePlan { int per, blocks; };
+ColumnMessagePlan plan_column_message(const ContextPlan& plan, int cols, int max_blocks, const long long* peer, int npeer);
 }  // namespace lbm_internal
 
-// Steps of the next launch of the K-step kernels when `left` steps remain (lbm_host.cpp; lbm_plan_steps is its public
+// Steps of the next launch of the K-step kernels when `left` steps remain (lbm_plan.cpp; lbm_plan_steps is its public
 // form): shared by lbm_run, the split-phase macro-steps and the peer-to-peer loop, so that they cannot disagree.
 extern "C" int lbm_plan_next(int K, int four_rows, int tail4, int left);
 // The launches of the next group (one halo exchange) of a partitioned run; public form in lbm_d2q9.h (four_rows = ghost >= 4, tail4 on).
@@ -83,3 +128,11 @@ extern "C" int lbm_plan_whole(const lbm_params* p, int free_cells, int y0, int n
 extern "C" int lbm_plan_rank(const lbm_params* p, int free_cells, int nranks, int rank, unsigned flags, lbm_internal::ContextPlan* out);
 extern "C" int lbm_plan_tile(const lbm_params* p, int free_cells, int px, int py, int rank, unsigned flags, lbm_internal::ContextPlan* out);
 extern "C" int lbm_plan_kernel_name(const lbm_internal::ContextPlan* plan, char* kernel_name, size_t len);
+// One launch of a context of that plan, and every step-kernel launch of a run of n_steps in the order a serial-schedule run enqueues them
+// (schedule kScheduleSerial: each launch over all its tiles; kScheduleEdge: the first launch of a group as interior + edge, adjacent) —
+// lbm_run, the split-phase calls and the peer-to-peer loop alike.  Returns the number of launches (the first `cap` are written), -1 on a bad argument.
+extern "C" int lbm_plan_launch_sizeof(void);
+extern "C" int lbm_plan_launch(const lbm_internal::ContextPlan* plan, int k, int ext, int which, int says_ready, lbm_internal::LaunchPlan* out);
+extern "C" int lbm_plan_run_launches(const lbm_internal::ContextPlan* plan, int n_steps, int schedule, lbm_internal::LaunchPlan* out, int cap);
+// edge_rows_suffice for the group a run makes with `left` steps remaining and the one after it (0 where no group follows).
+extern "C" int lbm_plan_edge_rows_suffice(const lbm_internal::ContextPlan* plan, int left);

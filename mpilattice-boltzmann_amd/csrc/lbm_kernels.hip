@@ -15,7 +15,10 @@
 // Kernels (all produce the same bits): kernels/multi.h lbm_multi_kernel<K>, kernels/tile.h lbm_tile_kernel<T,H>,
 // kernels/step.h lbm_step_kernel / _narrow, kernels/aux.h the rest.  WHICH of them a context runs, on what geometry and with what
 // buffer sizes, is decided before anything here is allocated: lbm_plan.cpp fills a ContextPlan (lbm_internal.h), and this file
-// allocates, uploads and launches by it.  Nothing here writes the plan after creation.
+// allocates, uploads and launches by it.  Nothing here writes the plan after creation.  WHAT a run launches is decided there too:
+// the steps of each launch and the groups between two exchanges (next_multi_k, plan_group), and every launch's rows, columns, tiles,
+// grid and kernel-table row as a LaunchPlan (plan_launch, plan_tile_launch).  Nothing here decides a tile range: launch_multi and
+// launch_tile add pointers and run state to a LaunchPlan, after_launch / end_run keep the run state.
 //
 // Layout in HBM: struct-of-arrays, 9 planes of rows*nx floats (plane stride padded, see
 // lbm_plan.cpp plane_stride_floats()), two grids (source / destination, swapped per launch like :376-378), the
@@ -60,16 +63,38 @@ namespace {
 // host side of the device ABI
 // ------------------------------------------------------------------------------------------------
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return 1;                                                                              \
-    }                                                                                        \
-  } while (0)
+// A failed HIP call leaves "<the call as written>: <HIP's words>" in lbm_last_error() and takes the exit `on_fail` (HIP_TRY: return 1).
+// (Both stringify their own argument: passed on through another macro, constants that are macros themselves would be spelled out.)
+bool hip_failed(hipError_t e, const char* call)
+{
+  if (e != hipSuccess) lbm_internal::set_error(std::string(call) + ": " + hipGetErrorString(e));
+  return e != hipSuccess;
+}
+#define HIP_TRY_OR(expr, on_fail) do { if (hip_failed((expr), #expr)) { on_fail; } } while (0)
+#define HIP_TRY(expr) do { if (hip_failed((expr), #expr)) return 1; } while (0)
 
 size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
+
+// Profile modes (lbm_set_profile, lbm_p2p_set_profile): timing events around the launches of a run, from a pool grown on demand and
+// reused from run to run (used = 0).  stamp: the next event, recorded on `s`; nullptr when the profile is off or on failure.
+struct EventPool {
+  bool on = false;
+  std::vector<hipEvent_t> pool;
+  size_t used = 0;
+  hipEvent_t stamp(hipStream_t s)
+  {
+    if (!on) return nullptr;
+    if (used == pool.size()) {
+      hipEvent_t e = nullptr;
+      if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+      pool.push_back(e);
+    }
+    hipEvent_t e = pool[used++];
+    if (hipEventRecord(e, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    return e;
+  }
+  void destroy() { for (hipEvent_t e : pool) (void)hipEventDestroy(e); }
+};
 
 }  // namespace
 
@@ -116,10 +141,7 @@ struct lbm_ctx {
   int parity = 0;            // partials buffer written by the current step
   int n_prev = 0;            // partial count of the previous step (0 = nothing to fold)
   int n_prev_vecs = 1;       // ... and how many step vectors of that length the previous launch left (tile kernel: up to 8)
-  // lbm_set_profile: timing events around every step-kernel launch of lbm_run (pool grown on demand, reused)
-  bool profile = false;
-  std::vector<hipEvent_t> prof_pool;
-  size_t prof_used = 0;
+  EventPool prof;            // lbm_set_profile: timing events around every step-kernel launch of lbm_run
   struct ProfLaunch { int steps; hipEvent_t begin, end; };
   std::vector<ProfLaunch> prof_launches;
 };
@@ -209,22 +231,19 @@ void launch_step(lbm_ctx* c, const StepArgs& a, int blocks, hipStream_t s)
   kStepKernels[c->plan.lane_cells == 1][c->plan.nt_stores][c->plan.fused]<<<dim3(blocks + 1), dim3(kBlock), 0, s>>>(a);   // + the fold block
 }
 
-// Every instantiation of lbm_multi_kernel a context may launch, one row per (geometry, steps, terms, launch form) with what a launch
-// of it needs.  Rows of the tall geometry with K < 4 name the standard kernels (geom_for): no instantiation of their own.
-// The terms index of a row: the three forms of the sum|u| terms, then (index kMultiTermsFused) the fused arithmetic
-// with lbm_multi_kernel's default form of them: the instantiation <K, kTermsCompensated + kTermsFused, GEOM, PART>.
-struct MultiKernel { void (*fn)(MultiArgs); int lanes; size_t lds_bytes; };
-constexpr int kMultiTermsFused = 3;
-constexpr int kMultiTerms = 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
+// Every instantiation of lbm_multi_kernel a context may launch, one row per (geometry, steps, terms, launch form; lbm_geometry.h multi_row)
+// with what a launch of it needs besides its LaunchPlan.  Rows of the tall geometry with K < 4 name the standard kernels (geom_for): no
+// instantiation of their own.  The terms index kMultiTermsFused: the instantiation <K, kTermsCompensated + kTermsFused, GEOM, PART>.
+struct MultiKernel { void (*fn)(MultiArgs); size_t lds_bytes; };
 static_assert(kTermsDouble == 0 && kTermsFloat == 1 && kTermsCompensated == 2 && kPartPlain == 0 && kPartTile == 3 && kGeomTall == 2, "the values index the table");
-constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
 template <int ROW>
 constexpr MultiKernel multi_kernel_row()
 {
   constexpr int PART = ROW % kMultiParts, TERMS = ROW / kMultiParts % kMultiTerms, K = ROW / (kMultiParts * kMultiTerms) % kMaxMultiSteps + 1,
                 GEOM = geom_for(K, ROW / kMultiRowsPerGeom);
   static_assert(multi_row(K, ROW / kMultiRowsPerGeom, TERMS, PART) == ROW, "multi_row and its inverse");
-  return {&lbm_multi_kernel<K, TERMS == kMultiTermsFused ? (kTermsCompensated | kTermsFused) : TERMS, GEOM, PART>, MultiGeom<K, GEOM>::LANES, MultiGeom<K, GEOM>::lds_bytes};
+  static_assert(MultiGeom<K, GEOM>::LANES == multi_lanes(K, ROW / kMultiRowsPerGeom), "LaunchPlan::lanes is the row's block size");
+  return {&lbm_multi_kernel<K, TERMS == kMultiTermsFused ? (kTermsCompensated | kTermsFused) : TERMS, GEOM, PART>, MultiGeom<K, GEOM>::lds_bytes};
 }
 template <size_t... ROW>
 constexpr std::array<MultiKernel, sizeof...(ROW)> multi_kernel_rows(std::index_sequence<ROW...>) { return {{multi_kernel_row<static_cast<int>(ROW)>()...}}; }
@@ -248,31 +267,30 @@ hipError_t raise_multi_lds_limits_for(int geom)          // every instantiation 
   return raise_lds_limits(kMultiKernels, geom * kMultiRowsPerGeom, (geom + 1) * kMultiRowsPerGeom);
 }
 
-// Tiles of a launch that makes `k` steps on the owned rows and `ext` more rows on each side (ext > 0: a launch of a partitioned
-// run that is followed by `ext` more steps before the next halo exchange): the tile height depends on k (kernels/multi.h multi_ty).
-int ext_rows(const lbm_ctx* c, int ext) { return c->plan.ghost_rows > 0 ? ext : 0; }
-int multi_tile_rows(const lbm_ctx* c, int k, int ext = 0) { return (c->plan.nyl + 2 * ext_rows(c, ext) + multi_ty(k, c->plan.multi_geom) - 1) / multi_ty(k, c->plan.multi_geom); }
-int multi_tiles_for(const lbm_ctx* c, int k, int ext = 0) { return c->plan.multi_tiles_x * multi_tile_rows(c, k, ext); }
+using lbm_internal::LaunchPlan;
+using lbm_internal::GroupPlan;
+using lbm_internal::kLaunchWhole;
+using lbm_internal::kLaunchInterior;
+using lbm_internal::kLaunchEdge;
 
-// One launch of lbm_multi_kernel over the tile ranges [t0, t0+n0) and [t1, t1+n1): `ksteps` steps of the owned rows and `ext`
-// ghost rows on each side (tile row 0 starts at storage row ghost - ext).
-void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int n0, int t1, int n1, bool fold, hipStream_t s,
-                  const MultiArgs::Rect* rects = nullptr, int nrect = 0)    // rects: the launch's tiles as rectangles of the tile grid (tile ranks) instead of t0 .. n1
+// One launch of lbm_multi_kernel by its plan (lbm_plan.cpp plan_launch: rows, columns, tiles, grid and table row).  Added here, what
+// only the context knows: grids, plane bases and mask, the partials by parity and what is left to fold, sums and counter, the ready words.
+void launch_multi(lbm_ctx* c, const LaunchPlan& l, bool accel_last, bool fold, hipStream_t s)
 {
   MultiArgs a{};
   a.src = c->grid[c->cur]; a.dst = c->grid[c->cur ^ 1];
   for (int k = 0; k < 9; ++k) { a.srck[k] = a.src + k * c->plan.ps; a.dstk[k] = a.dst + k * c->plan.ps; }
   a.mask = c->mask; a.ps = c->plan.ps; a.nx = c->p.nx;
-  const int ext_y = ext_rows(c, ext);                           // ghost rows this launch advances (none where the rows wrap)
-  a.row_first = c->plan.ghost_rows - ext_y; a.rows_compute = c->plan.nyl + 2 * ext_y; a.rows_storage = c->plan.nyl + 2 * c->plan.ghost_rows;
-  a.count_first = c->plan.ghost_rows; a.count_end = c->plan.ghost_rows + c->plan.nyl;
-  a.cx0 = c->plan.ghost_x; a.cx1 = c->plan.ghost_x + c->plan.nxl;
-  a.keep_x0 = std::max(0, (c->plan.ghost_x - ext) & ~1); a.keep_x1 = std::min(c->p.nx, (c->plan.ghost_x + c->plan.nxl + ext + 1) & ~1);
-  a.y_periodic = (c->plan.self_periodic || (c->plan.ghost > 0 && c->plan.ghost_rows == 0)) ? 1 : 0;
-  a.y0_global = c->plan.y0 - ext_y; a.ny_global = c->p.ny;        // global row of storage row row_first
-  a.tiles_x = c->plan.multi_tiles_x;
-  a.tile_begin = t0; a.tile_count = n0; a.tile_begin2 = t1; a.tile_count2 = n1;
-  a.ntiles_total = multi_tiles_for(c, ksteps, ext);
+  a.row_first = l.row_first; a.rows_compute = l.rows_compute; a.rows_storage = l.rows_storage;
+  a.count_first = l.count_first; a.count_end = l.count_end;
+  a.cx0 = l.cx0; a.cx1 = l.cx1; a.keep_x0 = l.keep_x0; a.keep_x1 = l.keep_x1;
+  a.y_periodic = l.y_periodic; a.y0_global = l.y0_global; a.ny_global = c->p.ny;
+  a.tiles_x = l.tiles_x;
+  a.tile_begin = l.tile_begin; a.tile_count = l.tile_count; a.tile_begin2 = l.tile_begin2; a.tile_count2 = l.tile_count2;
+  a.ntiles_total = l.ntiles_total;
+  a.nrect = l.nrect;
+  for (int i = 0; i < l.nrect; ++i) a.rect[i] = MultiArgs::Rect{l.rect[i].ty0, l.rect[i].tx0, l.rect[i].ntx, l.rect[i].count};
+  a.xcd_remap = l.xcd_remap; a.nblocks = l.nblocks;
   a.omega = c->p.omega; a.accel_w1 = c->plan.accel_w1; a.accel_w2 = c->plan.accel_w2;
   a.accel_row = c->p.ny - 2; a.accel_last = accel_last ? 1 : 0;
   a.partials_out = c->partials[c->parity];
@@ -283,34 +301,13 @@ void launch_multi(lbm_ctx* c, int ksteps, int ext, bool accel_last, int t0, int 
   a.ready_epoch = c->ready_epoch;
   a.wait_ready = c->ready_epoch ? c->ready_wait : nullptr; a.timeout_ticks = c->ready_timeout_ticks; a.err = c->ready_err;
   c->ready_epoch = 0;
-  int blocks = n0 + n1;
-  if (nrect > 0) {
-    blocks = 0;
-    a.nrect = nrect; a.tile_count = 0; a.tile_count2 = 0;
-    for (int i = 0; i < nrect; ++i) { a.rect[i] = rects[i]; blocks += rects[i].count; }
-  }
-  // measured on 8192x8192, K=2: 515 us/step with the XCD-contiguous tile order, 549 without
-  a.xcd_remap = (c->knobs.multi_remap && blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
-  a.nblocks = blocks;
-  if (c->plan.ghost_x > 0 && c->knobs.multi_remap && blocks >= 64 && blocks % 8 != 0 && c->knobs.tile_pad_grid) {
-    blocks = (blocks + 7) / 8 * 8;                              // tile ranks: pad the grid (the form drops the extra blocks) and keep the XCD-contiguous order
-    a.xcd_remap = 1;
-  }
-  // the instantiation that does exactly `ksteps` steps: the tail of a run whose step count multi_K does not
-  // divide is a launch of a smaller frame, not a run-time loop bound (which cost scratch and ~10 % speed)
-  // the instantiation (kernels/multi.h PART): ghost rows computed too -> the counted test; ready words to say -> the fold block carries them
-  // (a rank of the tile decomposition: ghost columns in every launch)
-  const int part = c->plan.ghost_x > 0 ? kPartTile : ext > 0 ? kPartGhost : a.ready_epoch != 0ull ? kPartReady : kPartPlain;
-  const MultiKernel& k = kMultiKernels[multi_row(std::min(ksteps, kMaxMultiSteps), c->plan.multi_geom, c->plan.fused ? kMultiTermsFused : c->plan.multi_terms, part)];   // ksteps <= multi_K, or 4 in the tail of a K = 3 run (lbm_run)
-  k.fn<<<dim3(blocks + 1), dim3(k.lanes), k.lds_bytes, s>>>(a);
+  const MultiKernel& k = kMultiKernels[l.row];
+  k.fn<<<dim3(l.launched_blocks + 1), dim3(l.lanes), k.lds_bytes, s>>>(a);                            // + the fold block
 }
 
-// Every instantiation of lbm_tile_kernel, one row per (geometry, FULL, terms) with what a launch of it needs.  The terms index of a
-// row: double-precision sum|u| terms, float ones (LBM_FLAG_FAST_AVVELS), the fused arithmetic (LBM_FLAG_FUSED_ARITH; never with the float terms: create_impl).
+// Every instantiation of lbm_tile_kernel, one row per (geometry, FULL, terms; lbm_geometry.h tile_row) with what a launch of it needs.
 struct TileKernel { void (*fn)(TileArgs); int block; size_t lds_bytes; };
-constexpr int kTileTermsFused = 2, kTileTerms = 3, kTileRows = 4 * 2 * kTileTerms;
 static_assert(kTermsDouble == 0 && kTermsFloat == 1, "the values index the table");
-constexpr int tile_row(int t, int h, bool full, int terms) { return (((t == 8 ? 2 : 0) + (h == 4 ? 1 : 0)) * 2 + (full ? 1 : 0)) * kTileTerms + terms; }
 template <int ROW>
 constexpr TileKernel tile_kernel_row()
 {
@@ -323,24 +320,32 @@ template <size_t... ROW>
 constexpr std::array<TileKernel, sizeof...(ROW)> tile_kernel_rows(std::index_sequence<ROW...>) { return {{tile_kernel_row<static_cast<int>(ROW)>()...}}; }
 constexpr auto kTileKernels = tile_kernel_rows(std::make_index_sequence<kTileRows>{});
 
-void launch_tile(lbm_ctx* c, const TileArgs& a, hipStream_t s)
+// One launch of lbm_tile_kernel by its plan (lbm_plan.cpp plan_tile_launch); every launch of such a run has this form.
+void launch_tile(lbm_ctx* c, const LaunchPlan& l, bool accel_last, hipStream_t s)
 {
-  const TileKernel& k = kTileKernels[tile_row(c->plan.tile_T, c->plan.tile_H, a.ksteps == c->plan.tile_H, c->plan.fused ? kTileTermsFused : c->plan.fast_avvels ? kTermsFloat : kTermsDouble)];
-  k.fn<<<dim3(c->plan.n_tiles + 1), dim3(k.block), k.lds_bytes, s>>>(a);   // + the fold block
+  TileArgs a{};
+  a.src = c->grid[c->cur]; a.dst = c->grid[c->cur ^ 1];
+  a.mask = c->mask; a.ps = c->plan.ps; a.nx = c->p.nx; a.ny = c->plan.nyl; a.tiles_x = l.tiles_x;
+  a.ksteps = l.k;
+  a.single_max = c->plan.tile_single_max;
+  a.omega = c->p.omega; a.accel_w1 = c->plan.accel_w1; a.accel_w2 = c->plan.accel_w2;
+  a.accel_row = c->plan.accel_row; a.accel_last = accel_last ? 1 : 0;
+  a.partials_out = c->partials[c->parity];
+  a.prev_partials = c->partials[c->parity ^ 1];
+  a.n_prev = c->n_prev; a.n_prev_vecs = c->n_prev > 0 ? c->n_prev_vecs : 0;
+  a.sums = c->sums; a.counter = c->counter;
+  const TileKernel& k = kTileKernels[l.row];
+  k.fn<<<dim3(l.launched_blocks + 1), dim3(k.block), k.lds_bytes, s>>>(a);   // + the fold block
 }
 
-// Profile mode of lbm_run (lbm_set_profile): a pooled timing event recorded on `s`; nullptr when off.
-hipEvent_t prof_stamp(lbm_ctx* c, hipStream_t s)
+// The state flip after a launch (d2q9-bgk.c:376-378): it left `vecs` step vectors of n_partials per-block sums to fold and made `steps` steps.
+void after_launch(lbm_ctx* c, int n_partials, int vecs, int steps)
 {
-  if (!c->profile) return nullptr;
-  if (c->prof_used == c->prof_pool.size()) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    c->prof_pool.push_back(e);
-  }
-  hipEvent_t e = c->prof_pool[c->prof_used++];
-  if (hipEventRecord(e, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return e;
+  c->n_prev = n_partials;
+  c->n_prev_vecs = vecs;
+  c->parity ^= 1;
+  c->cur ^= 1;
+  c->run_done += steps;
 }
 
 int begin_run(lbm_ctx* c, int n_steps, hipStream_t s)
@@ -391,14 +396,13 @@ int fold_last(lbm_ctx* c, hipStream_t s, bool final = false)
   return 0;
 }
 
-// Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
-// divide is split into 3s and 4s where that avoids a K = 2 / K = 1 launch at the end (8192 x 8192, us per launch: K = 1 870,
-// K = 2 1000, K = 3 1050, K = 4 1290) — at K = 3: n = 3a + 4 or 3a + 8; at K = 4: n = 4a + 3, 4a + 6 or 4a + 9.  Whole periodic
-// grids (the frame wraps) and row partitions that keep four ghost rows.  A function of (K, ghost, left) only, so every
-// rank of a partitioned run makes the same sequence of macro-steps.
-int next_multi_k(const lbm_ctx* c, int left)
+// The end of a run on stream `s`: the closing event, the launch count lbm_last_run_kernel_ms reports, the last fold (which resets the counter).
+int end_run(lbm_ctx* c, int launches, hipStream_t s)
 {
-  return lbm_plan_next(c->plan.multi_K, (c->plan.self_periodic || c->plan.ghost >= 4) ? 1 : 0, c->plan.multi_tail4 ? 1 : 0, left);
+  HIP_TRY(hipEventRecord(c->ev_end, s));
+  c->ev_launches = launches;
+  c->ev_valid = true;
+  return fold_last(c, s, /*final=*/true);
 }
 
 constexpr int kGraphSteps = 64;   // even: the source/destination roles and the partial-sum parity return to their start
@@ -415,10 +419,7 @@ void full_step(lbm_ctx* c, bool accel_next, hipStream_t s)
   a.prev_partials = c->partials[c->parity ^ 1];
   a.n_prev = c->n_prev;
   launch_step(c, a, c->plan.n_part_full, s);
-  c->n_prev = c->plan.n_part_full;
-  c->n_prev_vecs = 1;
-  c->parity ^= 1;
-  c->cur ^= 1;
+  after_launch(c, c->plan.n_part_full, 1, 1);
 }
 
 // Captures kGraphSteps mid-run steps (previous partials to fold, accelerate epilogue on) starting
@@ -427,12 +428,12 @@ void full_step(lbm_ctx* c, bool accel_next, hipStream_t s)
 int ensure_graph(lbm_ctx* c, hipStream_t s)
 {
   if (c->graph_exec[c->cur]) return 0;
-  const int cur = c->cur, parity = c->parity, n_prev = c->n_prev;
+  const int cur = c->cur, parity = c->parity, n_prev = c->n_prev, run_done = c->run_done;
   hipGraph_t graph = nullptr;
   HIP_TRY(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
   for (int i = 0; i < kGraphSteps; ++i) full_step(c, true, s);
   hipError_t e = hipStreamEndCapture(s, &graph);
-  c->cur = cur; c->parity = parity; c->n_prev = n_prev;   // nothing ran
+  c->cur = cur; c->parity = parity; c->n_prev = n_prev; c->run_done = run_done;   // nothing ran
   HIP_TRY(e);
   e = hipGraphInstantiate(&c->graph_exec[cur], graph, nullptr, nullptr, 0);
   (void)hipGraphDestroy(graph);
@@ -495,22 +496,14 @@ static int create_impl(lbm_ctx** out, int plan_status, const lbm_internal::Conte
   c->device = device;
 
   auto fail = [&](void) { lbm_destroy(c); return 1; };
-#define HIP_TRY_C(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return fail();                                                                         \
-    }                                                                                        \
-  } while (0)
 
-  HIP_TRY_C(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY_C(hipEventCreate(&c->ev_begin));
-  HIP_TRY_C(hipEventCreate(&c->ev_end));
+  HIP_TRY_OR(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), return fail());
+  HIP_TRY_OR(hipEventCreate(&c->ev_begin), return fail());
+  HIP_TRY_OR(hipEventCreate(&c->ev_end), return fail());
   const size_t grid_floats = static_cast<size_t>(plan.grid_floats);
   for (int g = 0; g < 2; ++g) {
-    HIP_TRY_C(hipMalloc(&c->grid_alloc[g], sizeof(float) * grid_floats));
-    HIP_TRY_C(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(float) * grid_floats, c->stream));
+    HIP_TRY_OR(hipMalloc(&c->grid_alloc[g], sizeof(float) * grid_floats), return fail());
+    HIP_TRY_OR(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(float) * grid_floats, c->stream), return fail());
     c->grid[g] = c->grid_alloc[g] + 64;
   }
   if (knobs.debug_addr)      // placement experiments (scripts/experiments/alloc_order.py)
@@ -530,28 +523,28 @@ static int create_impl(lbm_ctx** out, int plan_status, const lbm_internal::Conte
       return obstacles_global + static_cast<size_t>(g) * nx;
     });
   }
-  HIP_TRY_C(hipMalloc(&c->mask, sizeof(uint32_t) * mwords));
-  HIP_TRY_C(hipMemcpy(c->mask, bits.data(), sizeof(uint32_t) * mwords, hipMemcpyHostToDevice));
+  HIP_TRY_OR(hipMalloc(&c->mask, sizeof(uint32_t) * mwords), return fail());
+  HIP_TRY_OR(hipMemcpy(c->mask, bits.data(), sizeof(uint32_t) * mwords, hipMemcpyHostToDevice), return fail());
   // halo buffers: 2 send + 2 recv, each [3][nxp]
   const size_t hb = static_cast<size_t>(3) * plan.nxp;
-  HIP_TRY_C(hipMalloc(&c->halo_alloc, sizeof(float) * hb * 4));
-  HIP_TRY_C(hipMemsetAsync(c->halo_alloc, 0, sizeof(float) * hb * 4, c->stream));
+  HIP_TRY_OR(hipMalloc(&c->halo_alloc, sizeof(float) * hb * 4), return fail());
+  HIP_TRY_OR(hipMemsetAsync(c->halo_alloc, 0, sizeof(float) * hb * 4, c->stream), return fail());
   c->send[0] = c->halo_alloc; c->send[1] = c->halo_alloc + hb;
   c->recv[0] = c->halo_alloc + 2 * hb; c->recv[1] = c->halo_alloc + 3 * hb;
   if (plan.ghost > 0) {
-    for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack[i], sizeof(float) * plan.pack_alloc_floats));
+    for (int i = 0; i < 2; ++i) HIP_TRY_OR(hipMalloc(&c->macro_pack[i], sizeof(float) * plan.pack_alloc_floats), return fail());
     if (plan.ghost_x > 0)             // a tile rank's column messages: here, never during a run (ensure_sums)
-      for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->macro_pack_x[i], sizeof(float) * 2 * plan.pack_floats_x));
+      for (int i = 0; i < 2; ++i) HIP_TRY_OR(hipMalloc(&c->macro_pack_x[i], sizeof(float) * 2 * plan.pack_floats_x), return fail());
   }
   // the kernels the plan names: lbm_multi_kernel's of its geometry, or lbm_tile_kernel's (up to 74 KB of dynamic LDS per block — two
   // 9 x R x R float buffers — above the 64 KB default limit).  Here, while the device still clears the grids: after the allocations
   // below, which wait for it, these host calls made lbm_create of a 2048 x 2048 grid 1.45 ms instead of 0.97
-  if (plan.multi_tiles_x > 0) HIP_TRY_C(raise_multi_lds_limits_for(plan.multi_geom));
-  else if (plan.tile_kernel) HIP_TRY_C(raise_lds_limits(kTileKernels, 0, kTileRows));
-  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * plan.partials_cap));
-  HIP_TRY_C(hipMalloc(&c->fold_scratch, sizeof(double) * kFoldSlices * 8));
-  HIP_TRY_C(hipMalloc(&c->counter, sizeof(int)));
-  HIP_TRY_C(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream));
+  if (plan.multi_tiles_x > 0) HIP_TRY_OR(raise_multi_lds_limits_for(plan.multi_geom), return fail());
+  else if (plan.tile_kernel) HIP_TRY_OR(raise_lds_limits(kTileKernels, 0, kTileRows), return fail());
+  for (int i = 0; i < 2; ++i) HIP_TRY_OR(hipMalloc(&c->partials[i], sizeof(double) * plan.partials_cap), return fail());
+  HIP_TRY_OR(hipMalloc(&c->fold_scratch, sizeof(double) * kFoldSlices * 8), return fail());
+  HIP_TRY_OR(hipMalloc(&c->counter, sizeof(int)), return fail());
+  HIP_TRY_OR(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream), return fail());
   if (ensure_sums(c, 1)) return fail();                   // max(max_iters, 4096) steps before any run starts (ensure_sums)
   // initial state (d2q9-bgk.c:880-902)
   {
@@ -559,10 +552,9 @@ static int create_impl(lbm_ctx** out, int plan_status, const lbm_internal::Conte
     const size_t cells = static_cast<size_t>(plan.ncells_storage);
     const int blocks = static_cast<int>((cells + 255) / 256);
     hipLaunchKernelGGL(lbm_init_kernel, dim3(blocks), dim3(256), 0, c->stream, c->grid[0], static_cast<size_t>(plan.ps), cells, w0, w1, w2);
-    HIP_TRY_C(hipGetLastError());
+    HIP_TRY_OR(hipGetLastError(), return fail());
   }
-  HIP_TRY_C(hipStreamSynchronize(c->stream));
-#undef HIP_TRY_C
+  HIP_TRY_OR(hipStreamSynchronize(c->stream), return fail());
   *out = c;
   return 0;
 }
@@ -665,7 +657,7 @@ int lbm_destroy(lbm_ctx* c)
   if (c->counter) (void)hipFree(c->counter);
   if (c->ev_begin) (void)hipEventDestroy(c->ev_begin);
   if (c->ev_end) (void)hipEventDestroy(c->ev_end);
-  for (hipEvent_t e : c->prof_pool) (void)hipEventDestroy(e);
+  c->prof.destroy();
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return 0;
@@ -679,52 +671,23 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
   if (n_steps == 0) return 0;
   HIP_TRY(hipSetDevice(c->device));
   hipStream_t s = c->stream;
-  c->prof_used = 0;
+  c->prof.used = 0;
   c->prof_launches.clear();
   if (begin_run(c, n_steps, s)) return 1;
-  int tile_launches = 0;
   const KernelFamily family = family_of(c);
-  for (int t = 0; family == kFamilyMulti && t < n_steps;) {
-    // up to multi_K steps per pass over HBM (lbm_multi_kernel).  A step count that 3 does not divide is split into 3s
-    // and 4s where that avoids the K = 2 / K = 1 launch at the end (8192 x 8192, us per launch: K = 1 870, K = 2 1000,
-    // K = 3 1050, K = 4 1460): n = 3a + 4 for n mod 3 = 1, n = 3a + 8 for n mod 3 = 2 (next_multi_k; row partitions
-    // with four ghost rows split the same way).
-    const int k = next_multi_k(c, n_steps - t);
-    hipEvent_t pb = prof_stamp(c, s);
-    launch_multi(c, k, 0, /*accel_last=*/t + k < n_steps, 0, multi_tiles_for(c, k), 0, 0, /*fold=*/true, s);
-    if (c->profile) c->prof_launches.push_back({k, pb, prof_stamp(c, s)});
-    c->n_prev = multi_tiles_for(c, k);
-    c->n_prev_vecs = k;
-    c->parity ^= 1;
-    c->cur ^= 1;
-    t += k;
-    ++tile_launches;
-    if (t >= n_steps) c->ev_tile_launches = tile_launches;
-  }
-  for (int t = 0; family == kFamilyTile && t < n_steps;) {
-    // up to tile_H steps per launch (lbm_tile_kernel); every launch of such a run has this form
-    const int k = std::min(c->plan.tile_H, n_steps - t);
-    TileArgs a{};
-    a.src = c->grid[c->cur]; a.dst = c->grid[c->cur ^ 1];
-    a.mask = c->mask; a.ps = c->plan.ps; a.nx = c->p.nx; a.ny = c->plan.nyl; a.tiles_x = c->p.nx / c->plan.tile_T;
-    a.ksteps = k;
-    a.single_max = c->plan.tile_single_max;
-    a.omega = c->p.omega; a.accel_w1 = c->plan.accel_w1; a.accel_w2 = c->plan.accel_w2;
-    a.accel_row = c->plan.accel_row; a.accel_last = (t + k < n_steps) ? 1 : 0;
-    a.partials_out = c->partials[c->parity];
-    a.prev_partials = c->partials[c->parity ^ 1];
-    a.n_prev = c->n_prev; a.n_prev_vecs = c->n_prev > 0 ? c->n_prev_vecs : 0;
-    a.sums = c->sums; a.counter = c->counter;
-    const dim3 grid(c->plan.n_tiles + 1);
-    hipEvent_t pb = prof_stamp(c, s);
-    launch_tile(c, a, s);
-    if (c->profile) c->prof_launches.push_back({k, pb, prof_stamp(c, s)});
-    ++tile_launches;
-    c->n_prev = c->plan.n_tiles; c->n_prev_vecs = k;
-    c->parity ^= 1;
-    c->cur ^= 1;
-    t += k;
-    if (t >= n_steps) c->ev_tile_launches = tile_launches;
+  for (int t = 0; family != kFamilyStep && t < n_steps;) {
+    // up to multi_K steps per pass over HBM (lbm_multi_kernel; a step count that K does not divide: next_multi_k), or up to tile_H
+    // steps per launch (lbm_tile_kernel)
+    LaunchPlan l;
+    if (family == kFamilyMulti) lbm_internal::plan_launch(c->plan, c->knobs, lbm_internal::next_multi_k(c->plan, n_steps - t), 0, kLaunchWhole, c->ready_epoch != 0, &l);
+    else lbm_internal::plan_tile_launch(c->plan, n_steps - t, &l);
+    hipEvent_t pb = c->prof.stamp(s);
+    if (family == kFamilyMulti) launch_multi(c, l, /*accel_last=*/t + l.k < n_steps, /*fold=*/true, s);
+    else launch_tile(c, l, /*accel_last=*/t + l.k < n_steps, s);
+    if (c->prof.on) c->prof_launches.push_back({l.k, pb, c->prof.stamp(s)});
+    after_launch(c, l.ntiles_total, l.k, l.k);
+    t += l.k;
+    ++c->ev_tile_launches;
   }
   for (int t = 0; family == kFamilyStep && t < n_steps;) {
     // launch-bound grids: replay a captured block of kGraphSteps steps while at least one more
@@ -732,20 +695,17 @@ int lbm_run(lbm_ctx* c, int n_steps, float* av_vels)
     if (c->plan.use_graph && c->n_prev > 0 && n_steps - t > kGraphSteps) {
       if (ensure_graph(c, s)) return 1;
       HIP_TRY(hipGraphLaunch(c->graph_exec[c->cur], s));
+      c->run_done += kGraphSteps;
       t += kGraphSteps;
     } else {
-      hipEvent_t pb = prof_stamp(c, s);
+      hipEvent_t pb = c->prof.stamp(s);
       full_step(c, /*accel_next=*/t + 1 < n_steps, s);
-      if (c->profile) c->prof_launches.push_back({1, pb, prof_stamp(c, s)});
+      if (c->prof.on) c->prof_launches.push_back({1, pb, c->prof.stamp(s)});
       t += 1;
     }
   }
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(c->ev_end, s));
-  c->ev_launches = family != kFamilyStep ? c->ev_tile_launches : n_steps;
-  c->ev_valid = true;
-  if (fold_last(c, s, /*final=*/true)) return 1;
-  c->run_done = n_steps;
+  if (end_run(c, family != kFamilyStep ? c->ev_tile_launches : n_steps, s)) return 1;
   // blocking waits: polling hipStreamQuery first measured no faster on 20-step runs of a 1-rank ring of 8192 x 1024 rows
   // (52.70 us/step blocking, 52.63 polling; profiles/r03/ab_ring_spin_8192x1024_s20.txt)
   if (av_vels) {
@@ -948,17 +908,8 @@ int lbm_step_finish(lbm_ctx* c, void* stream)
 {
   if (!c) { lbm_internal::set_error("lbm_step_finish: null context"); return 1; }
   hipStream_t s = pick_stream(c, stream);
-  c->n_prev = c->plan.n_part_interior + c->plan.n_part_boundary;
-  c->n_prev_vecs = 1;
-  c->parity ^= 1;
-  c->cur ^= 1;                                                              // d2q9-bgk.c:376-378
-  c->run_done += 1;
-  if (c->run_done == c->run_steps) {
-    HIP_TRY(hipEventRecord(c->ev_end, s));
-    c->ev_launches = c->run_steps * ((c->plan.n_part_interior > 0 ? 1 : 0) + 1);
-    c->ev_valid = true;
-    if (fold_last(c, s, /*final=*/true)) return 1;
-  }
+  after_launch(c, c->plan.n_part_interior + c->plan.n_part_boundary, 1, 1);
+  if (c->run_done == c->run_steps) return end_run(c, c->run_steps * ((c->plan.n_part_interior > 0 ? 1 : 0) + 1), s);
   return 0;
 }
 
@@ -1041,12 +992,10 @@ static int macro_pack_cols_launch(lbm_ctx* c, bool unpack, hipStream_t s)
   // incoming: the ghost columns before the owned ones (from the west, dir 0) and after them (from the east, dir 1)
   a.col[0] = unpack ? 0 : gx;
   a.col[1] = unpack ? gx + c->plan.nxl : c->plan.nxl;
-  // the widest access every row segment is aligned for, in the grid and in the messages (the test of p2p_push_cols)
-  auto all_mult = [&](int m) { return gx % m == 0 && c->plan.nxl % m == 0 && c->p.nx % m == 0 && c->plan.ps % m == 0; };
-  const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
-  const long long work = 18LL * c->plan.nyl * (gx / per);                 // vectors of the launch
   if (18LL * c->plan.nyl * gx >= (1LL << 30)) { lbm_internal::set_error("lbm_macro_pack_x: column messages too large for the kernel's 32-bit indices"); return 1; }
-  const dim3 grid(static_cast<unsigned>(std::max(1LL, std::min(4096LL, (work + 1023) / 1024))));
+  const lbm_internal::ColumnMessagePlan m = lbm_internal::plan_column_message(c->plan, gx, 4096, nullptr, 0);
+  const dim3 grid(m.blocks);
+  const int per = m.per;
   if (per == 4) hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<f4>, grid, dim3(256), 0, s, a);
   else if (per == 2) hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<f2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(lbm_macro_pack_cols_kernel<float>, grid, dim3(256), 0, s, a);
@@ -1083,151 +1032,58 @@ int lbm_macro_prepare(lbm_ctx* c, int n_steps, void* stream)
   return begin_run(c, n_steps, pick_stream(c, stream));
 }
 
-// The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
-// up to at most the ghost rows, group_max at most.  Launch i of a group advances, besides the owned rows, ext(i) = the steps of the
-// launches AFTER it in the group ghost rows on each side: what those launches read in place of exchanged rows.
-struct GroupPlan {
-  int n = 0, total = 0;
-  int k[kMaxGroup] = {};
-  int ext(int i) const { int e = 0; for (int j = i + 1; j < n; ++j) e += k[j]; return e; }
-};
-static GroupPlan plan_group(const lbm_ctx* c, int left)
-{
-  GroupPlan g;
-  g.n = lbm_plan_group_for(c->plan.multi_K, (c->plan.self_periodic || c->plan.ghost >= 4) ? 1 : 0, c->plan.multi_tail4 ? 1 : 0, c->plan.ghost,
-                           std::min(c->plan.group_max, static_cast<int>(kMaxGroup)), left, g.k, kMaxGroup);   // next_multi_k's launches
-  for (int i = 0; i < g.n; ++i) g.total += g.k[i];
-  return g;
-}
-static GroupPlan macro_group(const lbm_ctx* c) { return plan_group(c, c->run_steps - c->run_done); }
+static GroupPlan macro_group(const lbm_ctx* c) { return lbm_internal::plan_group(c->plan, c->run_steps - c->run_done); }
 
 int lbm_macro_next_steps(const lbm_ctx* c) { return (c && c->plan.ghost > 0 && c->run_done < c->run_steps) ? macro_group(c).total : 0; }
 int lbm_macro_next_launches(const lbm_ctx* c) { return (c && c->plan.ghost > 0 && c->run_done < c->run_steps) ? macro_group(c).n : 0; }
 
-// Tile rows of a launch of k steps that also advances `ext` ghost rows per side (tile row 0 starts at storage row ghost - ext): the
-// first `bottom_edge_rows` and the last `top_edge_rows` tile rows read exchanged rows (edge launch, after the exchange); the
-// `interior_rows` between them do not: the rows they need — their own, k below and k above — are owned rows.  (The last tile row
-// may hold fewer rows than a launch makes steps: the ring of the row below then reaches the ghost rows, and the top edge is two rows.)
-// (Tile ranks: the first `left_cols` and the last `right_cols` tile COLUMNS read exchanged columns as well — a tile's first sub-step reads
-// multi_ex(k - 1) + 1 columns beyond its own on each side; the interior is then the rectangle inside all four.)
-struct MacroRows { int bottom_edge_rows, interior_rows, top_edge_rows, left_cols, right_cols; };
-static MacroRows macro_rows(const lbm_ctx* c, int k, int ext = 0)
+// Launch i of a group over `which` of its tiles (lbm_plan.cpp plan_launch: all of them, those that read no exchanged cell, or the rest),
+// and the launch itself: called by both native loops and by the split-phase entry points below.
+static LaunchPlan group_launch_plan(const lbm_ctx* c, const GroupPlan& g, int i, int which)
 {
-  const int ty = multi_ty(k, c->plan.multi_geom);
-  const int ext_y = ext_rows(c, ext);
-  const int first = c->plan.ghost_rows - ext_y, rows = c->plan.nyl + 2 * ext_y;
-  const int nty = (rows + ty - 1) / ty;
-  const int lo = c->plan.ghost_rows, hi = c->plan.ghost_rows + c->plan.nyl;      // the owned rows [lo, hi)
-  int b = 0, t = 0;
-  if (c->plan.ghost_rows > 0) {                                        // (a column block wraps in y: no tile row reads an exchanged row)
-    while (b < nty && first + b * ty - k < lo) ++b;
-    while (t < nty - b && std::min(first + (nty - t) * ty, first + rows) - 1 + k >= hi) ++t;
-  }
-  int l = 0, r = 0;
-  if (c->plan.ghost_x > 0) {
-    const int tx = c->plan.multi_tx, ntx = c->plan.multi_tiles_x, reach = multi_ex(k - 1) + 1;
-    const int xlo = c->plan.ghost_x, xhi = c->plan.ghost_x + c->plan.nxl;         // the owned columns [xlo, xhi)
-    while (l < ntx && l * tx - reach < xlo) ++l;
-    while (r < ntx - l && (ntx - r) * tx - 1 + reach >= xhi) ++r;
-    if (ntx - l - r <= 0) return {nty, 0, 0, 0, 0};               // no tile column inside the rim: everything waits for the exchange
-  }
-  return {b, nty - b - t, t, l, r};
+  LaunchPlan l;
+  lbm_internal::plan_launch(c->plan, c->knobs, g.k[i], g.ext(i), which, /*says_ready=*/c->ready_epoch != 0, &l);
+  return l;
 }
-
-// The tiles of a tile rank's launch of k steps + ext as rectangles: the interior (at most one), or the rim around it (at most four).
-static int macro_rects(const lbm_ctx* c, int k, int ext, bool interior, MultiArgs::Rect* out)
+static void launch_group(lbm_ctx* c, const GroupPlan& g, int i, const LaunchPlan& l, bool more_after_group, hipStream_t s)
 {
-  const MacroRows m = macro_rows(c, k, ext);
-  const int ntx = c->plan.multi_tiles_x, mid = m.interior_rows;
-  int n = 0;
-  auto add = [&](int ty0, int nrows, int tx0, int cols) { if (nrows > 0 && cols > 0) out[n++] = MultiArgs::Rect{ty0, tx0, cols, nrows * cols}; };
-  if (interior) {
-    add(m.bottom_edge_rows, mid, m.left_cols, ntx - m.left_cols - m.right_cols);
-  } else {
-    add(0, m.bottom_edge_rows, 0, ntx);
-    add(m.bottom_edge_rows + mid, m.top_edge_rows, 0, ntx);
-    add(m.bottom_edge_rows, mid, 0, m.left_cols);
-    add(m.bottom_edge_rows, mid, ntx - m.right_cols, m.right_cols);
-  }
-  return n;
+  launch_multi(c, l, /*accel_last=*/i + 1 < g.n || more_after_group, /*fold=*/c->n_prev > 0, s);
 }
-
-// The launches of a group, called by both native loops and by the split-phase entry points below.
-static void launch_group_interior(lbm_ctx* c, const GroupPlan& g, bool more_after_group, hipStream_t s)
+// state flip after launch i of a group, made as `launches` launches
+static void group_launch_done(lbm_ctx* c, const GroupPlan& g, int i, const LaunchPlan& l, int launches)
 {
-  const int k = g.k[0], ext = g.ext(0);
-  if (c->plan.ghost_x > 0) {                                            // tile rank: the rectangle inside the rim
-    MultiArgs::Rect rects[4];
-    const int n = macro_rects(c, k, ext, true, rects);
-    launch_multi(c, k, ext, /*accel_last=*/g.n > 1 || more_after_group, 0, 0, 0, 0, /*fold=*/c->n_prev > 0, s, rects, n);
-    return;
-  }
-  const MacroRows r = macro_rows(c, k, ext);
-  launch_multi(c, k, ext, /*accel_last=*/g.n > 1 || more_after_group, r.bottom_edge_rows * c->plan.multi_tiles_x, r.interior_rows * c->plan.multi_tiles_x, 0, 0,
-               /*fold=*/c->n_prev > 0, s);
-}
-static void launch_group_edge(lbm_ctx* c, const GroupPlan& g, bool more_after_group, hipStream_t s)
-{
-  const int k = g.k[0], ext = g.ext(0);
-  if (c->plan.ghost_x > 0) {                                            // tile rank: the rim, four rectangles at most
-    MultiArgs::Rect rects[4];
-    const int n = macro_rects(c, k, ext, false, rects);
-    launch_multi(c, k, ext, /*accel_last=*/g.n > 1 || more_after_group, 0, 0, 0, 0, /*fold=*/c->n_prev > 0, s, rects, n);
-    return;
-  }
-  const MacroRows r = macro_rows(c, k, ext);
-  launch_multi(c, k, ext, /*accel_last=*/g.n > 1 || more_after_group, 0, r.bottom_edge_rows * c->plan.multi_tiles_x,
-               (r.bottom_edge_rows + r.interior_rows) * c->plan.multi_tiles_x, r.top_edge_rows * c->plan.multi_tiles_x, /*fold=*/c->n_prev > 0, s);
-}
-static void launch_group_whole(lbm_ctx* c, const GroupPlan& g, int i, bool more_after_group, hipStream_t s)   // launch i of the group over all its tiles
-{
-  launch_multi(c, g.k[i], g.ext(i), /*accel_last=*/i + 1 < g.n || more_after_group, 0, multi_tiles_for(c, g.k[i], g.ext(i)), 0, 0, /*fold=*/c->n_prev > 0, s);
-}
-// state flip after launch i of a group (d2q9-bgk.c:376-378)
-static void group_launch_done(lbm_ctx* c, const GroupPlan& g, int i, int launches)
-{
-  c->n_prev = multi_tiles_for(c, g.k[i], g.ext(i));
-  c->n_prev_vecs = g.k[i];
-  c->parity ^= 1;
-  c->cur ^= 1;
-  c->run_done += g.k[i];
+  after_launch(c, l.ntiles_total, g.k[i], g.k[i]);
   c->ev_tile_launches += launches;
+}
+
+// The split-phase calls of a group's first launch: `which` of its tiles, if it has any; whichever of the launches of a macro-step comes
+// first folds the previous launch's sums.
+static int macro_launch(lbm_ctx* c, int which, void* stream, const char* not_k_step, const char* no_steps)
+{
+  if (!c || c->plan.ghost == 0) { lbm_internal::set_error(not_k_step); return 1; }
+  if (c->run_done >= c->run_steps) { lbm_internal::set_error(no_steps); return 1; }
+  const GroupPlan g = macro_group(c);
+  const LaunchPlan l = group_launch_plan(c, g, 0, which);
+  if (which == kLaunchInterior && l.nblocks == 0) return 0;   // no tile whose rings stay inside the owned cells
+  launch_group(c, g, 0, l, c->run_done + g.total < c->run_steps, pick_stream(c, stream));
+  HIP_TRY(hipGetLastError());
+  c->n_prev = 0;   // folded by this launch's block 0
+  return 0;
 }
 
 int lbm_macro_interior(lbm_ctx* c, void* stream)
 {
-  if (!c || c->plan.ghost == 0) { lbm_internal::set_error("lbm_macro_interior: not a K-step context"); return 1; }
-  if (c->run_done >= c->run_steps) { lbm_internal::set_error("lbm_macro_interior: no steps left; call lbm_macro_prepare"); return 1; }
-  const GroupPlan g = macro_group(c);
-  if (macro_rows(c, g.k[0], g.ext(0)).interior_rows > 0) {   // tile rows whose rings stay inside the owned rows
-    launch_group_interior(c, g, c->run_done + g.total < c->run_steps, pick_stream(c, stream));
-    HIP_TRY(hipGetLastError());
-    c->n_prev = 0;   // folded by this launch's block 0
-  }
-  return 0;
+  return macro_launch(c, kLaunchInterior, stream, "lbm_macro_interior: not a K-step context", "lbm_macro_interior: no steps left; call lbm_macro_prepare");
 }
 
 int lbm_macro_edge(lbm_ctx* c, void* stream)
 {
-  if (!c || c->plan.ghost == 0) { lbm_internal::set_error("lbm_macro_edge: not a K-step context"); return 1; }
-  if (c->run_done >= c->run_steps) { lbm_internal::set_error("lbm_macro_edge: no steps left; call lbm_macro_prepare"); return 1; }
-  const GroupPlan g = macro_group(c);
-  // whichever of the two launches of a macro-step comes first folds the previous launch's sums
-  launch_group_edge(c, g, c->run_done + g.total < c->run_steps, pick_stream(c, stream));
-  HIP_TRY(hipGetLastError());
-  c->n_prev = 0;
-  return 0;
+  return macro_launch(c, kLaunchEdge, stream, "lbm_macro_edge: not a K-step context", "lbm_macro_edge: no steps left; call lbm_macro_prepare");
 }
 
 int lbm_macro_all(lbm_ctx* c, void* stream)
 {
-  if (!c || c->plan.ghost == 0) { lbm_internal::set_error("lbm_macro_all: not a K-step context"); return 1; }
-  if (c->run_done >= c->run_steps) { lbm_internal::set_error("lbm_macro_all: no steps left; call lbm_macro_prepare"); return 1; }
-  const GroupPlan g = macro_group(c);
-  launch_group_whole(c, g, 0, c->run_done + g.total < c->run_steps, pick_stream(c, stream));
-  HIP_TRY(hipGetLastError());
-  c->n_prev = 0;
-  return 0;
+  return macro_launch(c, kLaunchWhole, stream, "lbm_macro_all: not a K-step context", "lbm_macro_all: no steps left; call lbm_macro_prepare");
 }
 
 int lbm_macro_finish(lbm_ctx* c, void* stream)
@@ -1237,19 +1093,15 @@ int lbm_macro_finish(lbm_ctx* c, void* stream)
   hipStream_t s = pick_stream(c, stream);
   const GroupPlan g = macro_group(c);
   const bool more = c->run_done + g.total < c->run_steps;
-  group_launch_done(c, g, 0, 2);
+  group_launch_done(c, g, 0, group_launch_plan(c, g, 0, kLaunchWhole), 2);
   // the rest of the group: launches over all tiles that read the ghost rows the first one advanced — no exchange in between
   for (int i = 1; i < g.n; ++i) {
-    launch_group_whole(c, g, i, more, s);
+    const LaunchPlan l = group_launch_plan(c, g, i, kLaunchWhole);
+    launch_group(c, g, i, l, more, s);
     HIP_TRY(hipGetLastError());
-    group_launch_done(c, g, i, 1);
+    group_launch_done(c, g, i, l, 1);
   }
-  if (c->run_done == c->run_steps) {
-    HIP_TRY(hipEventRecord(c->ev_end, s));
-    c->ev_launches = c->ev_tile_launches;
-    c->ev_valid = true;
-    if (fold_last(c, s, /*final=*/true)) return 1;
-  }
+  if (c->run_done == c->run_steps) return end_run(c, c->ev_tile_launches, s);
   return 0;
 }
 
@@ -1324,8 +1176,8 @@ int lbm_last_run_kernel_ms(lbm_ctx* c, double* ms, int* launches)
 int lbm_set_profile(lbm_ctx* c, int on)
 {
   if (!c) { lbm_internal::set_error("lbm_set_profile: null context"); return 1; }
-  c->profile = on != 0;
-  if (!c->profile) c->prof_launches.clear();
+  c->prof.on = on != 0;
+  if (!c->prof.on) c->prof_launches.clear();
   return 0;
 }
 

@@ -1,6 +1,7 @@
 // lbm_p2p_impl.h — host half of the peer-to-peer halo transport (include/lbm_d2q9_p2p.h).
 // Included at the end of lbm_kernels.hip: it drives the K-step launches of a context directly
-// (launch_multi, begin_run, fold_last) and owns the streams / events / mapped peer memory of one rank.
+// (group_launch_plan / launch_group, begin_run, fold_last) and owns the streams / events / mapped peer memory of one rank.
+// Which tiles a launch covers, and whether a push may overtake the interior launch (edge_rows_suffice), is lbm_plan.cpp's to say.
 //
 // Per GROUP of launches (plan_group: the launches next_multi_k plans — K steps each, 3s and 4s at the end — for as long as their steps
 // add up to at most the ghost rows; two 4-step launches on 8 ghost rows by default) of one rank, reference lines d2q9-bgk.c:
@@ -83,10 +84,8 @@ struct lbm_p2p {
   bool connected = false;
   unsigned long long epoch = 0, reduce_round = 0;
   long long timeout_ticks = 0;
-  // lbm_p2p_set_profile: timing events around the launches of a run (a pool, grown on demand and reused)
-  bool profile = false, phases_valid = false;
-  std::vector<hipEvent_t> ev_pool;
-  size_t ev_used = 0;
+  EventPool ev;                        // lbm_p2p_set_profile: timing events around the launches of a run
+  bool phases_valid = false;
   hipEvent_t ev_reduce_end = nullptr;
   double phases[LBM_P2P_PHASES] = {};
 };
@@ -114,20 +113,6 @@ void p2p_unmap(lbm_p2p* t)
     }
     p = P2PPeer{};
   }
-}
-
-// Profile mode: the next pooled timing event, recorded on `s` (nullptr when the profile is off or on failure).
-hipEvent_t p2p_stamp(lbm_p2p* t, hipStream_t s)
-{
-  if (!t->profile) return nullptr;
-  if (t->ev_used == t->ev_pool.size()) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    t->ev_pool.push_back(e);
-  }
-  hipEvent_t e = t->ev_pool[t->ev_used++];
-  if (hipEventRecord(e, s) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  return e;
 }
 
 double p2p_us(hipEvent_t a, hipEvent_t b)
@@ -198,13 +183,10 @@ int p2p_push_cols(lbm_p2p* t, unsigned long long epoch, int k, hipStream_t s)
   a.wait_flags = header_of(t->window)->halo_flag_x;
   a.wait_parity = header_of(t->window)->halo_parity_x;
   a.timeout_ticks = t->timeout_ticks; a.err = t->err;
-  auto all_mult = [&](int m) {
-    return k % m == 0 && gx % m == 0 && c->plan.nxl % m == 0 && c->p.nx % m == 0 && c->plan.ps % m == 0 && pw.blob.w % m == 0 && pe.blob.w % m == 0 &&
-           pw.blob.ps % m == 0 && pe.blob.ps % m == 0 && pw.blob.nxl % m == 0 && pw.blob.ghost_x % m == 0 && pe.blob.ghost_x % m == 0;
-  };
-  const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
-  const int work = 18 * c->plan.nyl * (k / per);
-  const dim3 grid(std::max(1, std::min(kP2PPushBlocks, (work + 1023) / 1024)));
+  const long long peer[] = {pw.blob.w, pe.blob.w, static_cast<long long>(pw.blob.ps), static_cast<long long>(pe.blob.ps), pw.blob.nxl, pw.blob.ghost_x, pe.blob.ghost_x};
+  const lbm_internal::ColumnMessagePlan m = lbm_internal::plan_column_message(c->plan, k, kP2PPushBlocks, peer, 7);
+  const dim3 grid(m.blocks);
+  const int per = m.per;
   if (per == 4) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f4>, grid, dim3(256), 0, s, a);
   else if (per == 2) hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<f2>, grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(lbm_p2p_push_cols_kernel<float>, grid, dim3(256), 0, s, a);
@@ -283,7 +265,7 @@ int p2p_reduce(lbm_p2p* t, int n_steps, double* tot_u_per_step)
     a.err = t->err;
     hipLaunchKernelGGL(lbm_p2p_allreduce_kernel, dim3(t->nranks), dim3(256), 0, cs, a);
     HIP_TRY(hipGetLastError());
-    t->ev_reduce_end = p2p_stamp(t, cs);
+    t->ev_reduce_end = t->ev.stamp(cs);
     HIP_TRY(hipStreamSynchronize(cs));
     std::memcpy(tot_u_per_step + t0, t->reduce_out, sizeof(double) * n);     // host-mapped: the kernel wrote it in place
   }
@@ -333,9 +315,9 @@ int p2p_run_one_step(lbm_p2p* t, int n_steps, double* tot_u_per_step)
   unsigned long long epoch = t->epoch + 1;
   bind(epoch, epoch);
   const std::chrono::steady_clock::time_point h0 = std::chrono::steady_clock::now();
-  hipEvent_t e_run0 = p2p_stamp(t, cs);
+  hipEvent_t e_run0 = t->ev.stamp(cs);
   if (lbm_step_prepare(c, n_steps, cs)) return 1;              // step-0 accelerate_flow + the messages of the first step
-  hipEvent_t e_steps0 = p2p_stamp(t, cs);
+  hipEvent_t e_steps0 = t->ev.stamp(cs);
   P2PWindowHeader* mine = header_of(t->window);
   for (int step = 0; step < n_steps; ++step, ++epoch) {
     hipLaunchKernelGGL(lbm_p2p_signal_wait_kernel, dim3(1), dim3(64), 0, cs, &header_of(ps.window)->halo_flag[1], &header_of(pn.window)->halo_flag[0],
@@ -346,11 +328,11 @@ int p2p_run_one_step(lbm_p2p* t, int n_steps, double* tot_u_per_step)
     if (lbm_step_interior(c, cs) || lbm_step_boundary(c, cs) || lbm_step_finish(c, cs)) { (void)hipStreamSynchronize(cs); return 1; }
   }
   t->epoch = epoch - 1;
-  hipEvent_t e_steps1 = p2p_stamp(t, cs);
+  hipEvent_t e_steps1 = t->ev.stamp(cs);
   const std::chrono::steady_clock::time_point h_enq = std::chrono::steady_clock::now();
   if (p2p_reduce(t, n_steps, tot_u_per_step)) return 1;
   if (p2p_check_error(t)) return 1;
-  if (t->profile) {
+  if (t->ev.on) {
     auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     double* ph = t->phases;
     std::fill(ph, ph + LBM_P2P_PHASES, 0.0);
@@ -416,16 +398,8 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   // real link is slower than local memory — a push that outlasts the interior launch would be the critical path
   t->push_blocks_edge = std::max(1, knobs.p2p_push_blocks);
   auto fail = [&]() { lbm_p2p_destroy(t); return 1; };
-#define P2P_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return fail();                                                                         \
-    }                                                                                        \
-  } while (0)
-  P2P_TRY(hipEventCreateWithFlags(&t->edge_done, hipEventDisableTiming));
-  P2P_TRY(hipEventCreateWithFlags(&t->interior_done, hipEventDisableTiming));
+  HIP_TRY_OR(hipEventCreateWithFlags(&t->edge_done, hipEventDisableTiming), return fail());
+  HIP_TRY_OR(hipEventCreateWithFlags(&t->interior_done, hipEventDisableTiming), return fail());
   // exported window: flags + reduce slots.  Uncached device memory, so that a flag raised by a peer is seen
   // by a kernel that is already running here; fine-grained, then ordinary memory as fall-backs.
   t->reduce_cap = static_cast<size_t>(std::max(ctx->p.max_iters, 4096));
@@ -442,7 +416,7 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   const int want = knobs.p2p_window;
   if (want <= 0 && hipExtMallocWithFlags(&w, t->window_bytes, hipDeviceMallocUncached) == hipSuccess) t->window_kind = "uncached";
   else if (want <= 1 && hipExtMallocWithFlags(&w, t->window_bytes, hipDeviceMallocFinegrained) == hipSuccess) t->window_kind = "fine-grained";
-  else if (want >= 2) { (void)hipGetLastError(); P2P_TRY(hipMalloc(&w, t->window_bytes)); t->window_kind = "coarse"; }
+  else if (want >= 2) { (void)hipGetLastError(); HIP_TRY_OR(hipMalloc(&w, t->window_bytes), return fail()); t->window_kind = "coarse"; }
   else {
     (void)hipGetLastError();
     lbm_internal::set_error("lbm_p2p_create: neither an uncached nor a fine-grained device allocation is available for the flag window "
@@ -451,16 +425,15 @@ int lbm_p2p_create(lbm_p2p** out, lbm_ctx* ctx, int nranks, int rank)
   }
   (void)hipGetLastError();
   t->window = static_cast<char*>(w);
-  P2P_TRY(hipMemset(t->window, 0, t->window_bytes));
-  P2P_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->err), sizeof(int), hipHostMallocMapped));
+  HIP_TRY_OR(hipMemset(t->window, 0, t->window_bytes), return fail());
+  HIP_TRY_OR(hipHostMalloc(reinterpret_cast<void**>(&t->err), sizeof(int), hipHostMallocMapped), return fail());
   *t->err = 0;
-  P2P_TRY(hipMalloc(&t->done, 4 * sizeof(unsigned int)));
-  P2P_TRY(hipMemset(t->done, 0, 4 * sizeof(unsigned int)));
-  P2P_TRY(hipHostMalloc(reinterpret_cast<void**>(&t->reduce_out), sizeof(double) * t->reduce_cap, hipHostMallocMapped));
-  P2P_TRY(hipMalloc(&t->d_slots, sizeof(double*) * 2 * nranks));
-  P2P_TRY(hipMalloc(&t->d_flags, sizeof(unsigned long long*) * nranks));
-  P2P_TRY(hipDeviceSynchronize());
-#undef P2P_TRY
+  HIP_TRY_OR(hipMalloc(&t->done, 4 * sizeof(unsigned int)), return fail());
+  HIP_TRY_OR(hipMemset(t->done, 0, 4 * sizeof(unsigned int)), return fail());
+  HIP_TRY_OR(hipHostMalloc(reinterpret_cast<void**>(&t->reduce_out), sizeof(double) * t->reduce_cap, hipHostMallocMapped), return fail());
+  HIP_TRY_OR(hipMalloc(&t->d_slots, sizeof(double*) * 2 * nranks), return fail());
+  HIP_TRY_OR(hipMalloc(&t->d_flags, sizeof(unsigned long long*) * nranks), return fail());
+  HIP_TRY_OR(hipDeviceSynchronize(), return fail());
   *out = t;
   return 0;
 }
@@ -614,7 +587,7 @@ int lbm_p2p_destroy(lbm_p2p* t)
   if (t->d_flags) (void)hipFree(t->d_flags);
   if (t->edge_done) (void)hipEventDestroy(t->edge_done);
   if (t->interior_done) (void)hipEventDestroy(t->interior_done);
-  for (hipEvent_t e : t->ev_pool) (void)hipEventDestroy(e);
+  t->ev.destroy();
   if (t->edge) (void)hipStreamDestroy(t->edge);
   delete t;
   return 0;
@@ -636,7 +609,7 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
     return 1;
   }
   const clock::time_point h0 = clock::now();
-  t->ev_used = 0;
+  t->ev.used = 0;
   t->phases_valid = false;
   t->ev_reduce_end = nullptr;
   if (c->plan.ghost == 0) return p2p_run_one_step(t, n_steps, tot_u_per_step);
@@ -647,15 +620,7 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
     if (t->edge_stream) (void)hipStreamSynchronize(es);
     return 1;
   };
-#define P2P_RUN_TRY(expr)                                                                    \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return bail();                                                                         \
-    }                                                                                        \
-  } while (0)
-  hipEvent_t e_run0 = p2p_stamp(t, cs);
+  hipEvent_t e_run0 = t->ev.stamp(cs);
   if (begin_run(c, n_steps, cs)) return bail();                // step-0 accelerate_flow (d2q9-bgk.c:345-348)
   // The rows my neighbours need for the first macro-step (the state may have been set since the last run, and the
   // step-0 accelerate_flow has just changed row ny-2).  Edge-stream schedule: the push goes to the edge stream behind
@@ -664,108 +629,93 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
   // complement of blocks (nothing overlaps it).
   unsigned long long epoch = t->epoch + 1;
   std::vector<P2PSpan> sp_interior, sp_edge, sp_push, sp_whole;
-  GroupPlan g = plan_group(c, n_steps);                        // the same sequence of groups on every rank
+  GroupPlan g = lbm_internal::plan_group(c->plan, n_steps);                        // the same sequence of groups on every rank
   {
     P2PSpan sp;
     if (t->edge_stream) {
-      P2P_RUN_TRY(hipEventRecord(t->interior_done, cs));       // "the accelerated state is ready"
-      P2P_RUN_TRY(hipStreamWaitEvent(es, t->interior_done, 0));
-      sp.begin = p2p_stamp(t, es);
+      HIP_TRY_OR(hipEventRecord(t->interior_done, cs), return bail());       // "the accelerated state is ready"
+      HIP_TRY_OR(hipStreamWaitEvent(es, t->interior_done, 0), return bail());
+      sp.begin = t->ev.stamp(es);
       if (p2p_push(t, epoch, g.total, es)) return bail();
-      sp.end = p2p_stamp(t, es);
+      sp.end = t->ev.stamp(es);
     } else {
-      sp.begin = p2p_stamp(t, cs);
+      sp.begin = t->ev.stamp(cs);
       if (p2p_push(t, epoch, g.total, cs, /*exposed=*/true)) return bail();
-      sp.end = p2p_stamp(t, cs);
+      sp.end = t->ev.stamp(cs);
     }
-    if (t->profile) sp_push.push_back(sp);
+    if (t->ev.on) sp_push.push_back(sp);
   }
-  hipEvent_t e_steps0 = p2p_stamp(t, cs);
+  hipEvent_t e_steps0 = t->ev.stamp(cs);
   int groups = 0, launches = 0, prev_n = 0;
   bool es_has_waited = true;                                   // the edge stream has waited for the compute stream's last launch (run start: above)
   for (int done = 0; done < n_steps; ++epoch, ++groups) {
     const bool more = done + g.total < n_steps;
-    const MacroRows rows = macro_rows(c, g.k[0], g.ext(0));    // (the tile height follows the steps of the launch)
+    // launch i of the group by its plan, between two stamps of the profile
+    auto launch = [&](int i, const LaunchPlan& l, hipStream_t s, std::vector<P2PSpan>& spans) {
+      P2PSpan sp;
+      sp.begin = t->ev.stamp(s);
+      launch_group(c, g, i, l, more, s);
+      sp.end = t->ev.stamp(s);
+      if (t->ev.on) spans.push_back(sp);
+    };
     if (t->edge_stream) {
-      if (rows.interior_rows > 0) {                            // :350, beside the exchange
+      const LaunchPlan interior = group_launch_plan(c, g, 0, kLaunchInterior), edge = group_launch_plan(c, g, 0, kLaunchEdge);
+      if (interior.nblocks > 0) {                              // :350, beside the exchange
         // sources: the previous group's last launch — on this stream when that group had several launches, else its edge rows
-        if (groups > 0 && prev_n == 1) P2P_RUN_TRY(hipStreamWaitEvent(cs, t->edge_done, 0));
-        P2PSpan sp;
-        sp.begin = p2p_stamp(t, cs);
-        launch_group_interior(c, g, more, cs);
-        sp.end = p2p_stamp(t, cs);
-        if (t->profile) sp_interior.push_back(sp);
+        if (groups > 0 && prev_n == 1) HIP_TRY_OR(hipStreamWaitEvent(cs, t->edge_done, 0), return bail());
+        launch(0, interior, cs, sp_interior);
         c->n_prev = 0;
       }
       // MPI_Waitall (:364) happened on the device, at the end of the push kernel that precedes this launch
-      if (!es_has_waited) P2P_RUN_TRY(hipStreamWaitEvent(es, t->interior_done, 0));   // the previous group's launches on the compute stream
-      P2PSpan sp;
-      sp.begin = p2p_stamp(t, es);
-      launch_group_edge(c, g, more, es);                       // :365-366
-      sp.end = p2p_stamp(t, es);
-      if (t->profile) sp_edge.push_back(sp);
+      if (!es_has_waited) HIP_TRY_OR(hipStreamWaitEvent(es, t->interior_done, 0), return bail());   // the previous group's launches on the compute stream
+      launch(0, edge, es, sp_edge);                            // :365-366
       c->n_prev = 0;
-      P2P_RUN_TRY(hipGetLastError());
-      P2P_RUN_TRY(hipEventRecord(t->edge_done, es));
-      group_launch_done(c, g, 0, 2);
-      for (int i = 1; i < g.n; ++i) {                          // over all tiles: nothing exchanged is read
-        if (i == 1) P2P_RUN_TRY(hipStreamWaitEvent(cs, t->edge_done, 0));
-        if (i == g.n - 1 && more) p2p_say_ready(t, epoch + 1);
-        P2PSpan sw;
-        sw.begin = p2p_stamp(t, cs);
-        launch_group_whole(c, g, i, more, cs);
-        sw.end = p2p_stamp(t, cs);
-        if (t->profile) sp_whole.push_back(sw);
-        P2P_RUN_TRY(hipGetLastError());
-        group_launch_done(c, g, i, 1);
-      }
-      P2P_RUN_TRY(hipEventRecord(t->interior_done, cs));       // "the compute stream's launches of this group"
+      HIP_TRY_OR(hipGetLastError(), return bail());
+      HIP_TRY_OR(hipEventRecord(t->edge_done, es), return bail());
+      group_launch_done(c, g, 0, edge, 2);
+    }
+    for (int i = t->edge_stream ? 1 : 0; i < g.n; ++i) {       // over all tiles: (edge stream: nothing exchanged is read)
+      if (t->edge_stream && i == 1) HIP_TRY_OR(hipStreamWaitEvent(cs, t->edge_done, 0), return bail());
+      if (g.n > 1 && i == g.n - 1 && more) p2p_say_ready(t, epoch + 1);
+      const LaunchPlan whole = group_launch_plan(c, g, i, kLaunchWhole);
+      launch(i, whole, cs, i == 0 ? sp_interior : sp_whole);
+      HIP_TRY_OR(hipGetLastError(), return bail());
+      group_launch_done(c, g, i, whole, 1);
+    }
+    if (t->edge_stream) {
+      HIP_TRY_OR(hipEventRecord(t->interior_done, cs), return bail());       // "the compute stream's launches of this group"
       es_has_waited = false;
-    } else {
-      for (int i = 0; i < g.n; ++i) {
-        if (g.n > 1 && i == g.n - 1 && more) p2p_say_ready(t, epoch + 1);
-        P2PSpan sp;
-        sp.begin = p2p_stamp(t, cs);
-        launch_group_whole(c, g, i, more, cs);
-        sp.end = p2p_stamp(t, cs);
-        if (t->profile) (i == 0 ? sp_interior : sp_whole).push_back(sp);
-        P2P_RUN_TRY(hipGetLastError());
-        group_launch_done(c, g, i, 1);
-      }
     }
     launches += g.n;
     done += g.total;
     prev_n = g.n;
     if (more) {                                                // MPI_Startall (:327) for the next group
-      const GroupPlan next = plan_group(c, n_steps - done);
-      if (t->edge_stream) {
-        // the rows to push are the last launch's: its edge rows when the group was one launch and those tile rows hold all
-        // next.total rows of either side (then the push need not wait for the interior launch); else the compute stream's
-        const bool edge_rows_suffice = g.n == 1 && !t->tiles && (c->plan.ghost_rows - g.ext(0)) + rows.bottom_edge_rows * multi_ty(g.k[0], c->plan.multi_geom) >= c->plan.ghost_rows + next.total &&
-                                       (c->plan.ghost_rows - g.ext(0)) + (rows.bottom_edge_rows + rows.interior_rows) * multi_ty(g.k[0], c->plan.multi_geom) <= c->plan.ghost_rows + c->plan.nyl - next.total;
-        if (!edge_rows_suffice) { P2P_RUN_TRY(hipStreamWaitEvent(es, t->interior_done, 0)); es_has_waited = true; }
+      const GroupPlan next = lbm_internal::plan_group(c->plan, n_steps - done);
+      // the rows to push are the last launch's: where its edge tile rows hold them the push need not wait for the interior launch
+      if (t->edge_stream && !lbm_internal::edge_rows_suffice(c->plan, g, lbm_internal::macro_rows(c->plan, g.k[0], g.ext(0)), next.total)) {
+        HIP_TRY_OR(hipStreamWaitEvent(es, t->interior_done, 0), return bail());
+        es_has_waited = true;
       }
       P2PSpan sp;
-      sp.begin = p2p_stamp(t, es);
+      sp.begin = t->ev.stamp(es);
       if (p2p_push(t, epoch + 1, next.total, es)) return bail();
-      sp.end = p2p_stamp(t, es);
-      if (t->profile) sp_push.push_back(sp);
+      sp.end = t->ev.stamp(es);
+      if (t->ev.on) sp_push.push_back(sp);
       g = next;
     }
   }
   t->epoch = epoch - 1;
-  if (t->edge_stream) P2P_RUN_TRY(hipStreamWaitEvent(cs, t->edge_done, 0));
-  P2P_RUN_TRY(hipEventRecord(c->ev_end, cs));
-  hipEvent_t e_steps1 = p2p_stamp(t, cs);
+  if (t->edge_stream) HIP_TRY_OR(hipStreamWaitEvent(cs, t->edge_done, 0), return bail());
+  HIP_TRY_OR(hipEventRecord(c->ev_end, cs), return bail());
+  hipEvent_t e_steps1 = t->ev.stamp(cs);
   c->ev_launches = c->ev_tile_launches;
   c->ev_valid = true;
   if (fold_last(c, cs, /*final=*/true)) return bail();
   const clock::time_point h_enq = clock::now();
   if (p2p_reduce(t, n_steps, tot_u_per_step)) return bail();
-  if (t->edge_stream) P2P_RUN_TRY(hipStreamSynchronize(es));
-#undef P2P_RUN_TRY
+  if (t->edge_stream) HIP_TRY_OR(hipStreamSynchronize(es), return bail());
   if (p2p_check_error(t)) return 1;
-  if (t->profile) {
+  if (t->ev.on) {
     const clock::time_point h1 = clock::now();
     auto us = [](clock::time_point a, clock::time_point b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     double* ph = t->phases;
@@ -794,8 +744,8 @@ int lbm_p2p_run(lbm_p2p* t, int n_steps, double* tot_u_per_step)
 int lbm_p2p_set_profile(lbm_p2p* t, int on)
 {
   if (!t) { lbm_internal::set_error("lbm_p2p_set_profile: null argument"); return 1; }
-  t->profile = on != 0;
-  if (!t->profile) t->phases_valid = false;
+  t->ev.on = on != 0;
+  if (!t->ev.on) t->phases_valid = false;
   return 0;
 }
 

@@ -1,6 +1,6 @@
 // lbm_plan.cpp — the host-only planning unit of liblbm_d2q9.so: which kernel, which geometry and which buffer sizes a context
-// gets.  No HIP call and no device pointer anywhere in this file, so every rule here can be read, called and tested on a CPU
-// (tests/test_plan.py, through the lbm_plan_* exports at the end).
+// gets, and what each launch of a run covers.  No HIP call and no device pointer anywhere in this file, so every rule here can be
+// read, called and tested on a CPU (tests/test_plan.py and tests/test_launch_plan.py, through the lbm_plan_* exports at the end).
 //
 //   the rules        macro_eligible, macro_k_for, macro_ghost_for, macro_group_for, pick_geom, plane_stride_floats, pick_iters,
 //                    blocks_for — each with the measurements behind it
@@ -10,6 +10,10 @@
 //                    a device pointer.  plan_whole / plan_rank / plan_tile are its three callers, one per way of creating a
 //                    context; lbm_kernels.hip allocates, uploads and launches by the plan and never writes it
 //   the names        family_of(plan) and plan_kernel_name(plan): the only place the kernel families' names are spelled
+//   the launches     lbm_plan_next / lbm_plan_group_for cut a run into launches and groups; plan_launch fills a LaunchPlan: the rows,
+//                    columns, tiles (macro_rows, macro_rects), grid and kernel-table row of one launch of lbm_multi_kernel
+//                    (plan_tile_launch: of lbm_tile_kernel); edge_rows_suffice and plan_column_message are the exchange's two
+//                    geometric rules.  No heap allocation anywhere on this path: it runs once per launch
 //
 // Refusals keep the words and the order lbm_create* always had: what was checked before the device was touched returns
 // kPlanRefused, what was checked after it kPlanRefusedLate (the caller lets a bad device speak first).
@@ -441,9 +445,206 @@ void plan_kernel_name(const ContextPlan& c, char* kernel_name, size_t len)
   else std::snprintf(kernel_name, len, c.lane_cells == 1 ? "lbm_step_kernel_narrow<%s>" : "lbm_step_kernel<%s>", nt);
 }
 
+// ---- what a run launches ------------------------------------------------------------------------------------------------------
+
+// Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
+// divide is split into 3s and 4s where that avoids a K = 2 / K = 1 launch at the end (8192 x 8192, us per launch: K = 1 870,
+// K = 2 1000, K = 3 1050, K = 4 1290) — at K = 3: n = 3a + 4 or 3a + 8; at K = 4: n = 4a + 3, 4a + 6 or 4a + 9.  Whole periodic
+// grids (the frame wraps) and row partitions that keep four ghost rows.  A function of (K, ghost, left) only, so every
+// rank of a partitioned run makes the same sequence of macro-steps.
+int next_multi_k(const ContextPlan& c, int left)
+{
+  return lbm_plan_next(c.multi_K, (c.self_periodic || c.ghost >= 4) ? 1 : 0, c.multi_tail4 ? 1 : 0, left);
+}
+
+static_assert(kGroupCap == kMaxGroup, "GroupPlan holds the longest group");
+GroupPlan plan_group(const ContextPlan& c, int left)
+{
+  GroupPlan g;
+  g.n = lbm_plan_group_for(c.multi_K, (c.self_periodic || c.ghost >= 4) ? 1 : 0, c.multi_tail4 ? 1 : 0, c.ghost,
+                           std::min(c.group_max, static_cast<int>(kMaxGroup)), left, g.k, kMaxGroup);   // next_multi_k's launches
+  for (int i = 0; i < g.n; ++i) g.total += g.k[i];
+  return g;
+}
+
+// Tiles of a launch that makes `k` steps on the owned rows and `ext` more rows on each side (ext > 0: a launch of a partitioned
+// run that is followed by `ext` more steps before the next halo exchange): the tile height depends on k (lbm_geometry.h multi_ty).
+static int ext_rows(const ContextPlan& c, int ext) { return c.ghost_rows > 0 ? ext : 0; }   // ghost rows a launch advances (none where the rows wrap)
+static int multi_tile_rows(const ContextPlan& c, int k, int ext) { return (c.nyl + 2 * ext_rows(c, ext) + multi_ty(k, c.multi_geom) - 1) / multi_ty(k, c.multi_geom); }
+static int multi_tiles_for(const ContextPlan& c, int k, int ext) { return c.multi_tiles_x * multi_tile_rows(c, k, ext); }
+
+// Tile rows of a launch of k steps that also advances `ext` ghost rows per side (tile row 0 starts at storage row ghost - ext): the
+// first `bottom_edge_rows` and the last `top_edge_rows` tile rows read exchanged rows (edge launch, after the exchange); the
+// `interior_rows` between them do not: the rows they need — their own, k below and k above — are owned rows.  (The last tile row
+// may hold fewer rows than a launch makes steps: the ring of the row below then reaches the ghost rows, and the top edge is two rows.)
+// (Tile ranks: the first `left_cols` and the last `right_cols` tile COLUMNS read exchanged columns as well — a tile's first sub-step reads
+// multi_ex(k - 1) + 1 columns beyond its own on each side; the interior is then the rectangle inside all four.)
+MacroRows macro_rows(const ContextPlan& c, int k, int ext)
+{
+  const int ty = multi_ty(k, c.multi_geom);
+  const int ext_y = ext_rows(c, ext);
+  const int first = c.ghost_rows - ext_y, rows = c.nyl + 2 * ext_y;
+  const int nty = (rows + ty - 1) / ty;
+  const int lo = c.ghost_rows, hi = c.ghost_rows + c.nyl;              // the owned rows [lo, hi)
+  int b = 0, t = 0;
+  if (c.ghost_rows > 0) {                                              // (a column block wraps in y: no tile row reads an exchanged row)
+    while (b < nty && first + b * ty - k < lo) ++b;
+    while (t < nty - b && std::min(first + (nty - t) * ty, first + rows) - 1 + k >= hi) ++t;
+  }
+  int l = 0, r = 0;
+  if (c.ghost_x > 0) {
+    const int tx = c.multi_tx, ntx = c.multi_tiles_x, reach = multi_ex(k - 1) + 1;
+    const int xlo = c.ghost_x, xhi = c.ghost_x + c.nxl;                // the owned columns [xlo, xhi)
+    while (l < ntx && l * tx - reach < xlo) ++l;
+    while (r < ntx - l && (ntx - r) * tx - 1 + reach >= xhi) ++r;
+    if (ntx - l - r <= 0) return {nty, 0, 0, 0, 0};               // no tile column inside the rim: everything waits for the exchange
+  }
+  return {b, nty - b - t, t, l, r};
+}
+
+// The tiles of a tile rank's launch of k steps + ext as rectangles: the interior (at most one), or the rim around it (at most four).
+static int macro_rects(const ContextPlan& c, int k, int ext, bool interior, LaunchPlan::Rect* out)
+{
+  const MacroRows m = macro_rows(c, k, ext);
+  const int ntx = c.multi_tiles_x, mid = m.interior_rows;
+  int n = 0;
+  auto add = [&](int ty0, int nrows, int tx0, int cols) { if (nrows > 0 && cols > 0) out[n++] = LaunchPlan::Rect{ty0, tx0, cols, nrows * cols}; };
+  if (interior) {
+    add(m.bottom_edge_rows, mid, m.left_cols, ntx - m.left_cols - m.right_cols);
+  } else {
+    add(0, m.bottom_edge_rows, 0, ntx);
+    add(m.bottom_edge_rows + mid, m.top_edge_rows, 0, ntx);
+    add(m.bottom_edge_rows, mid, 0, m.left_cols);
+    add(m.bottom_edge_rows, mid, ntx - m.right_cols, m.right_cols);
+  }
+  return n;
+}
+
+// One launch of lbm_multi_kernel: `k` steps of the owned rows and `ext` ghost rows on each side (tile row 0 starts at storage row
+// ghost - ext), over all its tiles (kLaunchWhole), over those that read no exchanged cell (kLaunchInterior) or over the rest (kLaunchEdge).
+void plan_launch(const ContextPlan& c, const Knobs& knobs, int k, int ext, int which, bool says_ready, LaunchPlan* out)
+{
+  LaunchPlan a{};
+  a.k = k; a.ext = ext;
+  const int ext_y = ext_rows(c, ext);
+  a.row_first = c.ghost_rows - ext_y; a.rows_compute = c.nyl + 2 * ext_y; a.rows_storage = c.nyl + 2 * c.ghost_rows;
+  a.count_first = c.ghost_rows; a.count_end = c.ghost_rows + c.nyl;
+  a.cx0 = c.ghost_x; a.cx1 = c.ghost_x + c.nxl;
+  a.keep_x0 = std::max(0, (c.ghost_x - ext) & ~1); a.keep_x1 = std::min(c.nx, (c.ghost_x + c.nxl + ext + 1) & ~1);
+  a.y_periodic = (c.self_periodic || (c.ghost > 0 && c.ghost_rows == 0)) ? 1 : 0;
+  a.y0_global = c.y0 - ext_y;                                     // global row of storage row row_first
+  a.tiles_x = c.multi_tiles_x;
+  a.ntiles_total = multi_tiles_for(c, k, ext);
+  if (which == kLaunchWhole) {
+    a.tile_count = a.ntiles_total;
+  } else if (c.ghost_x > 0) {                                     // tile rank: the rectangle inside the rim, or the rim (four rectangles at most)
+    a.nrect = macro_rects(c, k, ext, which == kLaunchInterior, a.rect);
+  } else {
+    const MacroRows r = macro_rows(c, k, ext);
+    if (which == kLaunchInterior) { a.tile_begin = r.bottom_edge_rows * a.tiles_x; a.tile_count = r.interior_rows * a.tiles_x; }
+    else { a.tile_count = r.bottom_edge_rows * a.tiles_x; a.tile_begin2 = (r.bottom_edge_rows + r.interior_rows) * a.tiles_x; a.tile_count2 = r.top_edge_rows * a.tiles_x; }
+  }
+  int blocks = a.tile_count + a.tile_count2;
+  for (int i = 0; i < a.nrect; ++i) blocks += a.rect[i].count;
+  // measured on 8192x8192, K=2: 515 us/step with the XCD-contiguous tile order, 549 without
+  a.xcd_remap = (knobs.multi_remap && blocks % 8 == 0 && blocks >= 64) ? 1 : 0;
+  a.nblocks = blocks;
+  if (c.ghost_x > 0 && knobs.multi_remap && blocks >= 64 && blocks % 8 != 0 && knobs.tile_pad_grid) {
+    blocks = (blocks + 7) / 8 * 8;                                // tile ranks: pad the grid (the form drops the extra blocks) and keep the XCD-contiguous order
+    a.xcd_remap = 1;
+  }
+  a.launched_blocks = blocks;
+  // the instantiation that does exactly `k` steps: the tail of a run whose step count multi_K does not
+  // divide is a launch of a smaller frame, not a run-time loop bound (which cost scratch and ~10 % speed)
+  // the form (kernels/multi.h PART): ghost rows computed too -> the counted test; ready words to say -> the fold block carries them
+  // (a rank of the tile decomposition: ghost columns in every launch)
+  a.part = c.ghost_x > 0 ? kPartTile : ext > 0 ? kPartGhost : says_ready ? kPartReady : kPartPlain;
+  const int steps = std::min(k, static_cast<int>(kMaxMultiSteps));       // k <= multi_K, or 4 in the tail of a K = 3 run (next_multi_k)
+  a.row = multi_row(steps, c.multi_geom, c.fused ? kMultiTermsFused : c.multi_terms, a.part);
+  a.lanes = multi_lanes(steps, c.multi_geom);
+  *out = a;
+}
+
+// The next launch of lbm_tile_kernel when `left` steps remain: up to tile_H steps; FULL when it is exactly tile_H.
+void plan_tile_launch(const ContextPlan& c, int left, LaunchPlan* out)
+{
+  LaunchPlan a{};
+  a.k = std::min(c.tile_H, left);
+  a.full = a.k == c.tile_H;
+  a.tiles_x = c.nx / c.tile_T;
+  a.ntiles_total = a.tile_count = a.nblocks = a.launched_blocks = c.n_tiles;
+  a.row = tile_row(c.tile_T, c.tile_H, a.full != 0, c.fused ? kTileTermsFused : c.fast_avvels ? kTermsFloat : kTermsDouble);
+  *out = a;
+}
+
+// The rows the next push sends are the last launch's: its edge rows when the group was one launch of a row partition and those tile
+// rows hold all next_total rows of either side (then the push need not wait for the interior launch); else the compute stream's.
+bool edge_rows_suffice(const ContextPlan& c, const GroupPlan& g, const MacroRows& rows, int next_total)
+{
+  const int first = c.ghost_rows - g.ext(0), ty = multi_ty(g.k[0], c.multi_geom);
+  return g.n == 1 && c.ghost_x == 0 && first + rows.bottom_edge_rows * ty >= c.ghost_rows + next_total &&
+         first + (rows.bottom_edge_rows + rows.interior_rows) * ty <= c.ghost_rows + c.nyl - next_total;
+}
+
+// The widest access every row segment of a column message is aligned for, in the grid and in the messages, and the blocks of its
+// kernel: 1024 vectors per block.
+ColumnMessagePlan plan_column_message(const ContextPlan& c, int cols, int max_blocks, const long long* peer, int npeer)
+{
+  auto all_mult = [&](int m) {
+    for (int i = 0; i < npeer; ++i) if (peer[i] % m != 0) return false;
+    return cols % m == 0 && c.ghost_x % m == 0 && c.nxl % m == 0 && c.nx % m == 0 && c.ps % m == 0;
+  };
+  const int per = all_mult(4) ? 4 : all_mult(2) ? 2 : 1;
+  const long long work = 18LL * c.nyl * (cols / per);                  // vectors of the launch
+  return {per, static_cast<int>(std::max(1LL, std::min(static_cast<long long>(max_blocks), (work + 1023) / 1024)))};
+}
+
 }  // namespace lbm_internal
 
 extern "C" {
+
+int lbm_plan_next(int K, int four_rows, int tail4, int left)
+{
+  int k = left < K ? left : K;
+  if (!four_rows || !tail4) return k;
+  if (K == 3 && ((left % 3 == 1 && left >= 4) || (left % 3 == 2 && left >= 8))) k = 4;
+  if (K == 4 && ((left % 4 == 3) || (left % 4 == 2 && left >= 6) || (left % 4 == 1 && left >= 9))) k = 3;
+  return k;
+}
+
+// The launches between two halo exchanges of a partitioned run ("a group"): the next launches by lbm_plan_next for as long as their
+// steps add up to at most `ghost` (the first launch of a group advances the ghost rows the later ones read), `group_max` launches at most.
+// The first launch is always taken.  One implementation for the loops (plan_group above, with the context's four_rows / tail4)
+// and for the public lbm_plan_group that bench.py and the tests plan with, so that the two cannot disagree.
+int lbm_plan_group_for(int K, int four_rows, int tail4, int ghost, int group_max, int left, int* steps, int cap)
+{
+  int n = 0, used = 0;
+  while (left > 0 && n < group_max) {
+    const int k = lbm_plan_next(K, four_rows, tail4, left);
+    if (n > 0 && used + k > ghost) break;
+    if (n < cap) steps[n] = k;
+    ++n; used += k; left -= k;
+  }
+  return n;
+}
+
+int lbm_plan_group(int K, int ghost, int group_max, int left, int* steps, int cap)
+{
+  if (K < 1 || K > 4 || ghost < K || group_max < 1 || left < 0 || cap < 0 || (cap > 0 && !steps)) { lbm_internal::set_error("lbm_plan_group: bad argument"); return -1; }
+  return lbm_plan_group_for(K, ghost >= 4 ? 1 : 0, 1, ghost, group_max, left, steps, cap);
+}
+
+int lbm_plan_steps(int K, int four_rows, int n_steps, int* steps, int cap)
+{
+  if (K < 1 || K > 4 || n_steps < 0 || cap < 0 || (cap > 0 && !steps)) { lbm_internal::set_error("lbm_plan_steps: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_plan_next(K, four_rows, 1, left);
+    if (n < cap) steps[n] = k;
+    left -= k;
+  }
+  return n;
+}
 
 int lbm_rank_layout(const lbm_params* p, int nranks, int rank, unsigned flags, lbm_layout* out)
 {
@@ -515,6 +716,59 @@ int lbm_plan_kernel_name(const ContextPlan* plan, char* kernel_name, size_t len)
   if (!plan || !kernel_name || !len) { set_error("lbm_plan_kernel_name: null argument"); return 1; }
   lbm_internal::plan_kernel_name(*plan, kernel_name, len);
   return 0;
+}
+
+int lbm_plan_launch_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::LaunchPlan)); }
+int lbm_plan_launch(const ContextPlan* plan, int k, int ext, int which, int says_ready, lbm_internal::LaunchPlan* out)
+{
+  if (!plan || !out || plan->multi_tiles_x <= 0 || k < 1 || k > kMaxMultiSteps || ext < 0 || ext > kMaxGhost || which < lbm_internal::kLaunchWhole || which > lbm_internal::kLaunchEdge) {
+    set_error("lbm_plan_launch: bad argument");
+    return 1;
+  }
+  lbm_internal::plan_launch(*plan, knobs_from_env(), k, ext, which, says_ready != 0, out);
+  return 0;
+}
+
+int lbm_plan_run_launches(const ContextPlan* plan, int n_steps, int schedule, lbm_internal::LaunchPlan* out, int cap)
+{
+  using namespace lbm_internal;
+  if (!plan || n_steps < 0 || cap < 0 || (cap > 0 && !out) || (schedule != kScheduleSerial && schedule != kScheduleEdge)) { set_error("lbm_plan_run_launches: bad argument"); return -1; }
+  const Knobs knobs = knobs_from_env();
+  const KernelFamily family = family_of(*plan);
+  int n = 0;
+  LaunchPlan l;
+  auto put = [&](const LaunchPlan& a) { if (n < cap) out[n] = a; ++n; };
+  if (family == kFamilyTile) {
+    for (int left = n_steps; left > 0; left -= l.k) { plan_tile_launch(*plan, left, &l); put(l); }
+  } else if (family == kFamilyMulti && plan->ghost == 0) {                  // lbm_run: whole periodic grids
+    for (int left = n_steps; left > 0; left -= l.k) { plan_launch(*plan, knobs, next_multi_k(*plan, left), 0, kLaunchWhole, false, &l); put(l); }
+  } else if (family == kFamilyMulti) {                                     // the split-phase calls and the peer-to-peer loop: group by group
+    for (int left = n_steps; left > 0;) {
+      const GroupPlan g = plan_group(*plan, left);
+      const bool more = left > g.total;
+      for (int i = 0; i < g.n; ++i) {
+        if (i == 0 && schedule == kScheduleEdge) {
+          plan_launch(*plan, knobs, g.k[0], g.ext(0), kLaunchInterior, false, &l);
+          if (l.nblocks > 0) put(l);
+          plan_launch(*plan, knobs, g.k[0], g.ext(0), kLaunchEdge, false, &l);
+        } else {
+          plan_launch(*plan, knobs, g.k[i], g.ext(i), kLaunchWhole, g.n > 1 && i == g.n - 1 && more, &l);   // the group's last launch says "ready" for the next push
+        }
+        put(l);
+      }
+      left -= g.total;
+    }
+  }
+  return n;
+}
+
+int lbm_plan_edge_rows_suffice(const ContextPlan* plan, int left)
+{
+  using namespace lbm_internal;
+  if (!plan || plan->ghost <= 0 || left <= 0) return 0;
+  const GroupPlan g = plan_group(*plan, left);
+  if (left <= g.total) return 0;
+  return edge_rows_suffice(*plan, g, macro_rows(*plan, g.k[0], g.ext(0)), plan_group(*plan, left - g.total).total) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -1,5 +1,7 @@
 // plan_table_main.cpp — the planning unit under the host sanitizers: the three plan functions over the table of tests/plan_cases.py and
-// over the refusals, printed one line per context.  Host-only code, no GPU and no Python:
+// over the refusals, printed one line per context, and under each context every launch of its runs of 11 and 20 steps, both schedules
+// (lbm_plan_run_launches), one line per launch.  Host-only code, no GPU and no Python (of lbm_host.cpp the planner needs set_error and
+// the two decompositions only):
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I mpilattice-boltzmann_amd/csrc
 //       scripts/plan_table_main.cpp mpilattice-boltzmann_amd/csrc/lbm_plan.cpp mpilattice-boltzmann_amd/csrc/lbm_host.cpp -pthread -o plan_table && ./plan_table
 #include <cstdio>
@@ -7,13 +9,25 @@
 #include "lbm_d2q9.h"
 #include "lbm_internal.h"
 
-static int shown = 0;
+static int shown = 0, launches = 0;
 static void show(const char* what, int nx, int ny, int rc, const lbm_internal::ContextPlan& plan)
 {
   char name[256] = "";
   if (rc == 0) lbm_plan_kernel_name(&plan, name, sizeof name);
   std::printf("%-5s %6d x %-6d %s\n", what, nx, ny, rc == 0 ? name : lbm_last_error());
   ++shown;
+  if (rc != 0) return;
+  static lbm_internal::LaunchPlan l[64];
+  for (int steps : {11, 20})
+    for (int schedule : {kScheduleSerial, kScheduleEdge}) {
+      const int n = lbm_plan_run_launches(&plan, steps, schedule, l, 64);
+      for (int i = 0; i < n && i < 64; ++i, ++launches)
+        std::printf("  %2d steps %s  k %d ext %2d  rows %d+%d of %d  keep [%d, %d)  tiles %d+%d @%d,%d / %d rects of %d  blocks %d -> %d  remap %d  part %d row %d lanes %d\n",
+                    steps, schedule == kScheduleEdge ? "edge  " : "serial", l[i].k, l[i].ext, l[i].row_first, l[i].rows_compute, l[i].rows_storage, l[i].keep_x0, l[i].keep_x1,
+                    l[i].tile_count, l[i].tile_count2, l[i].tile_begin, l[i].tile_begin2, l[i].nrect, l[i].ntiles_total, l[i].nblocks, l[i].launched_blocks, l[i].xcd_remap,
+                    l[i].part, l[i].row, l[i].lanes);
+      if (schedule == kScheduleSerial && plan.ghost == 0) break;      // lbm_run has one schedule
+    }
 }
 
 int main()
@@ -41,6 +55,6 @@ int main()
     for (int r = 0; r < t[2] * t[3]; ++r) show("tile", t[0], t[1], lbm_plan_tile(&p, 1000, t[2], t[3], r, 0, &plan), plan);
   }
   show("null", 0, 0, lbm_plan_whole(nullptr, 1, 0, 1, 0, 0, &plan), plan);
-  std::printf("%d plans, clean\n", shown);
+  std::printf("%d plans, %d launches, clean\n", shown, launches);
   return 0;
 }
