@@ -11,6 +11,12 @@
  *   - nothing is contracted (-ffp-contract=off, no fast-math); division and square root are correctly rounded;
  *   - av_vels[t] = (sum over the free cells of sqrt(msq) * rinv, in double) * free_cells_inv.  Only the ORDER of that sum differs
  *     from a serial loop's (per-lane partial sums, a fixed tree per block, block 0 of the next launch folds the blocks' sums).
+ *     With LBM64_FLAG_TILE_STEPS on an eligible grid (lbm_tile_kernel_f64<T, H>, blocks of B = 256 lanes for <8, 4> and 512 otherwise)
+ *     the tree of one entry is: a lane adds the terms of the owned cells it meets in that sub-step (one per pass: 1 addition, 2 where
+ *     the sub-step's region has more than B cells), six butterfly levels join the 64 lanes of a wave, one lane adds the B / 64 waves'
+ *     sums serially: the tile's sum.  The fold then adds the tiles' sums: a lane ceil(tiles / F) of them serially, six butterfly
+ *     levels, F / 64 waves' sums serially, where F = B in block 0 of the next launch and F = 256 in the last fold of a run.
+ *     No atomics: the same state, grid and geometry give the same bits in every run.
  * tests/f64_ref.c restates it on a CPU; DESIGN.md section 5 gives the measured distances to the reference's shipped results.
  *
  * Conventions are those of lbm_d2q9.h: 0 on success, otherwise lbm_last_error() has the message for the calling thread; cells cross
@@ -18,9 +24,9 @@
  * lbm_last_error of lbm_d2q9.h serve this mode as they are.
  *
  * OUT OF SCOPE of this mode (use lbm_d2q9.h): row or tile partitions and every halo transport (peer-to-peer, RCCL, split-phase calls)
- * — a context is a whole periodic grid on one GPU; several steps per launch (lbm_multi_kernel, lbm_tile_kernel) — every step is one
- * launch of lbm_step_kernel_f64; the fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH); a state digest
- * (lbm_state_checksum) of doubles.
+ * — a context is a whole periodic grid on one GPU; several steps per launch of grids above the size cap of LBM64_FLAG_TILE_STEPS
+ * (lbm_multi_kernel) — without that flag, and on every grid it does not take, every step is one launch of lbm_step_kernel_f64; the
+ * fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH); a state digest (lbm_state_checksum) of doubles.
  */
 #ifndef LBM_D2Q9_F64_H
 #define LBM_D2Q9_F64_H
@@ -34,6 +40,13 @@ extern "C" {
 #endif
 
 #define LBM64_ABI_VERSION 1
+
+/* lbm64_create flag, beside LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES: advance a small whole grid several steps per launch with the
+ * temporally blocked kernel lbm_tile_kernel_f64<T, H> (T x T tiles, up to H steps per launch; csrc/kernels/tile64.h).  Taken where
+ * nx and ny are multiples of T and nx * ny is at most LBM_TUNE_TILE64_MAX (scripts/README.md; by default 1024 x 1024 cells);
+ * every other grid runs lbm_step_kernel_f64 exactly as without the flag.  Populations are the same bits either way; av_vels differs in
+ * the order of its additions only (above).  lbm_create of lbm_d2q9.h ignores this bit. */
+#define LBM64_FLAG_TILE_STEPS 512u
 
 /* t_param (d2q9-bgk.c:79-90) with its three floats as doubles. */
 typedef struct lbm64_params {
@@ -71,7 +84,7 @@ int lbm64_write_av_vels(const char* path, const double* av_vels, int n);
 
 /* A whole periodic nx x ny grid (ny >= 3) on GPU `device`, in the initial state of d2q9-bgk.c:880-902.  obstacles = ny*nx ints.
  * flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default once the two grids
- * exceed the Infinity Cache); any other flag is refused. */
+ * exceed the Infinity Cache), each with or without LBM64_FLAG_TILE_STEPS; any other flag is refused. */
 int lbm64_create(lbm64_ctx** ctx, const lbm64_params* params, int free_cells, const int* obstacles, int device, unsigned flags);
 int lbm64_destroy(lbm64_ctx* ctx);
 
@@ -91,11 +104,12 @@ int lbm64_get_observables(lbm64_ctx* ctx, double* obs);
  * block, then the blocks' sums on the host). */
 int lbm64_av_velocity_sum(lbm64_ctx* ctx, double* tot_u);
 
-/* Device time of the step launches of the last lbm64_run (events around them), and their number. */
+/* Device time of the step launches of the last lbm64_run (events around them), and their number (tiled: launches, not steps). */
 int lbm64_last_run_kernel_ms(lbm64_ctx* ctx, double* ms, int* launches);
 
 /* What a step launch looks like: the kernel's name, its work blocks (one more block folds the previous step's sums), the cells
- * a block advances (256 lanes x cells per lane x units per lane) and the bytes of the two grids. */
+ * a block advances (256 lanes x cells per lane x units per lane) and the bytes of the two grids.  A context that
+ * LBM64_FLAG_TILE_STEPS advances with the tiled kernel: "lbm_tile_kernel_f64<T, H>", the tiles, T * T. */
 int lbm64_describe(const lbm64_ctx* ctx, char* kernel_name, size_t len, long long* blocks, long long* cells_per_block, long long* state_bytes);
 
 #ifdef __cplusplus

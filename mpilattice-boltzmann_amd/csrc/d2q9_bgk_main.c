@@ -15,7 +15,9 @@
  *
  * LBM_PRECISION=double runs the double-precision mode (include/lbm_d2q9_f64.h): the reference's arithmetic with every float object a double,
  * which is what the reference's shipped results and README were produced with; the same five lines and two files.  One GPU only
- * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES) and has no other default.
+ * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES) and 512 (LBM64_FLAG_TILE_STEPS:
+ * a small grid advances several steps per launch, the same populations and files) and has no other default.  LBM_DESCRIBE=1 adds one
+ * line on stderr: the kernel that advanced the grid (lbm64_describe) and the step launches of the run.
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
  * the reference's rule (d2q9-bgk.c:834-862), rank r lives on device LBM_DEVICES[r] (a comma list; default r), one host
@@ -119,6 +121,14 @@ static int main_double(char* argv[])
   if (lbm64_run(ctx, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
   toc = wall_seconds();                                                    /* :397-398 */
   if (lbm64_get_observables(ctx, obs)) die(lbm_last_error(), __LINE__, __FILE__);
+  if (env_int("LBM_DESCRIBE", 0)) {
+    char kernel[128];
+    double ms = 0.0;
+    int launches = 0;
+    if (lbm64_describe(ctx, kernel, sizeof kernel, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
+    if (params.max_iters > 0 && lbm64_last_run_kernel_ms(ctx, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
+    fprintf(stderr, "kernel: %s, %d launches\n", kernel, launches);
+  }
   lbm64_destroy(ctx);
   getrusage(RUSAGE_SELF, &ru);                                             /* :399-403 */
   usrtim = ru.ru_utime.tv_sec + ru.ru_utime.tv_usec / 1000000.0;

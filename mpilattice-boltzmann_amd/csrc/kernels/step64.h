@@ -243,14 +243,19 @@ __global__ void __launch_bounds__(kBlock) lbm_step_kernel_f64(const Step64Args a
   if (threadIdx.x == 0) a.partials_out[wblock] = acc;
 }
 
-// The last launch's partials, after the loop: one block.
-__global__ void __launch_bounds__(kBlock) lbm64_fold_kernel(const double* partials, int n, double* sums, int* counter)
+// The last launch's partials, after the loop: one block.  nvecs vectors of n sums, one per step of that launch (the one-step kernel: 1;
+// lbm_tile_kernel_f64: its steps), each summed as the one vector always was.
+__global__ void __launch_bounds__(kBlock) lbm64_fold_kernel(const double* partials, int n, int nvecs, double* sums, int* counter)
 {
   __shared__ double red[kBlock / 64];
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += kBlock) s += partials[i];
-  s = block_sum(s, red);
-  if (threadIdx.x == 0) { sums[*counter] = s; *counter = 0; }       // 0: the next run starts counting again
+  const int first = threadIdx.x == 0 ? *counter : 0;                 // lane 0 alone reads and writes it
+  for (int v = 0; v < nvecs; ++v) {
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += kBlock) s += partials[static_cast<size_t>(v) * n + i];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) sums[first + v] = s;
+  }
+  if (threadIdx.x == 0) *counter = 0;                               // 0: the next run starts counting again
 }
 
 // accelerate_flow (d2q9-bgk.c:442-478) in place on one row: before the first step of a run.

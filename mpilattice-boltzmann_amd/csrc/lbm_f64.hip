@@ -4,9 +4,10 @@
 //
 // What one step does is what lbm_kernels.hip's header lists, with every float object a double (the contract: lbm_d2q9_f64.h):
 // pull-stream, moments + equilibrium, BGK relaxation / bounce-back, the sum|u| terms into per-block partials, accelerate_flow as an
-// epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  One kernel, lbm_step_kernel_f64<CELLS, NT>,
-// one step per launch: whole periodic grids on one GPU only (no partitions, no several steps per launch, no fused arithmetic, no
-// hipGraph, no state digest).
+// epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  lbm_step_kernel_f64<CELLS, NT> makes one
+// step per launch; with LBM64_FLAG_TILE_STEPS a small grid is advanced by lbm_tile_kernel_f64<T, H, FULL> (kernels/tile64.h), up to H
+// steps per launch.  Whole periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph, no state digest).
+// What a context gets of all that is decided in lbm_plan.cpp (Plan64, lbm_internal.h); this unit allocates and launches by the plan.
 //
 // Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (the float path's rule in elements: lbm_plan.cpp plane_stride_floats), two grids
 // swapped per launch, the obstacle map as the float path's bitfield.  Compiled with -ffp-contract=off like the rest of the library:
@@ -28,6 +29,7 @@
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 #include "kernels/step64.h"
+#include "kernels/tile64.h"
 
 namespace {
 
@@ -48,15 +50,12 @@ struct lbm64_ctx {
   int free_cells = 0;
   double free_cells_inv = 0.0;
   int device = 0;
-  bool nt_stores = false;
-  int lane_cells = kPairCells;       // 2 (nx even) or 1
-  size_t ncells = 0, ps = 0, grid_doubles = 0;
+  lbm_internal::Plan64 plan{};       // kernels, launch shapes and sizes (lbm_plan.cpp plan64_whole): written once
+  size_t ncells = 0, ps = 0;
   double* grid_alloc[2] = {nullptr, nullptr};
   double* grid[2] = {nullptr, nullptr};      // plane 0 row 0 (after the front guard)
   int cur = 0;
   uint32_t* mask = nullptr;
-  uint32_t units = 0;
-  int iters = 1, blocks = 0;         // work blocks of a step launch
   double* partials[2] = {nullptr, nullptr};
   double* sums = nullptr;
   int sums_cap = 0;
@@ -76,10 +75,14 @@ constexpr Step64Kernel kStep64Kernels[2][2] = {
   {&lbm_step_kernel_f64<kPairCells, false>, &lbm_step_kernel_f64<kPairCells, true>},
   {&lbm_step_kernel_f64<1, false>, &lbm_step_kernel_f64<1, true>},
 };
-const char* const kStep64Names[2][2] = {
-  {"lbm_step_kernel_f64<2>", "lbm_step_kernel_f64<2,nt>"},
-  {"lbm_step_kernel_f64<1>", "lbm_step_kernel_f64<1,nt>"},
+
+using Tile64Kernel = void (*)(Tile64Args);
+// every instantiation of the tiled kernel, by tile64_row(T, H, FULL) (lbm_geometry.h, which also has their block sizes and LDS bytes)
+constexpr Tile64Kernel kTile64Kernels[kTile64Rows] = {
+  &lbm_tile_kernel_f64<16, 8, false>, &lbm_tile_kernel_f64<16, 8, true>, &lbm_tile_kernel_f64<16, 4, false>, &lbm_tile_kernel_f64<16, 4, true>,
+  &lbm_tile_kernel_f64<8, 8, false>,  &lbm_tile_kernel_f64<8, 8, true>,  &lbm_tile_kernel_f64<8, 4, false>,  &lbm_tile_kernel_f64<8, 4, true>,
 };
+static_assert(tile64_row(16, 8, false) == 0 && tile64_row(16, 4, true) == 3 && tile64_row(8, 8, false) == 4 && tile64_row(8, 4, true) == 7, "the order of kTile64Kernels");
 
 int ensure_sums(lbm64_ctx* c, int n)
 {
@@ -128,8 +131,8 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   if (p->nx < 1) { lbm_internal::set_error("lbm64_create: nx must be positive"); return 1; }
   if (p->ny < 3) { lbm_internal::set_error("lbm64_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
   if (free_cells <= 0) { lbm_internal::set_error("lbm64_create: free_cells must be positive"); return 1; }
-  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES)) != 0u) {
-    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only (whole grids, one step per launch, exact arithmetic)");
+  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS)) != 0u) {
+    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only, each with or without LBM64_FLAG_TILE_STEPS (whole grids, exact arithmetic)");
     return 1;
   }
   if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { lbm_internal::set_error("lbm64_create: grid too large for 32-bit cell indices"); return 1; }
@@ -144,17 +147,9 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   c->accel_w1 = p->density * p->accel * 0.111111111111111111111111;         // d2q9-bgk.c:445
   c->accel_w2 = p->density * p->accel * 0.0277777777777777777777778;        // d2q9-bgk.c:446
   c->ncells = static_cast<size_t>(p->nx) * p->ny;
-  c->ps = lbm_internal::plane_stride_floats(c->ncells, c->knobs.skew);   // the float path's rule, in elements: always even (the pair form's aligned 16-byte accesses)
-  c->grid_doubles = 9 * c->ps + 128;
-  // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache (the float path's rule and flags)
-  const size_t state_bytes = 2 * 9 * c->ncells * sizeof(double);
-  c->nt_stores = state_bytes > (192u << 20);
-  if (flags & LBM_FLAG_NT_STORES) c->nt_stores = true;
-  if (flags & LBM_FLAG_NO_NT_STORES) c->nt_stores = false;
-  c->lane_cells = (p->nx % kPairCells == 0) ? kPairCells : 1;
-  c->units = static_cast<uint32_t>(c->ncells / c->lane_cells);
-  c->iters = lbm_internal::pick_iters(c->units, std::max(c->knobs.maxblocks, 1));
-  c->blocks = static_cast<int>((static_cast<long long>(c->units) + static_cast<long long>(kBlock) * c->iters - 1) / (static_cast<long long>(kBlock) * c->iters));
+  lbm_internal::plan64_whole(c->knobs, p, flags, &c->plan);
+  const lbm_internal::Plan64& plan = c->plan;
+  c->ps = static_cast<size_t>(plan.ps);
 
   auto fail = [&](void) { lbm64_destroy(c); return 1; };
 #define HIP_TRY_C(expr)                                                                      \
@@ -170,8 +165,8 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   HIP_TRY_C(hipEventCreate(&c->ev_begin));
   HIP_TRY_C(hipEventCreate(&c->ev_end));
   for (int g = 0; g < 2; ++g) {
-    HIP_TRY_C(hipMalloc(&c->grid_alloc[g], sizeof(double) * c->grid_doubles));
-    HIP_TRY_C(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(double) * c->grid_doubles, c->stream));
+    HIP_TRY_C(hipMalloc(&c->grid_alloc[g], sizeof(double) * static_cast<size_t>(plan.grid_doubles)));
+    HIP_TRY_C(hipMemsetAsync(c->grid_alloc[g], 0, sizeof(double) * static_cast<size_t>(plan.grid_doubles), c->stream));
     c->grid[g] = c->grid_alloc[g] + 64;
   }
   // obstacle bitfield: bit c of the cell index, as the float path's
@@ -183,7 +178,12 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
     HIP_TRY_C(hipMalloc(&c->mask, sizeof(uint32_t) * mwords));
     HIP_TRY_C(hipMemcpy(c->mask, bits.data(), sizeof(uint32_t) * mwords, hipMemcpyHostToDevice));
   }
-  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * (c->blocks + 1)));
+  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * static_cast<size_t>(plan.partials_cap)));
+  if (plan.tile_kernel && plan.tile_lds_bytes > 65536) {     // dynamic LDS above 64 KiB: raised once, for the two instantiations the context launches
+    for (int full = 0; full < 2; ++full)
+      HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(kTile64Kernels[tile64_row(plan.tile_T, plan.tile_H, full != 0)]),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, plan.tile_lds_bytes));
+  }
   HIP_TRY_C(hipMalloc(&c->counter, sizeof(int)));
   HIP_TRY_C(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream));
   if (ensure_sums(c, 1)) return fail();
@@ -211,35 +211,73 @@ int lbm64_run(lbm64_ctx* c, int n_steps, double* av_vels)
   const uint32_t nx = static_cast<uint32_t>(c->p.nx), ny = static_cast<uint32_t>(c->p.ny);
   hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, s, c->grid[c->cur], c->ps, c->mask, nx, ny - 2, c->accel_w1, c->accel_w2);
   HIP_TRY(hipGetLastError());
-  Step64Args a{};
-  a.mask = c->mask;
-  a.ps = c->ps;
-  a.nx = nx; a.ny = ny;
-  a.units = c->units;
-  a.iters = c->iters;
-  a.omega = c->p.omega;
-  a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
-  a.sums = c->sums;
-  a.counter = c->counter;
-  const Step64Kernel kernel = kStep64Kernels[c->lane_cells == 1][c->nt_stores];
-  HIP_TRY(hipEventRecord(c->ev_begin, s));
-  int parity = 0;
-  for (int t = 0; t < n_steps; ++t) {
-    a.src = c->grid[c->cur];
-    a.dst = c->grid[c->cur ^ 1];
-    a.accel_row = t + 1 < n_steps ? static_cast<int>(ny) - 2 : -1;
-    a.partials_out = c->partials[parity];
-    a.prev_partials = c->partials[parity ^ 1];
-    a.n_prev = t > 0 ? c->blocks : 0;
-    kernel<<<dim3(c->blocks + 1), dim3(kBlock), 0, s>>>(a);               // + the fold block
-    parity ^= 1;
-    c->cur ^= 1;
+  const lbm_internal::Plan64& plan = c->plan;
+  int parity = 0, launches = 0;
+  int last_n = 0, last_vecs = 0;        // the last launch's partials: vectors of last_n sums, one per step
+  if (plan.tile_kernel) {
+    // up to tile_H steps per launch (lbm_plan.cpp plan64_next_steps); block 0 of a launch folds the vectors of the launch before it
+    Tile64Args a{};
+    a.mask = c->mask;
+    a.ps = c->ps;
+    a.nx = static_cast<int>(nx); a.ny = static_cast<int>(ny);
+    a.tiles_x = plan.tiles_x;
+    a.omega = c->p.omega;
+    a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+    a.accel_row = static_cast<int>(ny) - 2;
+    a.n_prev = plan.n_tiles;
+    a.sums = c->sums;
+    a.counter = c->counter;
+    HIP_TRY(hipEventRecord(c->ev_begin, s));
+    for (int left = n_steps; left > 0;) {
+      const int k = lbm_internal::plan64_next_steps(plan, left);
+      left -= k;
+      a.src = c->grid[c->cur];
+      a.dst = c->grid[c->cur ^ 1];
+      a.ksteps = k;
+      a.accel_last = left > 0;
+      a.partials_out = c->partials[parity];
+      a.prev_partials = c->partials[parity ^ 1];
+      a.n_prev_vecs = last_vecs;
+      const Tile64Kernel kernel = kTile64Kernels[tile64_row(plan.tile_T, plan.tile_H, k == plan.tile_H)];
+      kernel<<<dim3(plan.n_tiles + 1), dim3(plan.tile_block), static_cast<size_t>(plan.tile_lds_bytes), s>>>(a);   // + the fold block
+      last_vecs = k;
+      parity ^= 1;
+      c->cur ^= 1;
+      ++launches;
+    }
+    last_n = plan.n_tiles;
+  } else {
+    Step64Args a{};
+    a.mask = c->mask;
+    a.ps = c->ps;
+    a.nx = nx; a.ny = ny;
+    a.units = plan.units;
+    a.iters = plan.iters;
+    a.omega = c->p.omega;
+    a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+    a.sums = c->sums;
+    a.counter = c->counter;
+    const Step64Kernel kernel = kStep64Kernels[plan.lane_cells == 1][plan.nt_stores];
+    HIP_TRY(hipEventRecord(c->ev_begin, s));
+    for (int t = 0; t < n_steps; ++t) {
+      a.src = c->grid[c->cur];
+      a.dst = c->grid[c->cur ^ 1];
+      a.accel_row = t + 1 < n_steps ? static_cast<int>(ny) - 2 : -1;
+      a.partials_out = c->partials[parity];
+      a.prev_partials = c->partials[parity ^ 1];
+      a.n_prev = t > 0 ? plan.blocks : 0;
+      kernel<<<dim3(plan.blocks + 1), dim3(kBlock), 0, s>>>(a);               // + the fold block
+      parity ^= 1;
+      c->cur ^= 1;
+    }
+    launches = n_steps;
+    last_n = plan.blocks; last_vecs = 1;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(c->ev_end, s));
-  c->ev_launches = n_steps;
+  c->ev_launches = launches;
   c->ev_valid = true;
-  hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, s, c->partials[parity ^ 1], c->blocks, c->sums, c->counter);
+  hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, s, c->partials[parity ^ 1], last_n, last_vecs, c->sums, c->counter);
   HIP_TRY(hipGetLastError());
   if (av_vels) {
     HIP_TRY(hipMemcpyAsync(av_vels, c->sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s));
@@ -351,9 +389,10 @@ int lbm64_last_run_kernel_ms(lbm64_ctx* c, double* ms, int* launches)
 int lbm64_describe(const lbm64_ctx* c, char* kernel_name, size_t len, long long* blocks, long long* cells_per_block, long long* state_bytes)
 {
   if (!c) { lbm_internal::set_error("lbm64_describe: null context"); return 1; }
-  if (kernel_name && len > 0) std::snprintf(kernel_name, len, "%s", kStep64Names[c->lane_cells == 1][c->nt_stores]);
-  if (blocks) *blocks = c->blocks;
-  if (cells_per_block) *cells_per_block = static_cast<long long>(kBlock) * c->iters * c->lane_cells;
+  const lbm_internal::Plan64& plan = c->plan;
+  if (kernel_name && len > 0) lbm_internal::plan64_kernel_name(plan, kernel_name, len);
+  if (blocks) *blocks = plan.tile_kernel ? plan.n_tiles : plan.blocks;
+  if (cells_per_block) *cells_per_block = plan.tile_kernel ? static_cast<long long>(plan.tile_T) * plan.tile_T : static_cast<long long>(kBlock) * plan.iters * plan.lane_cells;
   if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->ncells * sizeof(double));
   return 0;
 }

@@ -36,6 +36,22 @@ constexpr int kFoldSlices = 64;
 // ---- the double-precision one-step kernel (kernels/step64.h) ----
 constexpr int kPairCells = 2;        // one 16-byte access per population per lane
 
+// ---- lbm_tile_kernel_f64<T, H, FULL> (kernels/tile64.h): its geometries, and what a block of each takes ----
+// T = owned tile edge, H = ghost ring = most steps of a launch; the region is R x R, R = T + 2H.  One cell per lane, dealt anew in every
+// sub-step over a strided loop: 256 lanes hold the largest computed region of <8,4> (14 x 14), 512 that of <8,8> and <16,4> (22 x 22) in
+// one pass; <16,8> (30 x 30 down to 16 x 16) takes two passes of 512 lanes while its region has more than 512 cells.
+// LDS: two buffers of 9 R^2 doubles, H x waves doubles of reduction scratch, one flag byte per region cell.
+constexpr bool tile64_geom_ok(int t, int h) { return (t == 8 || t == 16) && (h == 4 || h == 8); }
+constexpr int tile64_region(int t, int h) { return t + 2 * h; }
+constexpr int tile64_block(int t, int h) { return (t == 8 && h == 4) ? 256 : 512; }
+constexpr int tile64_lds_bytes(int t, int h)
+{
+  return tile64_region(t, h) * tile64_region(t, h) * (2 * 9 * 8 + 1) + 8 * h * (tile64_block(t, h) / 64);
+}
+constexpr int kTile64Rows = 4 * 2;   // the host's table kTile64Kernels (lbm_f64.hip): one row per (geometry, FULL)
+constexpr int tile64_row(int t, int h, bool full) { return ((t == 8 ? 2 : 0) + (h == 4 ? 1 : 0)) * 2 + (full ? 1 : 0); }
+static_assert(tile64_lds_bytes(16, 8) <= 160 * 1024 && tile64_lds_bytes(8, 4) <= 64 * 1024, "a block's LDS: at most what a CU gives one workgroup");
+
 // ---- lbm_multi_kernel (kernels/multi.h) ----
 #ifndef LBM_MTY            // experiment builds: -DLBM_MTY=24 -DLBM_MLANES=768 (taller tiles, two blocks per CU)
 #define LBM_MTY 16

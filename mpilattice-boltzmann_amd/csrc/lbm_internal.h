@@ -5,6 +5,7 @@
 #include <string>
 
 #include "lbm_d2q9.h"
+#include "lbm_d2q9_f64.h"
 #include "lbm_knobs.h"
 
 namespace lbm_internal {
@@ -69,6 +70,28 @@ void plan_kernel_name(const ContextPlan& plan, char* kernel_name, size_t len);
 size_t plane_stride_floats(size_t ncells, int skew);
 int pick_iters(long long quads, int max_blocks);
 int blocks_for(long long quads, int iters);
+
+// ---- lbm_plan.cpp: a context of the double-precision mode (include/lbm_d2q9_f64.h; lbm_f64.hip allocates and launches by it) ------
+// Plain data in this order — tests/test_plan64.py mirrors it field for field and refuses a library whose lbm_plan64_sizeof() differs.
+struct Plan64 {
+  unsigned flags;                    // as lbm64_create took them
+  // the one-step kernel: non-temporal stores; cells per lane (2: x-pairs, nx even; 1); pairs or cells of the grid; 256-unit chunks per
+  // block; work blocks of a launch
+  int nt_stores, lane_cells;
+  unsigned units;
+  int iters, blocks;
+  // lbm_tile_kernel_f64<tile_T, tile_H>: tile_kernel = the context advances up to tile_H steps per launch with it (LBM64_FLAG_TILE_STEPS
+  // on an eligible grid); tiles (= work blocks of a launch) and tiles per row; lanes and dynamic LDS bytes of a block (lbm_geometry.h)
+  int tile_kernel, tile_T, tile_H, n_tiles, tiles_x, tile_block, tile_lds_bytes;
+  int partials_cap;                  // doubles of each partials buffer: max(blocks, tile_H * n_tiles where tile_kernel) + 1
+  long long ps, grid_doubles;        // plane stride; one grid's allocation, in doubles
+};
+static_assert(sizeof(Plan64) == 14 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
+// Fills *out for a whole nx x ny grid (the caller has checked nx >= 1, ny >= 3 and the flags).
+void plan64_whole(const Knobs& knobs, const lbm64_params* p, unsigned flags, Plan64* out);
+void plan64_kernel_name(const Plan64& plan, char* kernel_name, size_t len);
+// Steps of the next launch of a run with `left` steps remaining: 1 (one-step kernel), or up to tile_H.
+int plan64_next_steps(const Plan64& plan, int left);
 
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
@@ -136,3 +159,10 @@ extern "C" int lbm_plan_launch(const lbm_internal::ContextPlan* plan, int k, int
 extern "C" int lbm_plan_run_launches(const lbm_internal::ContextPlan* plan, int n_steps, int schedule, lbm_internal::LaunchPlan* out, int cap);
 // edge_rows_suffice for the group a run makes with `left` steps remaining and the one after it (0 where no group follows).
 extern "C" int lbm_plan_edge_rows_suffice(const lbm_internal::ContextPlan* plan, int left);
+// The same for the double-precision mode: the plan a context of these arguments would get (0, or 1 where lbm64_create refuses them), its
+// kernel's name, and the launches of a run of n_steps (steps[i], and full[i] = 1 where launch i makes exactly tile_H steps of the tiled
+// kernel); returns the number of launches (the first `cap` are written), -1 on a bad argument.
+extern "C" int lbm_plan64_sizeof(void);
+extern "C" int lbm_plan64_whole(const lbm64_params* p, unsigned flags, lbm_internal::Plan64* out);
+extern "C" int lbm_plan64_kernel_name(const lbm_internal::Plan64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_run_launches(const lbm_internal::Plan64* plan, int n_steps, int* steps, int* full, int cap);

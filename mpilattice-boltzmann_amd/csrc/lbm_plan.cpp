@@ -445,6 +445,58 @@ void plan_kernel_name(const ContextPlan& c, char* kernel_name, size_t len)
   else std::snprintf(kernel_name, len, c.lane_cells == 1 ? "lbm_step_kernel_narrow<%s>" : "lbm_step_kernel<%s>", nt);
 }
 
+// ---- the double-precision mode --------------------------------------------------------------------------------------------------
+
+// What lbm64_create decides.  The one-step launch (every context has it: set_cells, the fallbacks) by the float path's rules in
+// elements; then, with LBM64_FLAG_TILE_STEPS, whether lbm_tile_kernel_f64 advances the grid and in which geometry.
+void plan64_whole(const Knobs& knobs, const lbm64_params* p, unsigned flags, Plan64* out)
+{
+  Plan64 c{};
+  c.flags = flags;
+  const size_t ncells = static_cast<size_t>(p->nx) * p->ny;
+  c.ps = static_cast<long long>(plane_stride_floats(ncells, knobs.skew));   // always even (the pair form's aligned 16-byte accesses)
+  c.grid_doubles = 9 * c.ps + 128;
+  // non-temporal output stores once the two grids no longer fit the 256 MiB Infinity Cache (the float path's rule and flags)
+  const size_t state_bytes = 2 * 9 * ncells * sizeof(double);
+  c.nt_stores = state_bytes > (192u << 20);
+  if (flags & LBM_FLAG_NT_STORES) c.nt_stores = 1;
+  if (flags & LBM_FLAG_NO_NT_STORES) c.nt_stores = 0;
+  c.lane_cells = (p->nx % kPairCells == 0) ? kPairCells : 1;
+  c.units = static_cast<unsigned>(ncells / c.lane_cells);
+  c.iters = pick_iters(c.units, std::max(knobs.maxblocks, 1));
+  c.blocks = static_cast<int>((static_cast<long long>(c.units) + static_cast<long long>(kBlock) * c.iters - 1) / (static_cast<long long>(kBlock) * c.iters));
+  // geometry by size (T * 10 + H): the fastest measured per deck (profiles/r08/f64_tile.txt), s per whole deck for the one-step
+  // kernel | <8,4> / <8,8> / <16,4> / <16,8>:  128x128 0.1429 | 0.0599 / 0.0621 / 0.0671 / 0.0660   128x256 0.1522 | 0.0837 / 0.0959 /
+  // 0.0771 / 0.0714   256x256 0.3344 | 0.2403 / 0.3476 / 0.1970 / 0.1751   512x512 (10 000 steps) 0.0982 | 0.0628 / 0.1460 / 0.0678 /
+  // 0.0666   1024x1024 0.4669 | 0.4129 / 1.1176 / 0.4572 / 0.4845.  Between two measured sizes the smaller one's geometry holds.
+  const int by_size = ncells < 32768 ? 84 : ncells < 262144 ? 168 : 84;
+  int geom = knob_or(knobs.tile64_geom, by_size);
+  if (geom < 0 || !tile64_geom_ok(geom / 10, geom % 10)) geom = by_size;      // a malformed value: the default
+  c.tile_T = geom / 10; c.tile_H = geom % 10;
+  c.tile_block = tile64_block(c.tile_T, c.tile_H);
+  c.tile_lds_bytes = tile64_lds_bytes(c.tile_T, c.tile_H);
+  const bool tiles = p->nx % c.tile_T == 0 && p->ny % c.tile_T == 0;
+  c.tiles_x = tiles ? p->nx / c.tile_T : 0;
+  c.n_tiles = tiles ? c.tiles_x * (p->ny / c.tile_T) : 0;
+  // the size cap (LBM_TUNE_TILE64_MAX): the largest measured grid at which the tiled launches beat the one-step ones by more than both
+  // max - min spreads together: 1024 x 1024 (0.4129 against 0.4669 s, spreads 0.0022 s), the largest grid measured
+  c.tile_kernel = (flags & LBM64_FLAG_TILE_STEPS) != 0u && tiles && static_cast<long long>(ncells) <= static_cast<long long>(knobs.tile64_max);
+  c.partials_cap = std::max(c.blocks, c.tile_kernel ? c.tile_H * c.n_tiles : 0) + 1;   // a context that never launches the tiled kernel keeps no room for it
+  *out = c;
+}
+
+void plan64_kernel_name(const Plan64& c, char* kernel_name, size_t len)
+{
+  if (c.tile_kernel) std::snprintf(kernel_name, len, "lbm_tile_kernel_f64<%d, %d>", c.tile_T, c.tile_H);
+  else std::snprintf(kernel_name, len, c.nt_stores ? "lbm_step_kernel_f64<%d,nt>" : "lbm_step_kernel_f64<%d>", c.lane_cells);
+}
+
+// A run of n steps is launches of tile_H steps and one shorter tail: a function of what is left of THIS run only.
+int plan64_next_steps(const Plan64& c, int left)
+{
+  return c.tile_kernel ? std::min(c.tile_H, left) : std::min(1, left);
+}
+
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
 
 // Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
@@ -758,6 +810,35 @@ int lbm_plan_run_launches(const ContextPlan* plan, int n_steps, int schedule, lb
       }
       left -= g.total;
     }
+  }
+  return n;
+}
+
+// ---- the double-precision mode's plan, for tests ----
+int lbm_plan64_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::Plan64)); }
+int lbm_plan64_whole(const lbm64_params* p, unsigned flags, lbm_internal::Plan64* out)
+{
+  if (!p || !out) { set_error("lbm_plan64_whole: null argument"); return 1; }
+  if (p->nx < 1 || p->ny < 3) { set_error("lbm_plan64_whole: nx must be positive and ny >= 3"); return 1; }
+  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS)) != 0u) { set_error("lbm_plan64_whole: a flag lbm64_create refuses"); return 1; }
+  if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { set_error("lbm_plan64_whole: grid too large for 32-bit cell indices"); return 1; }
+  lbm_internal::plan64_whole(knobs_from_env(), p, flags, out);
+  return 0;
+}
+int lbm_plan64_kernel_name(const lbm_internal::Plan64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_run_launches(const lbm_internal::Plan64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_run_launches: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_internal::plan64_next_steps(*plan, left);
+    if (n < cap) { steps[n] = k; full[n] = plan->tile_kernel && k == plan->tile_H; }
+    left -= k;
   }
   return n;
 }

@@ -3,7 +3,12 @@
 tests/golden/check/ (tolerance 1 %) and to the Reynolds number the reference published (tests/golden/f64_published.json), with the
 largest relative distance of av_vels from the shipped file beside it.
 
-    python scripts/check_f64_decks.py [--decks 128x128,128x256] [--out profiles/r07/check_f64_decks.txt]
+    python scripts/check_f64_decks.py [--decks 128x128,128x256] [--flags 512] [--out profiles/r07/check_f64_decks.txt]
+
+LBM_TUNE_TILE64_MAX and LBM_TUNE_TILE64_GEOM of the caller's environment reach the CLI; every other LBM_* variable is dropped.  Each
+deck's report ends with the kernel that ran and its launches (LBM_DESCRIBE=1).
+
+--flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS: several steps per launch where the grid is eligible).
 
 One CLI process per deck, each under a time limit; the first failure ends the script (exit status 1)."""
 import argparse
@@ -29,16 +34,20 @@ def main():
     ap.add_argument("--decks", default=",".join(DECKS))
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per deck")
+    ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS)")
     a = ap.parse_args()
     lbm.build()
     with open(os.path.join(GOLDEN, "f64_published.json")) as fh:
         published = json.load(fh)["reynolds"]
-    lines = ["# LBM_PRECISION=double bin/d2q9-bgk on the shipped decks (full length), then checker.check_files against tests/golden/check/ (tolerance 1 %)",
+    lines = [f"# LBM_PRECISION=double{f' LBM_FLAGS={a.flags}' if a.flags else ''} bin/d2q9-bgk on the shipped decks (full length), then checker.check_files against tests/golden/check/ (tolerance 1 %)",
              "# and the Reynolds line against the number the reference published"]
     ok = True
     for name in a.decks.split(","):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_")}
+        env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_") or k in ("LBM_TUNE_TILE64_MAX", "LBM_TUNE_TILE64_GEOM")}
         env["LBM_PRECISION"] = "double"
+        env["LBM_DESCRIBE"] = "1"                      # one line on stderr: the kernel that ran and its launches
+        if a.flags:
+            env["LBM_FLAGS"] = str(a.flags)
         with tempfile.TemporaryDirectory() as tmp:
             cmd = [lbm.CLI_PATH, os.path.join(GOLDEN, "decks", f"input_{name}.params"), os.path.join(GOLDEN, "decks", f"obstacles_{name}.dat")]
             r = subprocess.run(cmd, cwd=tmp, env=env, capture_output=True, text=True, timeout=a.timeout)
@@ -48,6 +57,11 @@ def main():
                 ok = False
                 break
             out = r.stdout.splitlines()
+            ran = [l for l in r.stderr.splitlines() if l.startswith("kernel: ")]
+            if len(ran) != 1:
+                lines.append("the CLI did not say which kernel ran")
+                ok = False
+                break
             ref_fs = os.path.join(GOLDEN, "check", f"{name}.final_state.dat.gz")
             have_fs = os.path.exists(ref_fs)
             ref_av = os.path.join(GOLDEN, "check", f"{name}.av_vels.dat.gz")
@@ -60,7 +74,7 @@ def main():
         re_rel = abs(float(re_text) - float(pub["value"])) / float(pub["value"])
         report = [rep.message, f"av_vels, largest relative distance from the shipped file: {av_rel:.3e}",
                   f"Reynolds number: {re_text}   published ({pub['source']}): {pub['value']}   relative distance {re_rel:.3e}",
-                  out[2], out[5]]
+                  out[2], out[5], ran[0]]
         lines += report
         ok = ok and rep.ok
         print("\n".join([f"== {name}"] + report), flush=True)

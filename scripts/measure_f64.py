@@ -14,11 +14,23 @@ Run it under a time limit, one workload per process (--work; --out then appends)
     timeout -k 10 120 python scripts/measure_f64.py --work 128  --out $F
 
 Bytes: a step reads and writes nine populations per cell, 144 B per cell-step in double and 72 B in float (the obstacle bit and the
-partial sums are not counted).  A record, not a gate."""
+partial sums are not counted).  A record, not a gate.
+
+--tile: LBM64_FLAG_TILE_STEPS (lbm_tile_kernel_f64, several steps per launch) in every geometry beside the one-step double path of a
+BASELINE build of the library (--baseline-lib: the parent commit's liblbm_d2q9.so, built beside this one and loaded privately), on the
+shipped decks at full length and on 512 x 512: device time of whole runs, the contexts alternating run by run.
+
+    F=profiles/r08/f64_tile.txt; rm -f $F
+    for w in 128x128 128x256 256x256 512x512 1024x1024; do
+      timeout -k 10 240 python scripts/measure_f64.py --tile --baseline-lib mpilattice-boltzmann_amd/lib/variants/liblbm_d2q9_parent.so --work $w --out $F || break
+    done"""
 import argparse
+import ctypes as C
 import os
 import statistics
 import sys
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -71,13 +83,117 @@ def measure(name, steps, reps, warm, lines):
     print("\n".join(lines[-4:]), flush=True)
 
 
+TILE_GEOMS = (84, 88, 164, 168)
+TILE_DECKS = {"128x128": None, "128x256": None, "256x256": None, "512x512": 10000, "1024x1024": None}      # steps; None: the deck's max_iters
+
+
+class BaselineGrid64:
+    """lbm64_* of another build of the library (dlopen'ed privately): create, run, last_run_kernel_ms, describe, close."""
+
+    def __init__(self, path, p, obst, flags=0):
+        # RTLD_DEEPBIND: the two builds export the same names (weak inline functions among them, whose types may differ between the
+        # builds); the baseline must call its own, not those of the library the package loaded first
+        self.lib = C.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
+        for name, (res, args) in f64._SIGNATURES.items():
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = res, args
+        self.lib.lbm_last_error.restype = C.c_char_p
+        self.obst = np.ascontiguousarray(obst, dtype=np.int32)
+        self.cp = f64._cparams(p)
+        self.ctx = C.c_void_p()
+        self._check(self.lib.lbm64_create(C.byref(self.ctx), C.byref(self.cp), int(self.obst.size - np.count_nonzero(self.obst)),
+                                          self.obst.ctypes.data_as(C.POINTER(C.c_int)), 0, flags))
+
+    def _check(self, rc):
+        if rc:
+            raise SystemExit(f"baseline library: {self.lib.lbm_last_error().decode()}")
+
+    def run(self, n):
+        av = np.zeros(n, np.float64)
+        self._check(self.lib.lbm64_run(self.ctx, n, av.ctypes.data_as(C.POINTER(C.c_double))))
+        return av
+
+    def last_run_kernel_ms(self):
+        ms, n = C.c_double(0.0), C.c_int(0)
+        self._check(self.lib.lbm64_last_run_kernel_ms(self.ctx, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def describe(self):
+        name = C.create_string_buffer(256)
+        self._check(self.lib.lbm64_describe(self.ctx, name, 256, None, None, None))
+        return {"kernel": name.value.decode()}
+
+    def close(self):
+        self.lib.lbm64_destroy(self.ctx)
+
+
+def measure_tile(name, baseline_lib, reps, lines, steps_override=None):
+    if name in ("128x128", "128x256", "256x256", "1024x1024"):
+        d = os.path.join(ROOT, "tests", "golden", "decks")
+        p = f64.read_params64(os.path.join(d, f"input_{name}.params"))
+        obst = lbm.read_obstacles(os.path.join(d, f"obstacles_{name}.dat"), p.nx, p.ny)[0]
+    else:
+        p, obst = deck(name)
+    steps = steps_override or TILE_DECKS[name] or p.max_iters
+    os.environ["LBM_TUNE_TILE64_MAX"] = str(1 << 30)      # read when a context is made: every geometry on every deck
+    runs = {"one-step (baseline build)": BaselineGrid64(baseline_lib, p, obst)}
+    for geom in TILE_GEOMS:
+        os.environ["LBM_TUNE_TILE64_GEOM"] = str(geom)
+        g = f64.Grid64(p, obst, flags=f64.FLAG_TILE_STEPS)
+        if not g.describe()["kernel"].startswith("lbm_tile_kernel_f64<"):
+            raise SystemExit(f"{name}, geometry {geom}: the context runs {g.describe()['kernel']}")
+        runs[f"<{geom // 10},{geom % 10}>"] = g
+    kernels = {k: q.describe()["kernel"] for k, q in runs.items()}
+    first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
+    base = first["one-step (baseline build)"]
+    for k, av in first.items():                            # the same run: av_vels agree to the order of their additions
+        if not np.allclose(av, base, rtol=1e-12, atol=0.0):
+            raise SystemExit(f"{name}, {k}: av_vels differ from the baseline's by {np.max(np.abs(av - base) / base):.3e}")
+    ms = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, q in runs.items():                          # alternate: all see the same drift of the card
+            q.run(steps)
+            ms[k].append(q.last_run_kernel_ms()[0])
+    for q in runs.values():
+        q.close()
+    lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; device time of a run's step launches")
+    for k in runs:
+        v = ms[k]
+        lines.append(f"  {k:26s} {kernels[k]:28s} s/run median {statistics.median(v) / 1e3:9.5f}  min {min(v) / 1e3:9.5f}  max {max(v) / 1e3:9.5f}   us/step {1e3 * statistics.median(v) / steps:8.3f}")
+    b = ms["one-step (baseline build)"]
+    best = min((k for k in runs if k.startswith("<")), key=lambda k: statistics.median(ms[k]))
+    gain = statistics.median(b) - statistics.median(ms[best])
+    spreads = (max(b) - min(b)) + (max(ms[best]) - min(ms[best]))
+    lines.append(f"  fastest geometry {best}: baseline / tiled {statistics.median(b) / statistics.median(ms[best]):.3f}; median gain {gain / 1e3:.5f} s against "
+                 f"the two max - min spreads together {spreads / 1e3:.5f} s -> {'a win' if gain > spreads else 'no win'}")
+    print("\n".join(lines[-(len(runs) + 2):]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small step counts (a functional check of this script)")
     ap.add_argument("--work", help="one workload only: 8192, 1024 or 128 (--out appends)")
     ap.add_argument("--out")
+    ap.add_argument("--tile", action="store_true", help="LBM64_FLAG_TILE_STEPS in every geometry against --baseline-lib's one-step path; --work: a deck")
+    ap.add_argument("--baseline-lib", help="liblbm_d2q9.so of the parent commit")
     a = ap.parse_args()
     lbm.build()
+    if a.tile:
+        if not a.baseline_lib or not os.path.exists(a.baseline_lib):
+            ap.error("--tile needs --baseline-lib, an existing build of the library")
+        decks = [a.work] if a.work else list(TILE_DECKS)
+        if any(d not in TILE_DECKS for d in decks):
+            ap.error(f"--work: one of {', '.join(TILE_DECKS)}")
+        lines = [] if a.work and a.out and os.path.exists(a.out) else [
+            "# scripts/measure_f64.py --tile: lbm_tile_kernel_f64 (LBM64_FLAG_TILE_STEPS), every geometry, beside the one-step double path of the parent commit's build",
+            "# device time of whole runs (lbm64_last_run_kernel_ms: events around the step launches of a run)"]
+        for d in decks:
+            measure_tile(d, a.baseline_lib, 3 if a.quick else 5, lines, steps_override=200 if a.quick else None)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a" if a.work else "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
     lines = ["# scripts/measure_f64.py: lbm_step_kernel_f64 beside the float one-step kernel, device time per step (events around the step launches)"]
     if a.quick:
         work = {"1024": ("1024x1024", 40, 3, 1), "128": ("128x128", 400, 3, 1)}
