@@ -463,6 +463,13 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   // then relaxes the ring pair and writes both (the dealing above takes two passes for each of sub-steps 1 - 3, every pair with the
   // term code).  Each lane adds exactly one pair's term per sub-step: acc[j-1] is that term, its compensated low part already added.
   // Plane 0 and the flag byte are kept in LDS for ring pairs only.
+  // Sub-step 1 has an interior form for tiles that are `inner` and hold no uncounted rows or columns (all but the edge tiles of a
+  // launch), chosen by a block-uniform branch.  Every owned pair is then computed, kept and counted, no source wraps and no row is
+  // missing, so it is two straight-line sections (the owned pair, then the ring pair of the first lanes) instead of one rolled body
+  // that serves both: one vector offset per pair on nine block-uniform plane bases that hold the rows' -+ nx as well as the x -+ 1, the
+  // owned pair's frame address the lane's fixed one, its flag bits constants.  The arithmetic of a pair is the same code in both forms,
+  // and both forms share the in-LDS sub-steps: a second, specialised copy of those was 2 % faster at 8192 x 8192 and made the whole
+  // kernel, the edge tiles' code included, 2.5 % slower at 1024 x 1024.
   auto owned_substeps = [&](auto count_c) __attribute__((always_inline)) {
     constexpr bool COUNT = decltype(count_c)::value;
     constexpr int TP = TX / 2;                                         // owned pairs per tile row
@@ -490,6 +497,56 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     const int py = tid / TP, ofx = EX + 2 * (tid - py * TP), ofy = EY + py;
     f2 own0 = f2{0.0f, 0.0f};                                          // population 0 of the owned pair
     uint32_t ofl = 0;                                                  // its flag bits; 0: not computed
+    if (!COUNT && inner) {                                             // block-uniform
+      // ---- sub-step 1, interior form: the owned pair, then a ring pair (the first G::ring_pairs(1) lanes)
+      const float* const here0 = a.srck[0], * const here1 = a.srck[1] - 1, * const here3 = a.srck[3] + 1;
+      const float* const south2 = a.srck[2] - nx, * const south5 = a.srck[5] - 1 - nx, * const south6 = a.srck[6] + 1 - nx;
+      const float* const north4 = a.srck[4] + nx, * const north8 = a.srck[8] - 1 + nx, * const north7 = a.srck[7] + 1 + nx;
+      // the mask's base is read here, with the plane bases, not between the loads of a pair behind a wait of its own; the address
+      // space is named again because the compiler cannot see through the statement that holds the value in scalar registers
+      typedef const __attribute__((address_space(1))) char* global_bytes;
+      const uint32_t* mask_arg = a.mask;
+      asm volatile("" : "+s"(mask_arg));
+      const global_bytes mask = (global_bytes)mask_arg;
+      auto pull_inner = [&](const int fx, const int fy, f2 (&p)[9], uint32_t& mbits) __attribute__((always_inline)) -> uint32_t {
+        const int cell = tile_row_base + __mul24(fy - EY, nx) + x0 + fx - EX;
+        const uint32_t o = 4u * static_cast<uint32_t>(cell);
+        p[0] = at_byte<f2>(here0, o);                                                    // :530-538
+        p[2] = at_byte<f2>(south2, o);
+        p[4] = at_byte<f2>(north4, o);
+        p[1] = at_byte<f2u>(here1, o);
+        p[5] = at_byte<f2u>(south5, o);
+        p[8] = at_byte<f2u>(north8, o);
+        p[3] = at_byte<f2u>(here3, o);
+        p[6] = at_byte<f2u>(south6, o);
+        p[7] = at_byte<f2u>(north7, o);
+        mbits = (*(const __attribute__((address_space(1))) uint32_t*)(mask + 4u * (static_cast<uint32_t>(cell) >> 5)) >> (cell & 31)) & 3u;
+        return o;
+      };
+      {
+        f2 p[9], out[9];
+        uint32_t mbits;
+        pull_inner(ofx, ofy, p, mbits);
+        const bool accel_row_here = on_accel_row(sy0 + py);
+        acc[0] = relax(p, mbits, accel_row_here, mbits, out);
+  #pragma unroll
+        for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, ofy * W, ofx, out[k]);
+        own0 = out[0];
+        ofl = pair_flag_bits(mbits, true, accel_row_here, false);
+      }
+      if (tid < G::ring_pairs(1)) {
+        int fx, fy;
+        ring_pos(std::integral_constant<int, 1>{}, tid, fx, fy);
+        f2 p[9], out[9];
+        uint32_t mbits;
+        pull_inner(fx, fy, p, mbits);
+        const bool accel_row_here = on_accel_row(sy0 + fy - EY);
+        relax(p, mbits, accel_row_here, 3u, out);
+  #pragma unroll
+        for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
+        pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(pair_flag_bits(mbits, false, accel_row_here, false));
+      }
+    } else {
     // ---- sub-step 1: item 0 = the owned pair, item 1 = a ring pair (the first G::ring_pairs(1) lanes)
   #pragma unroll 1
     for (int item = 0; item < 2; ++item) {
@@ -518,6 +575,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       }
       if (own) ofl = fl;
       else pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(fl);
+    }
     }
     LBM_MSTAMP(1);
     __syncthreads();
