@@ -16,6 +16,12 @@
  *     the sub-step's region has more than B cells), six butterfly levels join the 64 lanes of a wave, one lane adds the B / 64 waves'
  *     sums serially: the tile's sum.  The fold then adds the tiles' sums: a lane ceil(tiles / F) of them serially, six butterfly
  *     levels, F / 64 waves' sums serially, where F = B in block 0 of the next launch and F = 256 in the last fold of a run.
+ *     With LBM64_FLAG_MULTI_STEPS on an eligible grid (lbm_multi_kernel_f64<K>, 32 x 16 tiles, blocks of 512 lanes) the tree of one
+ *     entry is: a lane adds the terms of the owned cells it meets in that sub-step (at most two — the x-pair it pulls in the first
+ *     sub-step of a launch, the two cells it is dealt where a sub-step's region has more than 512 — so 2 additions), six butterfly
+ *     levels join the 64 lanes of a wave, one lane adds the eight waves' sums serially (7 additions): the tile's sum.  The fold then adds
+ *     the tiles' sums exactly as above: a lane ceil(tiles / F) of them serially, six butterfly levels, F / 64 waves' sums serially,
+ *     where F = 512 in block 0 of the next launch and F = 256 in the last fold of a run.
  *     No atomics: the same state, grid and geometry give the same bits in every run.
  * tests/f64_ref.c restates it on a CPU; DESIGN.md section 5 gives the measured distances to the reference's shipped results.
  *
@@ -24,8 +30,9 @@
  * lbm_last_error of lbm_d2q9.h serve this mode as they are.
  *
  * OUT OF SCOPE of this mode (use lbm_d2q9.h): row or tile partitions and every halo transport (peer-to-peer, RCCL, split-phase calls)
- * — a context is a whole periodic grid on one GPU; several steps per launch of grids above the size cap of LBM64_FLAG_TILE_STEPS
- * (lbm_multi_kernel) — without that flag, and on every grid it does not take, every step is one launch of lbm_step_kernel_f64; the
+ * — a context is a whole periodic grid on one GPU (several steps per launch are opt-in: LBM64_FLAG_TILE_STEPS for small grids,
+ * LBM64_FLAG_MULTI_STEPS for large ones that 32 x 16 tiles cover; without them, and on every grid they do not take, every step is one
+ * launch of lbm_step_kernel_f64); the
  * fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH); a state digest (lbm_state_checksum) of doubles.
  */
 #ifndef LBM_D2Q9_F64_H
@@ -47,6 +54,14 @@ extern "C" {
  * every other grid runs lbm_step_kernel_f64 exactly as without the flag.  Populations are the same bits either way; av_vels differs in
  * the order of its additions only (above).  lbm_create of lbm_d2q9.h ignores this bit. */
 #define LBM64_FLAG_TILE_STEPS 512u
+
+/* lbm64_create flag, alone or with the flags above: advance a large whole grid several steps per launch with lbm_multi_kernel_f64<K>
+ * (32 x 16 tiles, an in-place LDS frame, K steps per launch; csrc/kernels/multi64.h).  Taken where nx is a multiple of 32, ny a
+ * multiple of 16, nx * ny is at least LBM_TUNE_MULTI64_MIN and LBM64_FLAG_TILE_STEPS does not take the grid for the tiled kernel;
+ * K is LBM_TUNE_MULTI64_K (scripts/README.md has both knobs and their measured defaults).  Every other grid runs exactly as without
+ * this flag.  A run of n steps is floor(n / K) launches of K steps and at most one shorter launch, the last.  Populations are the
+ * same bits either way; av_vels differs in the order of its additions only (above).  lbm_create of lbm_d2q9.h ignores this bit. */
+#define LBM64_FLAG_MULTI_STEPS 1024u
 
 /* t_param (d2q9-bgk.c:79-90) with its three floats as doubles. */
 typedef struct lbm64_params {
@@ -84,7 +99,8 @@ int lbm64_write_av_vels(const char* path, const double* av_vels, int n);
 
 /* A whole periodic nx x ny grid (ny >= 3) on GPU `device`, in the initial state of d2q9-bgk.c:880-902.  obstacles = ny*nx ints.
  * flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default once the two grids
- * exceed the Infinity Cache), each with or without LBM64_FLAG_TILE_STEPS; any other flag is refused. */
+ * exceed the Infinity Cache), each with or without LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS (with both, the tiled kernel where
+ * it takes the grid, otherwise lbm_multi_kernel_f64 where that does); any other flag is refused. */
 int lbm64_create(lbm64_ctx** ctx, const lbm64_params* params, int free_cells, const int* obstacles, int device, unsigned flags);
 int lbm64_destroy(lbm64_ctx* ctx);
 
@@ -104,12 +120,15 @@ int lbm64_get_observables(lbm64_ctx* ctx, double* obs);
  * block, then the blocks' sums on the host). */
 int lbm64_av_velocity_sum(lbm64_ctx* ctx, double* tot_u);
 
-/* Device time of the step launches of the last lbm64_run (events around them), and their number (tiled: launches, not steps). */
+/* Device time of the step launches of the last lbm64_run (events around them), and their number (tiled and multi-step kernels:
+ * launches, not steps — ceil(n / K) for lbm_multi_kernel_f64<K>). */
 int lbm64_last_run_kernel_ms(lbm64_ctx* ctx, double* ms, int* launches);
 
 /* What a step launch looks like: the kernel's name, its work blocks (one more block folds the previous step's sums), the cells
  * a block advances (256 lanes x cells per lane x units per lane) and the bytes of the two grids.  A context that
- * LBM64_FLAG_TILE_STEPS advances with the tiled kernel: "lbm_tile_kernel_f64<T, H>", the tiles, T * T. */
+ * LBM64_FLAG_TILE_STEPS advances with the tiled kernel: "lbm_tile_kernel_f64<T, H>", the tiles, T * T.  One that LBM64_FLAG_MULTI_STEPS
+ * advances with the multi-step kernel: "lbm_multi_kernel_f64<K>" ("lbm_multi_kernel_f64<K,nt>" with non-temporal stores), the tiles,
+ * 32 * 16. */
 int lbm64_describe(const lbm64_ctx* ctx, char* kernel_name, size_t len, long long* blocks, long long* cells_per_block, long long* state_bytes);
 
 #ifdef __cplusplus

@@ -15,8 +15,9 @@
  *
  * LBM_PRECISION=double runs the double-precision mode (include/lbm_d2q9_f64.h): the reference's arithmetic with every float object a double,
  * which is what the reference's shipped results and README were produced with; the same five lines and two files.  One GPU only
- * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES) and 512 (LBM64_FLAG_TILE_STEPS:
- * a small grid advances several steps per launch, the same populations and files) and has no other default.  LBM_DESCRIBE=1 adds one
+ * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES), 512 (LBM64_FLAG_TILE_STEPS:
+ * a small grid advances several steps per launch, the same populations and files) and 1024 (LBM64_FLAG_MULTI_STEPS: the same for a
+ * large grid that 32 x 16 tiles cover, with lbm_multi_kernel_f64), in any sum, and has no other default.  LBM_DESCRIBE=1 adds one
  * line on stderr: the kernel that advanced the grid (lbm64_describe) and the step launches of the run.
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by

@@ -117,30 +117,24 @@ __device__ __forceinline__ double finish_cell_f64(const double (&t)[9], bool blo
 
 // Rows a destination row pulls from (d2q9-bgk.c:511-512 with one rank: periodic), as element offsets of their first cell.
 struct Rows64 { size_t here, south, north; };
-__device__ __forceinline__ Rows64 rows_of(const Step64Args& a, uint32_t y)
+__device__ __forceinline__ Rows64 rows_of(uint32_t nx, uint32_t ny, uint32_t y)
 {
   Rows64 r;
-  r.here = static_cast<size_t>(y) * a.nx;
-  r.south = static_cast<size_t>(y > 0 ? y - 1 : a.ny - 1) * a.nx;
-  r.north = static_cast<size_t>(y + 1 < a.ny ? y + 1 : 0) * a.nx;
+  r.here = static_cast<size_t>(y) * nx;
+  r.south = static_cast<size_t>(y > 0 ? y - 1 : ny - 1) * nx;
+  r.north = static_cast<size_t>(y + 1 < ny ? y + 1 : 0) * nx;
   return r;
 }
+__device__ __forceinline__ Rows64 rows_of(const Step64Args& a, uint32_t y) { return rows_of(a.nx, a.ny, y); }
 
-// The x-pair form (nx even): the two cells at (y, x0), (y, x0 + 1), x0 even.  Populations 0, 2, 4 come by 16-byte aligned loads,
-// the east- and west-moving ones by loads shifted one double; the pair at x0 == 0 fetches its west column from x = nx-1 and the
-// pair at x0 == nx-2 its east column from x = 0, each lane for itself (nx = 2: both on the one lane of a row).
-template <bool NT>
-__device__ __forceinline__ double step_pair_f64(const Step64Args& a, uint32_t pair)
+// The pull of an x-pair (d2q9-bgk.c:530-538; nx even): the two cells at (y, x0), (y, x0 + 1), x0 even.  Populations 0, 2, 4 come by
+// 16-byte aligned loads, the east- and west-moving ones by loads shifted one double; the pair at x0 == 0 fetches its west column from
+// x = nx-1 and the pair at x0 == nx-2 its east column from x = 0, each lane for itself (nx = 2: both on the one lane of a row).
+__device__ __forceinline__ void pull_pair_f64(const double* src, size_t ps, uint32_t nx, const Rows64& r, uint32_t x0, d2 (&p)[9])
 {
-  const uint32_t c = pair * kPairCells;
-  const uint32_t y = c / a.nx;
-  const uint32_t x0 = c - y * a.nx;
-  const size_t ps = a.ps;
-  const Rows64 r = rows_of(a, y);
-  const double* here = a.src + r.here + x0;
-  const double* south = a.src + r.south + x0;
-  const double* north = a.src + r.north + x0;
-  d2 p[9];                                     // pull (d2q9-bgk.c:530-538)
+  const double* here = src + r.here + x0;
+  const double* south = src + r.south + x0;
+  const double* north = src + r.north + x0;
   p[0] = load2(here);
   p[2] = load2(south + 2 * ps);
   p[4] = load2(north + 4 * ps);
@@ -150,18 +144,31 @@ __device__ __forceinline__ double step_pair_f64(const Step64Args& a, uint32_t pa
   p[3] = load2u(here + 3 * ps + 1);
   p[6] = load2u(south + 6 * ps + 1);
   p[7] = load2u(north + 7 * ps + 1);
-  const uint32_t mbits = (a.mask[c >> 5] >> (c & 31u)) & 3u;   // c is even: both bits in one word
   if (x0 == 0) {                               // x_w wraps to nx-1 (:529)
-    const size_t last = a.nx - 1;
-    p[1].x = a.src[ps + r.here + last];
-    p[5].x = a.src[5 * ps + r.south + last];
-    p[8].x = a.src[8 * ps + r.north + last];
+    const size_t last = nx - 1;
+    p[1].x = src[ps + r.here + last];
+    p[5].x = src[5 * ps + r.south + last];
+    p[8].x = src[8 * ps + r.north + last];
   }
-  if (x0 == a.nx - kPairCells) {               // x_e wraps to 0 (:527-528)
-    p[3].y = a.src[3 * ps + r.here];
-    p[6].y = a.src[6 * ps + r.south];
-    p[7].y = a.src[7 * ps + r.north];
+  if (x0 == nx - kPairCells) {                 // x_e wraps to 0 (:527-528)
+    p[3].y = src[3 * ps + r.here];
+    p[6].y = src[6 * ps + r.south];
+    p[7].y = src[7 * ps + r.north];
   }
+}
+
+// The x-pair form (nx even): pull_pair_f64, then the two cells one after the other.
+template <bool NT>
+__device__ __forceinline__ double step_pair_f64(const Step64Args& a, uint32_t pair)
+{
+  const uint32_t c = pair * kPairCells;
+  const uint32_t y = c / a.nx;
+  const uint32_t x0 = c - y * a.nx;
+  const size_t ps = a.ps;
+  const Rows64 r = rows_of(a, y);
+  d2 p[9];
+  pull_pair_f64(a.src, ps, a.nx, r, x0, p);
+  const uint32_t mbits = (a.mask[c >> 5] >> (c & 31u)) & 3u;   // c is even: both bits in one word
   const bool accel = static_cast<int>(y) == a.accel_row;
   d2 out[9];
   double acc = 0.0;

@@ -6,8 +6,9 @@
 // pull-stream, moments + equilibrium, BGK relaxation / bounce-back, the sum|u| terms into per-block partials, accelerate_flow as an
 // epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  lbm_step_kernel_f64<CELLS, NT> makes one
 // step per launch; with LBM64_FLAG_TILE_STEPS a small grid is advanced by lbm_tile_kernel_f64<T, H, FULL> (kernels/tile64.h), up to H
-// steps per launch.  Whole periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph, no state digest).
-// What a context gets of all that is decided in lbm_plan.cpp (Plan64, lbm_internal.h); this unit allocates and launches by the plan.
+// steps per launch; with LBM64_FLAG_MULTI_STEPS a large one by lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h), up to K.  Whole
+// periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph, no state digest).  What a context gets of all that
+// is decided in lbm_plan.cpp (Plan64 and PlanMulti64, lbm_internal.h); this unit allocates and launches by the plans.
 //
 // Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (the float path's rule in elements: lbm_plan.cpp plane_stride_floats), two grids
 // swapped per launch, the obstacle map as the float path's bitfield.  Compiled with -ffp-contract=off like the rest of the library:
@@ -30,6 +31,7 @@
 #include "lbm_knobs.h"
 #include "kernels/step64.h"
 #include "kernels/tile64.h"
+#include "kernels/multi64.h"
 
 namespace {
 
@@ -51,6 +53,7 @@ struct lbm64_ctx {
   double free_cells_inv = 0.0;
   int device = 0;
   lbm_internal::Plan64 plan{};       // kernels, launch shapes and sizes (lbm_plan.cpp plan64_whole): written once
+  lbm_internal::PlanMulti64 multi{}; // lbm_multi_kernel_f64's part of them (plan64_multi): written once
   size_t ncells = 0, ps = 0;
   double* grid_alloc[2] = {nullptr, nullptr};
   double* grid[2] = {nullptr, nullptr};      // plane 0 row 0 (after the front guard)
@@ -83,6 +86,13 @@ constexpr Tile64Kernel kTile64Kernels[kTile64Rows] = {
   &lbm_tile_kernel_f64<8, 8, false>,  &lbm_tile_kernel_f64<8, 8, true>,  &lbm_tile_kernel_f64<8, 4, false>,  &lbm_tile_kernel_f64<8, 4, true>,
 };
 static_assert(tile64_row(16, 8, false) == 0 && tile64_row(16, 4, true) == 3 && tile64_row(8, 8, false) == 4 && tile64_row(8, 4, true) == 7, "the order of kTile64Kernels");
+
+using Multi64Kernel = void (*)(Multi64Args);
+// every instantiation of the multi-step kernel, by multi64_row(K, NT, FULL) (lbm_geometry.h, which also has the block size and LDS bytes)
+#define LBM_MULTI64_ROWS(K) &lbm_multi_kernel_f64<K, false, false>, &lbm_multi_kernel_f64<K, false, true>, &lbm_multi_kernel_f64<K, true, false>, &lbm_multi_kernel_f64<K, true, true>
+constexpr Multi64Kernel kMulti64Kernels[kMulti64Rows] = {LBM_MULTI64_ROWS(2), LBM_MULTI64_ROWS(3), LBM_MULTI64_ROWS(4)};
+#undef LBM_MULTI64_ROWS
+static_assert(kMulti64MinK == 2 && kMulti64MaxK == 4 && multi64_row(2, false, true) == 1 && multi64_row(3, true, false) == 6 && multi64_row(4, true, true) == 11, "the order of kMulti64Kernels");
 
 int ensure_sums(lbm64_ctx* c, int n)
 {
@@ -131,8 +141,8 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   if (p->nx < 1) { lbm_internal::set_error("lbm64_create: nx must be positive"); return 1; }
   if (p->ny < 3) { lbm_internal::set_error("lbm64_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
   if (free_cells <= 0) { lbm_internal::set_error("lbm64_create: free_cells must be positive"); return 1; }
-  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS)) != 0u) {
-    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only, each with or without LBM64_FLAG_TILE_STEPS (whole grids, exact arithmetic)");
+  if ((flags & ~lbm_internal::kFlags64) != 0u) {
+    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only, each with or without LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS (whole grids, exact arithmetic)");
     return 1;
   }
   if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { lbm_internal::set_error("lbm64_create: grid too large for 32-bit cell indices"); return 1; }
@@ -149,6 +159,8 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   c->ncells = static_cast<size_t>(p->nx) * p->ny;
   lbm_internal::plan64_whole(c->knobs, p, flags, &c->plan);
   const lbm_internal::Plan64& plan = c->plan;
+  lbm_internal::plan64_multi(c->knobs, p, plan, &c->multi);
+  const lbm_internal::PlanMulti64& multi = c->multi;
   c->ps = static_cast<size_t>(plan.ps);
 
   auto fail = [&](void) { lbm64_destroy(c); return 1; };
@@ -178,11 +190,16 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
     HIP_TRY_C(hipMalloc(&c->mask, sizeof(uint32_t) * mwords));
     HIP_TRY_C(hipMemcpy(c->mask, bits.data(), sizeof(uint32_t) * mwords, hipMemcpyHostToDevice));
   }
-  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * static_cast<size_t>(plan.partials_cap)));
+  for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&c->partials[i], sizeof(double) * static_cast<size_t>(std::max(plan.partials_cap, multi.multi_kernel ? multi.partials_cap : 0))));
   if (plan.tile_kernel && plan.tile_lds_bytes > 65536) {     // dynamic LDS above 64 KiB: raised once, for the two instantiations the context launches
     for (int full = 0; full < 2; ++full)
       HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(kTile64Kernels[tile64_row(plan.tile_T, plan.tile_H, full != 0)]),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, plan.tile_lds_bytes));
+  }
+  if (multi.multi_kernel && multi.lds_bytes > 65536) {
+    for (int full = 0; full < 2; ++full)
+      HIP_TRY_C(hipFuncSetAttribute(reinterpret_cast<const void*>(kMulti64Kernels[multi64_row(multi.K, multi.nt_stores != 0, full != 0)]),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, multi.lds_bytes));
   }
   HIP_TRY_C(hipMalloc(&c->counter, sizeof(int)));
   HIP_TRY_C(hipMemsetAsync(c->counter, 0, sizeof(int), c->stream));
@@ -246,6 +263,39 @@ int lbm64_run(lbm64_ctx* c, int n_steps, double* av_vels)
       ++launches;
     }
     last_n = plan.n_tiles;
+  } else if (c->multi.multi_kernel) {
+    // up to K steps per launch (lbm_plan.cpp plan64_multi_next_steps); block 0 of a launch folds the vectors of the launch before it
+    const lbm_internal::PlanMulti64& multi = c->multi;
+    Multi64Args a{};
+    a.mask = c->mask;
+    a.ps = c->ps;
+    a.nx = static_cast<int>(nx); a.ny = static_cast<int>(ny);
+    a.tiles_x = multi.tiles_x;
+    a.omega = c->p.omega;
+    a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+    a.accel_row = static_cast<int>(ny) - 2;
+    a.n_prev = multi.n_tiles;
+    a.sums = c->sums;
+    a.counter = c->counter;
+    HIP_TRY(hipEventRecord(c->ev_begin, s));
+    for (int left = n_steps; left > 0;) {
+      const int k = lbm_internal::plan64_multi_next_steps(multi, left);
+      left -= k;
+      a.src = c->grid[c->cur];
+      a.dst = c->grid[c->cur ^ 1];
+      a.ksteps = k;
+      a.accel_last = left > 0;
+      a.partials_out = c->partials[parity];
+      a.prev_partials = c->partials[parity ^ 1];
+      a.n_prev_vecs = last_vecs;
+      const Multi64Kernel kernel = kMulti64Kernels[multi64_row(multi.K, multi.nt_stores != 0, k == multi.K)];
+      kernel<<<dim3(multi.n_tiles + 1), dim3(multi.block), static_cast<size_t>(multi.lds_bytes), s>>>(a);   // + the fold block
+      last_vecs = k;
+      parity ^= 1;
+      c->cur ^= 1;
+      ++launches;
+    }
+    last_n = multi.n_tiles;
   } else {
     Step64Args a{};
     a.mask = c->mask;
@@ -390,6 +440,14 @@ int lbm64_describe(const lbm64_ctx* c, char* kernel_name, size_t len, long long*
 {
   if (!c) { lbm_internal::set_error("lbm64_describe: null context"); return 1; }
   const lbm_internal::Plan64& plan = c->plan;
+  const lbm_internal::PlanMulti64& multi = c->multi;
+  if (multi.multi_kernel) {
+    if (kernel_name && len > 0) lbm_internal::plan64_multi_kernel_name(multi, kernel_name, len);
+    if (blocks) *blocks = multi.n_tiles;
+    if (cells_per_block) *cells_per_block = static_cast<long long>(multi.TX) * multi.TY;
+    if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->ncells * sizeof(double));
+    return 0;
+  }
   if (kernel_name && len > 0) lbm_internal::plan64_kernel_name(plan, kernel_name, len);
   if (blocks) *blocks = plan.tile_kernel ? plan.n_tiles : plan.blocks;
   if (cells_per_block) *cells_per_block = plan.tile_kernel ? static_cast<long long>(plan.tile_T) * plan.tile_T : static_cast<long long>(kBlock) * plan.iters * plan.lane_cells;

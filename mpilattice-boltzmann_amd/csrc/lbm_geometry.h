@@ -96,6 +96,27 @@ constexpr int geom_for(int k, int g) { return (g == kGeomTall && k < 4) ? kGeomS
 // 76 / 72 / 68 / 64 wide instead of 72 / 68 / 68 / 64, frames 12 columns wider than needed.)
 constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
 
+// ---- lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h): lbm_multi_kernel's scheme with every object a double ----
+// A block of kMulti64Lanes lanes owns a kMulti64TX x kMulti64TY tile, one owned cell per lane in the last sub-step.  The LDS frame is ONE
+// buffer of (TX + 2 multi_ex(K-1)) x (TY + 2 (K-1)) cells of nine doubles, updated in place; behind it kMulti64Accs x waves doubles
+// of reduction scratch and one flag byte per frame cell.  K = 2: 36 x 18, 47.6 KB; K = 3: 36 x 20, 52.8 KB (three blocks in a CU's
+// 160 KiB); K = 4: 40 x 22, 64.5 KB (two).
+constexpr int kMulti64TX = 32, kMulti64TY = 16, kMulti64Lanes = 512, kMulti64MinK = 2, kMulti64MaxK = 4;
+constexpr int kMulti64Accs = 4;       // per-lane accumulators, one per sub-step: what wave_sum_vec4 joins
+constexpr bool multi64_k_ok(int k) { return k >= kMulti64MinK && k <= kMulti64MaxK; }
+constexpr int multi64_frame_x(int k) { return kMulti64TX + 2 * multi_ex(k - 1); }
+constexpr int multi64_frame_y(int k) { return kMulti64TY + 2 * (k - 1); }
+constexpr int multi64_lds_bytes(int k)
+{
+  return multi64_frame_x(k) * multi64_frame_y(k) * (9 * 8 + 1) + 8 * kMulti64Accs * (kMulti64Lanes / 64);
+}
+constexpr int kMulti64Rows = (kMulti64MaxK - kMulti64MinK + 1) * 2 * 2;   // the host's table kMulti64Kernels (lbm_f64.hip): one row per (K, NT, FULL)
+constexpr int multi64_row(int k, bool nt, bool full) { return ((k - kMulti64MinK) * 2 + (nt ? 1 : 0)) * 2 + (full ? 1 : 0); }
+static_assert(kMulti64TX * kMulti64TY == kMulti64Lanes, "the last sub-step deals one owned cell to every lane");
+static_assert(kMulti64MaxK <= kMulti64Accs, "one accumulator per sub-step");
+static_assert((kMulti64TX + 2 * (kMulti64MaxK - 2)) * (kMulti64TY + 2 * (kMulti64MaxK - 2)) <= 2 * kMulti64Lanes, "a frame sub-step deals a lane at most two cells");
+static_assert(multi64_lds_bytes(kMulti64MaxK) <= 160 * 1024, "a block's LDS: at most what a CU gives one workgroup");
+
 // PART of lbm_multi_kernel (the forms themselves: kernels/multi.h): kPartPlain (whole periodic grids, and the launches of a partition that
 // compute its owned rows only), kPartGhost (a launch that also computes ghost rows: the counted test), kPartReady (owned rows only + the
 // ready words in the fold block), kPartTile (every launch of a rank of the 2-D decomposition: ghost rows AND ghost columns — the counted

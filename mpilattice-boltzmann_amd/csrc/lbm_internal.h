@@ -93,6 +93,26 @@ void plan64_kernel_name(const Plan64& plan, char* kernel_name, size_t len);
 // Steps of the next launch of a run with `left` steps remaining: 1 (one-step kernel), or up to tile_H.
 int plan64_next_steps(const Plan64& plan, int left);
 
+// lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h) for a context: LBM64_FLAG_MULTI_STEPS on a grid that TX x TY tiles cover exactly, of
+// at least LBM_TUNE_MULTI64_MIN cells, which Plan64.tile_kernel does not claim.  Plain data in this order (tests/test_plan64_multi.py
+// mirrors it); beside Plan64, whose layout does not change.
+struct PlanMulti64 {
+  int multi_kernel;                  // the context advances up to K steps per launch with it
+  int K, TX, TY;                     // steps of a full launch (LBM_TUNE_MULTI64_K); the tile (lbm_geometry.h)
+  int tiles_x, n_tiles;              // tiles per row; tiles (= work blocks of a launch); 0 where the tiles do not cover the grid
+  int block, lds_bytes;              // lanes and dynamic LDS bytes of a block
+  int nt_stores;                     // Plan64.nt_stores: the rule and flags of the one-step kernel
+  int partials_cap;                  // doubles of each partials buffer this kernel needs: K * n_tiles + 1
+};
+static_assert(sizeof(PlanMulti64) == 10 * sizeof(int), "no padding: the order above is the layout");
+// Fills *out for the context whose Plan64 is `plan` (the caller has checked the arguments as for plan64_whole).
+void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMulti64* out);
+void plan64_multi_kernel_name(const PlanMulti64& plan, char* kernel_name, size_t len);
+// Steps of the next launch with `left` steps remaining: K, or what is left as the one shorter launch that ends the run.
+int plan64_multi_next_steps(const PlanMulti64& plan, int left);
+// The flags lbm64_create takes: a store form, LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS.
+constexpr unsigned kFlags64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS;
+
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
 // up to at most the ghost rows, group_max at most.  Launch i of a group advances, besides the owned rows, ext(i) = the steps of the
@@ -166,3 +186,9 @@ extern "C" int lbm_plan64_sizeof(void);
 extern "C" int lbm_plan64_whole(const lbm64_params* p, unsigned flags, lbm_internal::Plan64* out);
 extern "C" int lbm_plan64_kernel_name(const lbm_internal::Plan64* plan, char* kernel_name, size_t len);
 extern "C" int lbm_plan64_run_launches(const lbm_internal::Plan64* plan, int n_steps, int* steps, int* full, int cap);
+// And for lbm_multi_kernel_f64: the PlanMulti64 a context of these arguments would get (0, or 1 where lbm64_create refuses them), its
+// kernel's name ("" where multi_kernel is 0), and the launches of a run (full[i] = 1 where launch i makes exactly K steps).
+extern "C" int lbm_plan64_multi_sizeof(void);
+extern "C" int lbm_plan64_multi(const lbm64_params* p, unsigned flags, lbm_internal::PlanMulti64* out);
+extern "C" int lbm_plan64_multi_kernel_name(const lbm_internal::PlanMulti64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* plan, int n_steps, int* steps, int* full, int cap);

@@ -497,6 +497,42 @@ int plan64_next_steps(const Plan64& c, int left)
   return c.tile_kernel ? std::min(c.tile_H, left) : std::min(1, left);
 }
 
+// LBM64_FLAG_MULTI_STEPS: lbm_multi_kernel_f64 where the tiled kernel does not claim the context, the tiles cover the grid exactly and
+// the grid has at least LBM_TUNE_MULTI64_MIN cells.  Both knobs' defaults are measured (profiles/r11/f64_multi.txt), us per step for the
+// one-step kernel | K = 2 / 3 / 4:  8192x8192 1715.9 | 1039.8 / 706.3 / 624.3   4096x4096 448.4 | 253.0 / 178.3 / 157.7   2048x2048 106.9 |
+// 67.5 / 46.4 / 41.3   1024x1024 23.46 | 18.40 / 13.70 / 11.99 (the tiled kernel there: 20.67).  K is the fastest at 8192 x 8192; the
+// minimum is the smallest measured size that beats the one-step kernel by more than both max - min spreads together (11.46 us against
+// 0.05 us), which is the smallest size measured.
+void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMulti64* out)
+{
+  PlanMulti64 m{};
+  constexpr int kDefaultK = 4;
+  m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kDefaultK;     // a malformed or unbuilt value: the default
+  m.TX = kMulti64TX; m.TY = kMulti64TY;
+  m.block = kMulti64Lanes;
+  m.lds_bytes = multi64_lds_bytes(m.K);
+  m.nt_stores = plan.nt_stores;
+  const bool tiles = p->nx % m.TX == 0 && p->ny % m.TY == 0;
+  m.tiles_x = tiles ? p->nx / m.TX : 0;
+  m.n_tiles = tiles ? m.tiles_x * (p->ny / m.TY) : 0;
+  m.multi_kernel = (plan.flags & LBM64_FLAG_MULTI_STEPS) != 0u && !plan.tile_kernel && tiles &&
+                   static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knobs.multi64_min);
+  m.partials_cap = m.K * m.n_tiles + 1;
+  *out = m;
+}
+
+void plan64_multi_kernel_name(const PlanMulti64& m, char* kernel_name, size_t len)
+{
+  if (!m.multi_kernel) { kernel_name[0] = '\0'; return; }
+  std::snprintf(kernel_name, len, m.nt_stores ? "lbm_multi_kernel_f64<%d,nt>" : "lbm_multi_kernel_f64<%d>", m.K);
+}
+
+// A run of n steps is floor(n / K) launches of K steps and at most one shorter launch, the last: a function of what is left of THIS run only.
+int plan64_multi_next_steps(const PlanMulti64& m, int left)
+{
+  return std::min(m.K, left);
+}
+
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
 
 // Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
@@ -820,10 +856,36 @@ int lbm_plan64_whole(const lbm64_params* p, unsigned flags, lbm_internal::Plan64
 {
   if (!p || !out) { set_error("lbm_plan64_whole: null argument"); return 1; }
   if (p->nx < 1 || p->ny < 3) { set_error("lbm_plan64_whole: nx must be positive and ny >= 3"); return 1; }
-  if ((flags & ~(LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS)) != 0u) { set_error("lbm_plan64_whole: a flag lbm64_create refuses"); return 1; }
+  if ((flags & ~lbm_internal::kFlags64) != 0u) { set_error("lbm_plan64_whole: a flag lbm64_create refuses"); return 1; }
   if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { set_error("lbm_plan64_whole: grid too large for 32-bit cell indices"); return 1; }
   lbm_internal::plan64_whole(knobs_from_env(), p, flags, out);
   return 0;
+}
+int lbm_plan64_multi_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanMulti64)); }
+int lbm_plan64_multi(const lbm64_params* p, unsigned flags, lbm_internal::PlanMulti64* out)
+{
+  lbm_internal::Plan64 plan;
+  if (!out) { set_error("lbm_plan64_multi: null argument"); return 1; }
+  if (lbm_plan64_whole(p, flags, &plan)) return 1;
+  lbm_internal::plan64_multi(knobs_from_env(), p, plan, out);
+  return 0;
+}
+int lbm_plan64_multi_kernel_name(const lbm_internal::PlanMulti64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_multi_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_multi_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || !multi64_k_ok(plan->K) || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_multi_run_launches: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_internal::plan64_multi_next_steps(*plan, left);
+    if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
+    left -= k;
+  }
+  return n;
 }
 int lbm_plan64_kernel_name(const lbm_internal::Plan64* plan, char* kernel_name, size_t len)
 {

@@ -9,8 +9,8 @@
         g.write_values("final_state.dat", "av_vels.dat", av_vels)
 
 The reference's arithmetic with every float object a double (the contract is in the header): whole periodic grids on one GPU, one
-step per launch of lbm_step_kernel_f64 or, with `flags=f64.FLAG_TILE_STEPS` on a small grid, several per launch of lbm_tile_kernel_f64
-(the same populations, bit for bit).  There is no CPU fallback: a missing library or symbol raises.
+step per launch of lbm_step_kernel_f64 or, with `flags=f64.FLAG_TILE_STEPS` on a small grid, several per launch of lbm_tile_kernel_f64,
+with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_multi_kernel_f64 (the same populations, bit for bit).  There is no CPU fallback: a missing library or symbol raises.
 """
 from __future__ import annotations
 
@@ -27,6 +27,7 @@ from .decks import Params
 ABI_VERSION = 1
 FLAG_NT_STORES, FLAG_NO_NT_STORES = _capi.FLAG_NT_STORES, _capi.FLAG_NO_NT_STORES
 FLAG_TILE_STEPS = 512        # LBM64_FLAG_TILE_STEPS: small grids advance several steps per launch (lbm_tile_kernel_f64); the same populations
+FLAG_MULTI_STEPS = 1024      # LBM64_FLAG_MULTI_STEPS: large grids that 32 x 16 tiles cover do (lbm_multi_kernel_f64); the same populations
 
 
 class CParams64(C.Structure):
@@ -187,4 +188,4 @@ class Grid64:
         return {"kernel": name.value.decode(), "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
 
 
-__all__ = ["ABI_VERSION", "EXPORTS", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "CParams64", "Grid64", "LbmError", "load_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]
+__all__ = ["ABI_VERSION", "EXPORTS", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "CParams64", "Grid64", "LbmError", "load_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]

@@ -8,7 +8,7 @@ largest relative distance of av_vels from the shipped file beside it.
 LBM_TUNE_TILE64_MAX and LBM_TUNE_TILE64_GEOM of the caller's environment reach the CLI; every other LBM_* variable is dropped.  Each
 deck's report ends with the kernel that ran and its launches (LBM_DESCRIBE=1).
 
---flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS: several steps per launch where the grid is eligible).
+--flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS, 1024 = LBM64_FLAG_MULTI_STEPS, 1536 = both: several steps per launch where the grid is eligible).
 
 One CLI process per deck, each under a time limit; the first failure ends the script (exit status 1)."""
 import argparse
@@ -34,7 +34,7 @@ def main():
     ap.add_argument("--decks", default=",".join(DECKS))
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per deck")
-    ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS)")
+    ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS, 1024: LBM64_FLAG_MULTI_STEPS, 1536: both)")
     a = ap.parse_args()
     lbm.build()
     with open(os.path.join(GOLDEN, "f64_published.json")) as fh:
@@ -43,7 +43,7 @@ def main():
              "# and the Reynolds line against the number the reference published"]
     ok = True
     for name in a.decks.split(","):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_") or k in ("LBM_TUNE_TILE64_MAX", "LBM_TUNE_TILE64_GEOM")}
+        env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_") or k in ("LBM_TUNE_TILE64_MAX", "LBM_TUNE_TILE64_GEOM", "LBM_TUNE_MULTI64_K", "LBM_TUNE_MULTI64_MIN")}
         env["LBM_PRECISION"] = "double"
         env["LBM_DESCRIBE"] = "1"                      # one line on stderr: the kernel that ran and its launches
         if a.flags:

@@ -23,7 +23,19 @@ shipped decks at full length and on 512 x 512: device time of whole runs, the co
     F=profiles/r08/f64_tile.txt; rm -f $F
     for w in 128x128 128x256 256x256 512x512 1024x1024; do
       timeout -k 10 240 python scripts/measure_f64.py --tile --baseline-lib mpilattice-boltzmann_amd/lib/variants/liblbm_d2q9_parent.so --work $w --out $F || break
-    done"""
+    done
+
+--multi: LBM64_FLAG_MULTI_STEPS (lbm_multi_kernel_f64, K steps per launch of a large grid) with every built K beside the one-step double
+path of the same BASELINE build, and beside LBM64_FLAG_TILE_STEPS where that flag takes the size: device time per step, the contexts
+alternating run by run.  --multi-bits K: on 8192 x 7296, whose planes pass 4 GiB, 2K + 1 steps with the flag and without, populations
+compared for equal bits (host-bound, about 13 GB of host memory); its line goes to the same file.
+
+    F=profiles/r11/f64_multi.txt; rm -f $F; B=mpilattice-boltzmann_amd/lib/variants/liblbm_d2q9_parent.so
+    timeout -k 10 300 python scripts/measure_f64.py --multi --baseline-lib $B --work 8192x8192 --out $F &&
+    timeout -k 10 180 python scripts/measure_f64.py --multi --baseline-lib $B --work 4096x4096 --out $F &&
+    timeout -k 10 120 python scripts/measure_f64.py --multi --baseline-lib $B --work 2048x2048 --out $F &&
+    timeout -k 10 120 python scripts/measure_f64.py --multi --baseline-lib $B --work 1024x1024 --out $F &&
+    timeout -k 10 300 python scripts/measure_f64.py --multi-bits 3 --out $F"""
 import argparse
 import ctypes as C
 import os
@@ -169,15 +181,125 @@ def measure_tile(name, baseline_lib, reps, lines, steps_override=None):
     print("\n".join(lines[-(len(runs) + 2):]), flush=True)
 
 
+MULTI_K = (2, 3, 4)                                          # every K lbm_multi_kernel_f64 is built for
+MULTI_WORK = {"1024x1024": 1200, "2048x2048": 240, "4096x4096": 120, "8192x8192": 60}      # steps per run: multiples of every K
+
+
+def measure_multi(name, baseline_lib, reps, lines, steps_override=None):
+    """LBM64_FLAG_MULTI_STEPS with every built K beside the one-step double kernel of the baseline build (and, where the tiled kernel
+    takes the size, beside LBM64_FLAG_TILE_STEPS): device time per step, the contexts alternating run by run."""
+    p, obst = deck(name)
+    steps = steps_override or MULTI_WORK[name]
+    n0 = len(lines)
+    os.environ["LBM_TUNE_MULTI64_MIN"] = "0"              # read when a context is made: every K on every size
+    base_key = "one-step (baseline build)"
+    runs = {base_key: BaselineGrid64(baseline_lib, p, obst)}
+    if not runs[base_key].describe()["kernel"].startswith("lbm_step_kernel_f64<"):
+        raise SystemExit(f"{name}: the baseline runs {runs[base_key].describe()['kernel']}")
+    for k in MULTI_K:
+        os.environ["LBM_TUNE_MULTI64_K"] = str(k)
+        g = f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS)
+        if not g.describe()["kernel"].startswith(f"lbm_multi_kernel_f64<{k}"):
+            raise SystemExit(f"{name}, K = {k}: the context runs {g.describe()['kernel']}")
+        runs[f"K = {k}"] = g
+    tiled = f64.Grid64(p, obst, flags=f64.FLAG_TILE_STEPS)   # default knobs: the tiled kernel where LBM_TUNE_TILE64_MAX lets it
+    if tiled.describe()["kernel"].startswith("lbm_tile_kernel_f64<"):
+        runs["tiled (flag 512)"] = tiled
+    else:
+        tiled.close()
+    kernels = {k: q.describe()["kernel"] for k, q in runs.items()}
+    first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
+    for k, av in first.items():                            # the same run: av_vels agree to the order of their additions
+        if not np.allclose(av, first[base_key], rtol=1e-12, atol=0.0):
+            raise SystemExit(f"{name}, {k}: av_vels differ from the baseline's by {np.max(np.abs(av - first[base_key]) / first[base_key]):.3e}")
+    us = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, q in runs.items():                          # alternate: all see the same drift of the card
+            q.run(steps)
+            us[k].append(1e3 * q.last_run_kernel_ms()[0] / steps)
+    for q in runs.values():
+        q.close()
+    med = {k: statistics.median(v) for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+    lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; device time of a run's step launches, us per step")
+    for k in runs:
+        lines.append(f"  {k:26s} {kernels[k]:28s} us/step median {med[k]:9.3f}  min {min(us[k]):9.3f}  max {max(us[k]):9.3f}   {144 * p.nx * p.ny / med[k] / 1e6:6.3f} TB/s at 144 B/cell-step")
+    best = min((k for k in runs if k.startswith("K = ")), key=lambda k: med[k])
+    for other in [k for k in runs if not k.startswith("K = ")]:
+        gain, spreads = med[other] - med[best], spread[other] + spread[best]
+        lines.append(f"  fastest {best} against {other}: {med[other] / med[best]:.3f} x; median gain {gain:.3f} us against the two max - min spreads together "
+                     f"{spreads:.3f} us -> {'a win' if gain > spreads else 'no win'}")
+    print("\n".join(lines[n0:]), flush=True)
+
+
+def multi_bits(ks, lines):
+    """8192 x 7296 (the nine planes pass 4 GiB): 2K + 1 steps from tests/test_f64.py's separable state with the flag and without;
+    populations compared by row blocks for equal bits."""
+    nx, ny = 8192, 7296
+    p = lbm.Params(nx=nx, ny=ny, max_iters=2, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85)
+    obst = lbm.synthetic_obstacles(nx, ny, p=0.005, seed=42, walls=True)
+    w0, w1, w2 = p.density * 4.0 / 9.0, p.density / 9.0, p.density / 36.0
+    cells = np.empty((ny, nx, 9), np.float64)
+    cells[:] = np.array([w0] + [w1] * 4 + [w2] * 4)
+    cells *= (1.0 + 0.03 * np.sin(0.013 * np.arange(ny)))[:, None, None]
+    cells *= (1.0 + 0.03 * np.cos(0.007 * np.arange(nx)))[None, :, None]
+    os.environ["LBM_TUNE_MULTI64_MIN"] = "0"
+    for k in ks:
+        os.environ["LBM_TUNE_MULTI64_K"] = str(k)
+        got, kernels = {}, {}
+        for flags in (0, f64.FLAG_MULTI_STEPS):
+            with f64.Grid64(p, obst, flags=flags) as g:
+                kernels[flags] = g.describe()["kernel"]
+                g.set_cells(cells)
+                av = g.run(2 * k + 1)
+                got[flags] = (g.get_cells(), av, g.last_run_kernel_ms()[1])
+        if not kernels[f64.FLAG_MULTI_STEPS].startswith(f"lbm_multi_kernel_f64<{k}") or not kernels[0].startswith("lbm_step_kernel_f64<"):
+            raise SystemExit(f"8192x7296: the contexts run {kernels}")
+        (off, av_off, n_off), (on, av_on, n_on) = got[0], got[f64.FLAG_MULTI_STEPS]
+        bad = [y0 for y0 in range(0, ny, 512) if not np.array_equal(off[y0:y0 + 512].view(np.uint64), on[y0:y0 + 512].view(np.uint64))]
+        lines.append(f"8192x7296  {2 * k + 1} steps from a separable state: {kernels[0]} in {n_off} launches, {kernels[f64.FLAG_MULTI_STEPS]} in {n_on}; "
+                     f"populations by row blocks of 512: {'equal bits in every block' if not bad else f'DIFFERENT in blocks at rows {bad}'}; "
+                     f"av_vels differ by at most {float(np.max(np.abs(av_on - av_off) / av_off)):.2e} relative")
+        print(lines[-1], flush=True)
+        del got, off, on
+        if bad:
+            raise SystemExit("8192x7296: the populations differ")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small step counts (a functional check of this script)")
     ap.add_argument("--work", help="one workload only: 8192, 1024 or 128 (--out appends)")
     ap.add_argument("--out")
     ap.add_argument("--tile", action="store_true", help="LBM64_FLAG_TILE_STEPS in every geometry against --baseline-lib's one-step path; --work: a deck")
+    ap.add_argument("--multi", action="store_true", help="LBM64_FLAG_MULTI_STEPS with every built K against --baseline-lib's one-step path; --work: a size")
+    ap.add_argument("--multi-bits", metavar="K[,K]", help="the 8192 x 7296 bit comparison of lbm_multi_kernel_f64<K> with the one-step kernel (--out appends)")
     ap.add_argument("--baseline-lib", help="liblbm_d2q9.so of the parent commit")
     a = ap.parse_args()
     lbm.build()
+    if a.multi_bits:
+        lines = []
+        multi_bits([int(v) for v in a.multi_bits.split(",")], lines)
+        if a.out:
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
+    if a.multi:
+        if not a.baseline_lib or not os.path.exists(a.baseline_lib):
+            ap.error("--multi needs --baseline-lib, an existing build of the library")
+        sizes = [a.work] if a.work else list(MULTI_WORK)
+        if any(d not in MULTI_WORK for d in sizes):
+            ap.error(f"--work: one of {', '.join(MULTI_WORK)}")
+        lines = [] if a.work and a.out and os.path.exists(a.out) else [
+            "# scripts/measure_f64.py --multi: lbm_multi_kernel_f64 (LBM64_FLAG_MULTI_STEPS), every built K, beside the one-step double path of the parent commit's build",
+            "# device time per step (lbm64_last_run_kernel_ms: events around the step launches of a run, over its steps)"]
+        for d in sizes:
+            measure_multi(d, a.baseline_lib, 3 if a.quick else 5, lines, steps_override=12 if a.quick else None)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a" if a.work else "w") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
     if a.tile:
         if not a.baseline_lib or not os.path.exists(a.baseline_lib):
             ap.error("--tile needs --baseline-lib, an existing build of the library")
