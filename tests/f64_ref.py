@@ -63,6 +63,14 @@ def lib() -> C.CDLL:
         L.f64_ref_init.restype = None
         L.f64_ref_run.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, ip, dp, C.c_int, C.c_int, dp, dp]
         L.f64_ref_run.restype = C.c_int
+        L.f64_ref_run_report.argtypes = L.f64_ref_run.argtypes + [ip, dp]
+        L.f64_ref_run_report.restype = C.c_int
+        L.f64_ref_accel_weights.argtypes = [C.c_double, C.c_double, dp, dp]
+        L.f64_ref_accel_weights.restype = None
+        L.f64_ref_cells.argtypes = [C.c_size_t, dp, ip, ip, C.c_double, C.c_double, C.c_double, dp, dp]
+        L.f64_ref_cells.restype = None
+        L.f64_ref_cells_moments.argtypes = L.f64_ref_cells.argtypes + [dp]
+        L.f64_ref_cells_moments.restype = None
         _lib = L
     return _lib
 
@@ -109,6 +117,57 @@ def run(p, obstacles: np.ndarray, n_steps: int, cells0: np.ndarray | None = None
     if rc != 0:
         raise MemoryError("f64_ref_run")
     return cells, serial[:n_steps], exact[:n_steps]
+
+
+POSITIVE, NAN_TERM, POS_INF_TERM, NEG_INF_TERM = 1, 2, 4, 8        # f64_ref.c's F64_REF_* status bits
+
+
+def run_report(p, obstacles: np.ndarray, n_steps: int, cells0: np.ndarray | None = None, nthreads: int = 8):
+    """run(), and what decides how each step's sum can be compared: cells, exact, status, abs_exact.
+    status (n_steps,) int32: POSITIVE where every free cell had a positive density in that step; NAN_TERM, POS_INF_TERM, NEG_INF_TERM
+    where some term was one.  abs_exact (n_steps,): the exactly rounded sum of the terms' magnitudes."""
+    obstacles = np.ascontiguousarray(obstacles, np.int32)
+    assert obstacles.shape == (p.ny, p.nx)
+    cells = initial_cells(p) if cells0 is None else np.array(cells0, dtype=np.float64, order="C").reshape(p.ny, p.nx, 9)
+    m = max(n_steps, 1)
+    serial, exact, abs_exact, status = np.zeros(m), np.zeros(m), np.zeros(m), np.zeros(m, np.int32)
+    rc = lib().f64_ref_run_report(p.nx, p.ny, p.density, p.accel, p.omega, obstacles.ctypes.data_as(C.POINTER(C.c_int)), _dp(cells), n_steps,
+                                  nthreads, _dp(serial), _dp(exact), status.ctypes.data_as(C.POINTER(C.c_int)), _dp(abs_exact))
+    if rc != 0:
+        raise MemoryError("f64_ref_run_report")
+    return cells, exact[:n_steps], status[:n_steps], abs_exact[:n_steps]
+
+
+def benign(status: np.ndarray) -> np.ndarray:
+    """Steps whose terms are all non-negative numbers: the premise of the summation bounds (tests/test_f64.py sum_bound and its kin)."""
+    return np.asarray(status) == POSITIVE
+
+
+def accel_weights(density: float, accel: float):
+    """(w1, w2): accelerate_flow's axis and diagonal weights as the restatement forms them (d2q9-bgk.c:445-446)."""
+    w1, w2 = C.c_double(0.0), C.c_double(0.0)
+    lib().f64_ref_accel_weights(density, accel, C.byref(w1), C.byref(w2))
+    return w1.value, w2.value
+
+
+def cells_each(pops: np.ndarray, blocked: np.ndarray, accel: np.ndarray, omega: float, w1: float, w2: float, moments: bool = False):
+    """f64_ref_cells: n cells without neighbours.  pops (n, 9) = what streamed in; returns out (n, 9) after bounce-back or relaxation
+    and, where accel is set on a free cell, the next step's accelerate_flow, and term (n,).  With moments=True also mom (n, 2) =
+    {density, squared momentum} as collide() formed them."""
+    pops = np.ascontiguousarray(pops, np.float64)
+    n = pops.shape[0]
+    assert pops.shape == (n, 9)
+    blocked = np.ascontiguousarray(blocked, np.int32)
+    accel = np.ascontiguousarray(accel, np.int32)
+    assert blocked.shape == accel.shape == (n,)
+    out, term = np.empty((n, 9), np.float64), np.empty(n, np.float64)
+    ip = C.POINTER(C.c_int)
+    if moments:
+        mom = np.empty((n, 2), np.float64)
+        lib().f64_ref_cells_moments(n, _dp(pops), blocked.ctypes.data_as(ip), accel.ctypes.data_as(ip), omega, w1, w2, _dp(out), _dp(term), _dp(mom))
+        return out, term, mom
+    lib().f64_ref_cells(n, _dp(pops), blocked.ctypes.data_as(ip), accel.ctypes.data_as(ip), omega, w1, w2, _dp(out), _dp(term))
+    return out, term
 
 
 def free_cells(obstacles: np.ndarray) -> int:

@@ -267,26 +267,44 @@ def test_cli_double_precision(lbm, f64, tmp_path):
     assert r.returncode != 0 and "double precision runs on one GPU" in r.stderr
 
 
-def test_bit_parity_8192x7296_planes_beyond_4_gib(lbm, f64):
-    """8192 x 7296, 2 steps: a plane is 478 MB and the nine planes 4.3 GB, so a 32-bit byte offset anywhere in the step kernel, the
-    copies or the read-outs shows.  Needs about 13 GB of host memory and is host-bound (about 10 s): the one test above a few seconds."""
-    nx, ny = 8192, 7296
-    p = lbm.Params(nx=nx, ny=ny, max_iters=2, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85)
+BIG = (8192, 7296)       # the smallest shape of whole 32 x 16 tiles whose ninth plane lies beyond 4 GiB
+
+
+def big_grid_case(lbm, steps):
+    """The deck and the state of the tests beyond 4 GiB (here and in tests/test_f64_multi.py): 0.5 % obstacles inside walls, and a state
+    that differs from cell to cell, made in place: rest * (1 + a small separable pattern)."""
+    nx, ny = BIG
+    p = lbm.Params(nx=nx, ny=ny, max_iters=steps, reynolds_dim=10, density=0.1, accel=0.005, omega=1.85)
     assert 9 * nx * ny * 8 > 1 << 32
     obst = lbm.synthetic_obstacles(nx, ny, p=0.005, seed=42, walls=True)
-    # a state that differs from cell to cell, made in place: rest * (1 + a small separable pattern)
     cells = f64_ref.initial_cells(p)
     cells *= (1.0 + 0.03 * np.sin(0.013 * np.arange(ny)))[:, None, None]
     cells *= (1.0 + 0.03 * np.cos(0.007 * np.arange(nx)))[None, :, None]
+    return p, obst, cells
+
+
+def big_grid_compare(p, obst, cells, got, steps):
+    """`steps` steps of the restatement on `cells`, IN PLACE, then the bits by row blocks (no whole-grid temporaries).  Returns exact."""
+    exact = np.zeros(steps)
+    rc = f64_ref.lib().f64_ref_run(p.nx, p.ny, p.density, p.accel, p.omega, obst.ctypes.data_as(f64_ref.C.POINTER(f64_ref.C.c_int)), f64_ref._dp(cells),
+                                   steps, 16, None, f64_ref._dp(exact))
+    assert rc == 0
+    for y0 in range(0, p.ny, 512):
+        assert np.array_equal(_bits(got[y0:y0 + 512]), _bits(cells[y0:y0 + 512])), f"rows {y0}..{y0 + 511}"
+    return exact
+
+
+def test_bit_parity_8192x7296_planes_beyond_4_gib(lbm, f64):
+    """8192 x 7296, 2 steps: a plane is 478 MB and the nine planes 4.3 GB, so a 32-bit byte offset anywhere in the step kernel, the
+    copies or the read-outs shows.  Needs about 13 GB of host memory and is host-bound (about 10 s): one of the two tests above a few
+    seconds (the other: tests/test_f64_multi.py, the same grid under the multi-step kernel)."""
+    nx, ny = BIG
+    p, obst, cells = big_grid_case(lbm, 2)
     with f64.Grid64(p, obst) as g:
         desc = g.describe()
         assert desc["state_bytes"] == 2 * 9 * nx * ny * 8 and desc["kernel"] == "lbm_step_kernel_f64<2,nt>"
         g.set_cells(cells)
         av = g.run(2)
         got = g.get_cells()
-    rc = f64_ref.lib().f64_ref_run(nx, ny, p.density, p.accel, p.omega, obst.ctypes.data_as(f64_ref.C.POINTER(f64_ref.C.c_int)), f64_ref._dp(cells), 2, 16,
-                                   None, f64_ref._dp(exact := np.zeros(2)))
-    assert rc == 0
-    for y0 in range(0, ny, 512):           # by row blocks: no whole-grid temporaries
-        assert np.array_equal(_bits(got[y0:y0 + 512]), _bits(cells[y0:y0 + 512])), f"rows {y0}..{y0 + 511}"
+    exact = big_grid_compare(p, obst, cells, got, 2)
     _check_av(av, exact, obst, desc)

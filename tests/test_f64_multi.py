@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import f64_ref
-from test_f64 import U, _bits, _deck, _random_state, _synthetic
+from test_f64 import U, _bits, _deck, _random_state, _synthetic, big_grid_case, big_grid_compare
 from test_f64 import sum_bound as step_sum_bound
 
 pytestmark = pytest.mark.gpu
@@ -268,6 +268,88 @@ def test_read_outs_after_a_multi_step_run(f64, digests, monkeypatch):
     blocks = min(-(-n // 256), 1024)
     exact = f64_ref.velocity_sum_exact(ref_cells, obst)
     assert abs(tot - exact) <= (-(-n // (blocks * 256)) + 9 + blocks) * U * exact       # tests/test_f64.py: lbm64_av_velocity_sum's own tree
+
+
+# ---- the kernel at its own sizes ----------------------------------------------------------------------------------------------------
+
+def _no_knobs(monkeypatch):
+    for k in [k for k in os.environ if k.startswith("LBM_TUNE_")]:
+        monkeypatch.delenv(k)
+
+
+@pytest.mark.parametrize("K", (4, 3))
+@pytest.mark.parametrize("nx,ny", [(1024, 144), (1024, 272)])
+def test_folds_that_take_a_second_stride(lbm, f64, monkeypatch, nx, ny, K):
+    """More tiles than a fold has lanes.  1024 x 144 is 288 tiles: the last fold of a run (lbm64_fold_kernel, 256 lanes) takes a second
+    stride for 32 of its lanes.  1024 x 272 is 544 tiles: the fold block of the next launch (512 lanes) does too, over a ragged
+    remainder of 32, and the last fold takes three.  20 % obstacles, a random state, run(K + 1) then run(2 K): a full launch and a tail,
+    then two full launches; the sums of every launch but the last of each run pass through the fold block, the last through the fold kernel."""
+    p, obst = _synthetic(lbm, nx, ny, seed=nx + ny)
+    tiles = (nx // TX) * (ny // TY)
+    assert tiles > 256 and (ny != 272 or tiles > LANES) and tiles % 256 != 0
+    _force(monkeypatch, K)
+    state = _random_state(p, seed=17)
+    ref_mid, _, exact_mid = f64_ref.run(p, obst, K + 1, cells0=state, nthreads=16)
+    ref_end, _, exact_end = f64_ref.run(p, obst, 2 * K, cells0=ref_mid, nthreads=16)
+    with f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS) as g:
+        desc = g.describe()
+        assert desc["kernel"] == _kernel_name(K) and desc["blocks"] == tiles, desc
+        g.set_cells(state)
+        av_mid = g.run(K + 1)
+        assert g.last_run_kernel_ms()[1] == 2
+        assert np.array_equal(_bits(g.get_cells()), _bits(ref_mid)), f"{nx}x{ny} run({K + 1}): {desc}"
+        av_end = g.run(2 * K)
+        assert g.last_run_kernel_ms()[1] == 2
+        assert np.array_equal(_bits(g.get_cells()), _bits(ref_end)), f"{nx}x{ny} run({K + 1}) + run({2 * K}): {desc}"
+    assert ref_end.min() > 0.0
+    _check_av_multi(np.concatenate([av_mid, av_end]), np.concatenate([exact_mid, exact_end]), obst, K, tiles)
+
+
+def test_default_plan_on_the_1024x1024_deck(f64, digests, monkeypatch):
+    """The flag alone, no knob in the environment: what a user of LBM64_FLAG_MULTI_STEPS gets at the size the default begins at.
+    K = 4 on 2048 tiles, 11 steps (two full launches and a 3-step tail) from a state that differs from cell to cell."""
+    _no_knobs(monkeypatch)
+    p, obst = _deck(f64, digests, "1024x1024_t200")
+    y, x = np.arange(p.ny, dtype=np.float64)[:, None, None], np.arange(p.nx, dtype=np.float64)[None, :, None]
+    state = f64_ref.initial_cells(p)[0, 0][None, None, :] * (1.0 + 0.05 * np.sin(0.37 * x + 0.11 * y) + 0.01 * np.arange(9)[None, None, :])
+    with f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS) as g:
+        desc = g.describe()
+        assert desc["kernel"] in (_kernel_name(4, nt=True), _kernel_name(4)) and desc["blocks"] == (1024 // TX) * (1024 // TY) == 2048, desc
+        g.set_cells(state)
+        av = g.run(11)
+        assert g.last_run_kernel_ms()[1] == 3
+        cells = g.get_cells()
+    ref_cells, _, exact = f64_ref.run(p, obst, 11, cells0=state, nthreads=16)
+    assert np.array_equal(_bits(cells), _bits(ref_cells)), desc
+    assert ref_cells.min() > 0.0
+    _check_av_multi(av, exact, obst, 4, desc["blocks"])
+
+
+def test_bit_parity_8192x7296_planes_beyond_4_gib_with_the_flag(lbm, f64, monkeypatch):
+    """tests/test_f64.py's grid beyond 4 GiB under the multi-step kernel, the flag alone and no knob set: the same state, K + 1 steps (a
+    full launch and a tail), the same comparison by row blocks.  A 32-bit byte offset in the kernel's pulls, its frame or its stores
+    shows in the ninth plane.  116 736 tiles: the bound of the tree is 482 x 2^-53 = 5.4e-14 (the fold kernel's lanes add 456 sums each),
+    so the 64 x 2^-53 cap of the small grids does not apply; a miscounted cell would be 1 / cells = 1.7e-8.
+    Needs about 13 GB of host memory and is host-bound: with tests/test_f64.py's test of this grid one of the two above a few seconds.
+    Measured side by side in one session on an MI355X (profiles/r12/pytest_gpu.log): 3.7 s for this test's 5 steps, 2.9 s for that
+    one's 2; less than twice, so the step count stays K + 1."""
+    _no_knobs(monkeypatch)
+    nx, ny = 8192, 7296
+    p, obst, cells = big_grid_case(lbm, max(BUILT_K) + 1)
+    with f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS) as g:
+        desc = g.describe()
+        assert desc["kernel"].startswith("lbm_multi_kernel_f64<") and desc["state_bytes"] == 2 * 9 * nx * ny * 8, desc
+        K = int(desc["kernel"][len("lbm_multi_kernel_f64<")])
+        assert K in BUILT_K and desc["blocks"] == (nx // TX) * (ny // TY) == 116736
+        g.set_cells(cells)
+        av = g.run(K + 1)
+        assert g.last_run_kernel_ms()[1] == 2
+        got = g.get_cells()
+    exact = big_grid_compare(p, obst, cells, got, K + 1)
+    err, bound = _av_err(av, exact, obst), multi_sum_bound(desc["blocks"])
+    print(f"  av_vels {desc['kernel']} on {desc['blocks']} tiles: {err / U:.2f} x 2^-53 against a bound of {bound / U:.0f} x 2^-53")
+    assert bound < 0.01 / (nx * ny)          # far below one miscounted cell
+    assert err <= bound
 
 
 # ---- the whole 128 x 128 deck ----------------------------------------------------------------------------------------------------

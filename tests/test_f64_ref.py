@@ -78,6 +78,91 @@ def test_thread_count_changes_no_bit(digests):
     assert np.array_equal(cb.view(np.uint64), c1.view(np.uint64)) and np.array_equal(np.concatenate([sa, sb]), s1)
 
 
+DX = (0, 1, 0, -1, 0, 1, -1, -1, 1)
+DY = (0, 0, 1, 0, -1, 1, 1, -1, -1)
+
+
+def _stream(state):
+    """in[y, x, k] = state[y - DY[k], x - DX[k], k], periodic: what streams into each cell."""
+    return np.stack([np.roll(state[..., k], (DY[k], DX[k]), axis=(0, 1)) for k in range(9)], axis=-1)
+
+
+def _unstream(pulled):
+    """The state whose streaming gives `pulled`: state[y - DY[k], x - DX[k], k] = pulled[y, x, k]."""
+    return np.stack([np.roll(pulled[..., k], (-DY[k], -DX[k]), axis=(0, 1)) for k in range(9)], axis=-1)
+
+
+def test_per_cell_entry_is_the_step():
+    """f64_ref_cells (what tests/test_f64_cells.py holds the device function to) is the function f64_ref_run applies to every cell, on a
+    12 x 7 grid with obstacles, some of them on the accelerated row.
+      First step, no acceleration (accel = 0.0 adds 0.0 to positive populations: the same bits): from the state built by inverse streaming
+      of `pulled`, one f64_ref_run step gives f64_ref_cells(pulled) exactly, and serial[0] / exact[0] are the sums of its terms.
+      Second step, accelerated: f64_ref_cells(pulled) with `accel` set on row ny-2 is the state after the first step AND the second step's
+      accelerate_flow; streamed and passed through f64_ref_cells again it must be exactly what one accelerated f64_ref_run step makes of
+      the first step's plain result."""
+    import math
+    nx, ny = 12, 7
+    rng = np.random.default_rng(12)
+    obst = (rng.random((ny, nx)) < 0.2).astype(np.int32)
+    obst[ny - 2, 3] = 1
+    obst[ny - 2, 4:6] = 0
+    p = f64_ref.SimpleNamespace(nx=nx, ny=ny, max_iters=1, reynolds_dim=1, density=0.1, accel=0.005, omega=1.85)
+    w1, w2 = f64_ref.accel_weights(p.density, p.accel)
+    assert (w1, w2) == (0.1 * 0.005 * 0.111111111111111111111111, 0.1 * 0.005 * 0.0277777777777777777777778)
+    pulled = f64_ref.initial_cells(p) * rng.uniform(0.8, 1.2, (ny, nx, 9))
+    pulled[ny - 2, 5] *= 1e-3                  # one free cell of the row too thin for accelerate_flow's condition
+    assert np.array_equal(_stream(_unstream(pulled)), pulled)
+    blocked = obst.reshape(-1)
+    none = np.zeros(nx * ny, np.int32)
+    row = np.zeros((ny, nx), np.int32)
+    row[ny - 2] = 1
+
+    def sums(term):
+        t = term.reshape(ny, nx)
+        parts = []
+        for part in (t[1:ny - 1], t[0:1], t[ny - 1:ny]):        # f64_ref_run's serial[]: rows 1..ny-2, row 0, row ny-1
+            acc = 0.0
+            for v in part.reshape(-1).tolist():
+                acc += v
+            parts.append(acc)
+        return parts[0] + parts[1] + parts[2], math.fsum(term.tolist())
+
+    # first step
+    still = f64_ref.SimpleNamespace(**{**vars(p), "accel": 0.0})
+    plain, term = f64_ref.cells_each(pulled.reshape(-1, 9), blocked, none, p.omega, w1, w2)
+    got, serial, exact = f64_ref.run(still, obst, 1, cells0=_unstream(pulled))
+    assert np.array_equal(got.view(np.uint64).reshape(-1, 9), plain.view(np.uint64))
+    assert np.all(term[blocked != 0] == 0.0) and np.all(term[blocked == 0] > 0.0)
+    assert (serial[0], exact[0]) == sums(term)
+    for k, back in enumerate((0, 3, 4, 1, 2, 7, 8, 5, 6)):
+        assert np.array_equal(plain[blocked != 0, back], pulled.reshape(-1, 9)[blocked != 0, k])
+    # second step
+    pushed, term_pushed, mom = f64_ref.cells_each(pulled.reshape(-1, 9), blocked, row.reshape(-1), p.omega, w1, w2, moments=True)
+    assert np.array_equal(term_pushed, term)
+    changed = np.any(pushed != plain, axis=1).reshape(ny, nx)
+    holds = ((plain[:, 3] - w1 > 0.0) & (plain[:, 6] - w2 > 0.0) & (plain[:, 7] - w2 > 0.0)).reshape(ny, nx)
+    assert np.array_equal(changed, holds & (row != 0) & (obst == 0)) and not changed[ny - 2, 5]
+    assert changed[ny - 2].sum() == (obst[ny - 2] == 0).sum() - 1
+    out, term2 = f64_ref.cells_each(_stream(pushed.reshape(ny, nx, 9)).reshape(-1, 9), blocked, none, p.omega, w1, w2)
+    got, serial, exact = f64_ref.run(p, obst, 1, cells0=plain.reshape(ny, nx, 9))
+    assert np.array_equal(got.view(np.uint64).reshape(-1, 9), out.view(np.uint64))
+    assert (serial[0], exact[0]) == sums(term2)
+    # the moments are collide()'s: the density added left to right from 0.0
+    rho = np.zeros(nx * ny)
+    for k in range(9):
+        rho = rho + pulled.reshape(-1, 9)[:, k]
+    assert np.array_equal(mom[blocked == 0, 0], rho[blocked == 0]) and np.all(mom[blocked != 0] == 0.0)
+    # run_report: this run is one the summation bounds apply to; with every density negative it is not, and the terms' magnitudes sum
+    # to what the terms summed to; a cell of zeros has the term 0 * inf
+    _, exact_r, status, mags = f64_ref.run_report(p, obst, 2, cells0=plain.reshape(ny, nx, 9))
+    assert f64_ref.benign(status).tolist() == [True, True] and exact_r[0] == exact[0] == mags[0]
+    _, exact_n, status, mags_n = f64_ref.run_report(still, obst, 1, cells0=-plain.reshape(ny, nx, 9))
+    assert status.tolist() == [0] and exact_n[0] == -mags_n[0] < 0.0
+    hole = plain.reshape(ny, nx, 9).copy()
+    hole[:] = 0.0
+    assert f64_ref.run_report(still, np.zeros_like(obst), 1, cells0=hole)[2].tolist() == [f64_ref.NAN_TERM]
+
+
 def test_rest_state_and_one_hand_computed_cell():
     """The rest state and one relaxation written out by hand in Python floats (IEEE doubles), operation by operation."""
     p = f64_ref.SimpleNamespace(nx=3, ny=3, max_iters=1, reynolds_dim=1, density=0.1, accel=0.0, omega=1.7)
