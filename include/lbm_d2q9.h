@@ -54,7 +54,9 @@ typedef struct lbm_ctx lbm_ctx;     /* opaque: device state of one partition */
 #define LBM_FLAG_FAST_AVVELS  64u   /* lbm_multi_kernel / lbm_tile_kernel form each cell's sum|u| term (d2q9-bgk.c:667) in float: populations
                                        unchanged bit for bit, av_vels equal to ~1e-7 (an ulp of the float it is); 2-5 % faster */
 #define LBM_FLAG_EXACT_AVVELS 128u  /* lbm_multi_kernel forms the terms in double precision, each correctly rounded (as lbm_step_kernel and
-                                       lbm_tile_kernel always do) instead of as compensated float sums of relative error ~2^-44 (its
+                                       lbm_tile_kernel always do) instead of as compensated float sums of relative error ~2^-44 where
+                                       the cell's squared momentum is at least 2^-104 (below that the error grows to 2^-25 at 2^-126, and
+                                       under 2^-126 the term is an under-estimate between 0 and the exact one: csrc/lbm_geometry.h) (its
                                        default: av_vels, a float, comes out the same; the launch runs at the socket power limit and the
                                        double-precision instructions cost 1-2.5 % of clock) */
 #define LBM_FLAG_FUSED_ARITH 256u   /* the cell update in its FUSED arithmetic: a fixed sequence of correctly rounded fused multiply-adds

@@ -16,7 +16,11 @@ constexpr int kHaloGuard = 4;        // floats of guard on each side of a halo-b
 //   kTermsCompensated (lbm_multi_kernel's default): without double-precision arithmetic.  The root as an unevaluated float
 //     sum s + c (s = msq * rsq(msq); c = the Newton correction of s from the residual msq - s*s, which a fused multiply-add
 //     delivers exactly), the product with rinv as p + lo (p = s * rinv, its rounding error by another fused multiply-add,
-//     plus c * rinv): relative error ~2^-44 per cell where the double form has 2^-53 — av_vels, a float, comes out bit for
+//     plus c * rinv): relative error at most 2^-43.6 + 2^-151 / msq per cell (float denormals kept, as this build keeps them)
+//     where the double form has 2^-53, i.e. ~2^-44 for msq >= 2^-104 and growing to 2^-25 at msq = 2^-126, as the residual
+//     underflows; below 2^-126 the guard on the rsq argument makes the term an under-estimate, between 0 and the double form's
+//     (derivation, per-pair test through this function and measured maxima: tests/test_terms_cells.py, profiles/r13) —
+//     av_vels, a float, comes out bit for
 //     bit the same in every test here — in 7 packed float instructions and two v_rsq_f32 per PAIR.  Only p is widened per
 //     pair; the lo parts are summed per lane in float (a lane adds at most a few per launch) and widened once.  Why it
 //     matters: the launch runs AT the socket power limit (scripts/power_trace.py: 1380 of 1400 W, shader clock 2.2 of

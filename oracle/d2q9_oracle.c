@@ -373,12 +373,96 @@ static void split_rows(int first, int last_excl, int parts, int part, int* a, in
   *b = *a + base + (part < rem ? 1 : 0);
 }
 
+/*
+ * The exactly rounded sum of doubles (this repo's own yardstick, nothing of the reference's): the running sum is kept as a
+ * list of non-overlapping doubles, smallest first, that add up to it EXACTLY; each new term goes through the list by TwoSum
+ * (Knuth), whose two results carry the whole of a sum of two doubles.  At the end the list is added from the largest down; the
+ * first inexact addition is the only rounding, corrected where its discarded half sits exactly on a tie that the rest of the list
+ * decides (Shewchuk's grow-expansion, the algorithm of Python's math.fsum).  Finite terms only, no overflow: what the per-cell
+ * terms are.  Needs ISO arithmetic (no reassociation, no contraction): -std=c99 without -ffast-math, as the Makefile has it.
+ */
+typedef struct exact_acc {
+  double* part;
+  size_t n, cap;
+} exact_acc;
+
+static int exact_add(exact_acc* a, double x)
+{
+  size_t kept = 0;
+  for (size_t j = 0; j < a->n; j++) {
+    double y = a->part[j];
+    if (fabs(x) < fabs(y)) { const double t = x; x = y; y = t; }
+    const double hi = x + y;
+    const double lo = y - (hi - x);                                       /* x + y == hi + lo exactly, |x| >= |y| */
+    if (lo != 0.0) a->part[kept++] = lo;
+    x = hi;
+  }
+  if (kept == a->cap) {
+    const size_t cap = a->cap ? 2 * a->cap : 32;
+    double* grown = (double*)realloc(a->part, cap * sizeof(double));
+    if (!grown) return -1;
+    a->part = grown;
+    a->cap = cap;
+  }
+  a->part[kept++] = x;
+  a->n = kept;
+  return 0;
+}
+
+static double exact_result(const exact_acc* a)
+{
+  size_t n = a->n;
+  double hi = 0.0, lo = 0.0;
+  if (n == 0) return 0.0;
+  hi = a->part[--n];
+  while (n > 0) {
+    const double x = hi, y = a->part[--n];
+    hi = x + y;
+    lo = y - (hi - x);
+    if (lo != 0.0) break;
+  }
+  /* a tie of the one inexact addition, and the parts below it push the same way: round away from hi */
+  if (n > 0 && ((lo < 0.0 && a->part[n - 1] < 0.0) || (lo > 0.0 && a->part[n - 1] > 0.0))) {
+    const double y = lo * 2.0, x = hi + y;
+    if (y == x - hi) hi = x;
+  }
+  return hi;
+}
+
+int oracle_exact_sum(const double* terms, const int* obstacles, size_t n, double* sum)
+{
+  exact_acc a = {NULL, 0, 0};
+  for (size_t c = 0; c < n; c++) {
+    if (obstacles && obstacles[c]) continue;
+    if (exact_add(&a, terms[c])) { free(a.part); return -1; }
+  }
+  *sum = exact_result(&a);
+  free(a.part);
+  return 0;
+}
+
+static int run_impl(const oracle_params* p, const int* obstacles, int free_cells, int n_steps, int nthreads, const float* cells0,
+                    float* cells_out, float* av_vels, double* av_exact, double* sum_exact);
+
 int oracle_run(const oracle_params* p, const int* obstacles, int free_cells, int n_steps,
                int nthreads, float* cells_out, float* av_vels, double* av_exact)
+{
+  return run_impl(p, obstacles, free_cells, n_steps, nthreads, NULL, cells_out, av_vels, av_exact, NULL);
+}
+
+int oracle_run_sums(const oracle_params* p, const int* obstacles, int free_cells, int n_steps, int nthreads,
+                    const float* cells0, float* cells_out, float* av_vels, double* av_exact, double* sum_exact)
+{
+  return run_impl(p, obstacles, free_cells, n_steps, nthreads, cells0, cells_out, av_vels, av_exact, sum_exact);
+}
+
+static int run_impl(const oracle_params* p, const int* obstacles, int free_cells, int n_steps, int nthreads, const float* cells0,
+                    float* cells_out, float* av_vels, double* av_exact, double* sum_exact)
 {
   run_state s;
   if (run_alloc(p, obstacles, free_cells, &s)) return -1;
   const int nx = p->nx, ny = p->ny;
+  if (cells0) memcpy(s.cells + (size_t)nx * Q, cells0, sizeof(float) * (size_t)ny * nx * Q);
   double* terms = (double*)malloc(sizeof(double) * (size_t)(ny + 2) * nx);
   if (!terms) { run_free(&s); return -1; }
   if (nthreads < 1) nthreads = 1;
@@ -422,6 +506,11 @@ int oracle_run(const oracle_params* p, const int* obstacles, int free_cells, int
         tot += rowsum;
       }
       av_exact[tt] = tot * (double)s.free_cells_inv;
+    }
+    if (sum_exact && oracle_exact_sum(terms + nx, s.obst + nx, (size_t)ny * nx, &sum_exact[tt])) {
+      free(terms);
+      run_free(&s);
+      return -1;
     }
 
     float* sw = s.cells;                                                  /* :376-378 */

@@ -79,6 +79,18 @@ void oracle_cell_observables(const oracle_params* p, const float* cell, int obst
 int oracle_run(const oracle_params* p, const int* obstacles, int free_cells, int n_steps,
                int nthreads, float* cells_out, float* av_vels, double* av_exact);
 
+/* The exactly rounded sum of terms[c] over the n entries with obstacles[c] == 0 (obstacles == NULL: over all of them): the one
+ * double nearest to the true sum, whatever the order — what math.fsum returns.  Finite terms.  Returns 0, or -1 out of memory. */
+int oracle_exact_sum(const double* terms, const int* obstacles, size_t n, double* sum);
+
+/* oracle_run with two more arguments:
+ *   cells0    : optional, ny*nx*9 floats: the state the run starts from instead of the rest equilibrium
+ *   sum_exact : optional, n_steps doubles: per step the exactly rounded sum over the free cells of the per-cell double terms
+ *               (the terms av_exact adds row by row), NOT multiplied by free_cells_inv — the yardstick the device's
+ *               per-step double sums are held to */
+int oracle_run_sums(const oracle_params* p, const int* obstacles, int free_cells, int n_steps, int nthreads,
+                    const float* cells0, float* cells_out, float* av_vels, double* av_exact, double* sum_exact);
+
 /* Same loop, but without per-cell term storage and with a per-thread float accumulator: this is
  * the form timed as the CPU baseline (row-parallel, as BASELINE.md §4).  av_vels differ from
  * oracle_run's only in summation order when nthreads > 1; cells_out is identical. */

@@ -123,6 +123,21 @@ void fused_ref_init(int nx, int ny, float density, float* cells)
   }
 }
 
+/* msq and rinv of n cells given by their nine streamed-in populations t[c * 9 + k], as relax_exact (mode 0) or relax_fused
+ * (mode 1) form them: what the velocity term of a cell is made of (tests/terms_ref.py). */
+void fused_ref_cells(size_t n, const float* t, float omega, int mode, float* msq, float* rinv)
+{
+  for (size_t c = 0; c < n; c++) {
+    cell_result r;
+    if (mode) relax_fused(t + c * NDIR, omega, &r); else relax_exact(t + c * NDIR, omega, &r);
+    msq[c] = r.msq;
+    rinv[c] = r.rinv;
+  }
+}
+
+static int run_impl(int nx, int ny, float density, float accel, float omega, const int* blocked, float* cells, int n_steps,
+                    int mode, int nthreads, double* sums, double* terms);
+
 /*
  * n_steps steps in place on `cells`.  Each step: acceleration of row ny - 2, then for every cell the pull from its
  * eight neighbours, rebound (blocked cells) or relaxation (the others), and the velocity term
@@ -132,6 +147,19 @@ void fused_ref_init(int nx, int ny, float density, float* cells)
  */
 int fused_ref_run(int nx, int ny, float density, float accel, float omega, const int* blocked, float* cells, int n_steps,
                   int mode, int nthreads, double* sums)
+{
+  return run_impl(nx, ny, density, accel, omega, blocked, cells, n_steps, mode, nthreads, sums, NULL);
+}
+
+/* ONE step of fused_ref_run that also hands out the velocity term of every cell: terms[y * nx + x], 0 at blocked cells. */
+int fused_ref_step_terms(int nx, int ny, float density, float accel, float omega, const int* blocked, float* cells,
+                         int mode, int nthreads, double* sum, double* terms)
+{
+  return run_impl(nx, ny, density, accel, omega, blocked, cells, 1, mode, nthreads, sum, terms);
+}
+
+static int run_impl(int nx, int ny, float density, float accel, float omega, const int* blocked, float* cells, int n_steps,
+                    int mode, int nthreads, double* sums, double* terms)
 {
   static const int reverse[NDIR] = {0, 3, 4, 1, 2, 7, 8, 5, 6};
   /* where direction k of a cell comes from: the neighbour at (x - dx[k], y - dy[k]) */
@@ -159,11 +187,14 @@ int fused_ref_run(int nx, int ny, float density, float accel, float omega, const
         float* out = next + ((size_t)y * nx + x) * NDIR;
         if (blocked[(size_t)y * nx + x]) {
           for (int k = 0; k < NDIR; k++) out[reverse[k]] = t[k];
+          if (terms) terms[(size_t)y * nx + x] = 0.0;
         } else {
           cell_result r;
           if (mode) relax_fused(t, omega, &r); else relax_exact(t, omega, &r);
           memcpy(out, r.f, sizeof r.f);
-          row_total += sqrt((double)r.msq) * (double)r.rinv;
+          const double term = sqrt((double)r.msq) * (double)r.rinv;
+          row_total += term;
+          if (terms) terms[(size_t)y * nx + x] = term;
         }
       }
       row_totals[y] = row_total;

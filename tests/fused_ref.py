@@ -62,6 +62,10 @@ def lib() -> C.CDLL:
         L.fused_ref_init.restype = None
         L.fused_ref_run.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, ip, fp, C.c_int, C.c_int, C.c_int, dp]
         L.fused_ref_run.restype = C.c_int
+        L.fused_ref_cells.argtypes = [C.c_size_t, fp, C.c_float, C.c_int, fp, fp]
+        L.fused_ref_cells.restype = None
+        L.fused_ref_step_terms.argtypes = [C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, ip, fp, C.c_int, C.c_int, dp, dp]
+        L.fused_ref_step_terms.restype = C.c_int
         _lib = L
     return _lib
 
@@ -86,6 +90,32 @@ def run(p, obstacles: np.ndarray, n_steps: int, mode: str = "fused", cells0: np.
     if rc != 0:
         raise MemoryError("fused_ref_run")
     return cells, sums[:n_steps]
+
+
+def cells_msq_rinv(t: np.ndarray, mode: str = "fused", omega: float = 1.0):
+    """msq and rinv (float32) of cells given by their nine streamed-in populations, t of shape (..., 9): relax_exact / relax_fused."""
+    t = np.ascontiguousarray(t, np.float32)
+    assert t.shape[-1] == 9
+    msq = np.empty(t.shape[:-1], np.float32)
+    rinv = np.empty(t.shape[:-1], np.float32)
+    fp = C.POINTER(C.c_float)
+    lib().fused_ref_cells(msq.size, t.ctypes.data_as(fp), omega, MODES[mode], msq.ctypes.data_as(fp), rinv.ctypes.data_as(fp))
+    return msq, rinv
+
+
+def step_terms(p, obstacles: np.ndarray, cells: np.ndarray, mode: str = "fused", nthreads: int = 4):
+    """One step from `cells`.  Returns the new cells, the step's sum as fused_ref_run adds it, and the (ny, nx) velocity terms of the
+    step (0 at blocked cells)."""
+    obstacles = np.ascontiguousarray(obstacles, np.int32)
+    cells = np.array(cells, dtype=np.float32, order="C").reshape(p.ny, p.nx, 9)
+    total = np.zeros(1, np.float64)
+    terms = np.zeros((p.ny, p.nx), np.float64)
+    rc = lib().fused_ref_step_terms(p.nx, p.ny, p.density, p.accel, p.omega, obstacles.ctypes.data_as(C.POINTER(C.c_int)),
+                                    cells.ctypes.data_as(C.POINTER(C.c_float)), MODES[mode], nthreads,
+                                    total.ctypes.data_as(C.POINTER(C.c_double)), terms.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc != 0:
+        raise MemoryError("fused_ref_step_terms")
+    return cells, float(total[0]), terms
 
 
 def free_cells_inv(obstacles: np.ndarray) -> np.float32:

@@ -57,6 +57,8 @@ def lib() -> C.CDLL:
         L.oracle_reynolds.restype = C.c_float
         L.oracle_run.argtypes = [pp, ip, C.c_int, C.c_int, C.c_int, fp, fp, dp]
         L.oracle_run_fast.argtypes = [pp, ip, C.c_int, C.c_int, C.c_int, fp, fp]
+        L.oracle_exact_sum.argtypes = [dp, ip, C.c_size_t, dp]
+        L.oracle_run_sums.argtypes = [pp, ip, C.c_int, C.c_int, C.c_int, fp, fp, fp, dp, dp]
         L.oracle_write_final_state.argtypes = [C.c_char_p, pp, fp, ip, C.c_int, C.c_int, C.c_int]
         L.oracle_write_av_vels.argtypes = [C.c_char_p, fp, C.c_int]
         _lib = L
@@ -115,6 +117,37 @@ def run(p, obstacles: np.ndarray, n_steps: int, nthreads: int = 1, exact: bool =
     rc = lib().oracle_run(C.byref(cp), _i(obstacles), free, n_steps, nthreads, _f(cells), _f(av), _d(ex) if exact else None)
     assert rc == 0
     return cells, av[:n_steps], (ex[:n_steps] if exact else None)
+
+
+def exact_sum(terms: np.ndarray, obstacles: np.ndarray | None = None) -> float:
+    """The exactly rounded sum of the terms of the free cells (of every term without an obstacle map): oracle_exact_sum."""
+    terms = np.ascontiguousarray(terms, np.float64)
+    out = C.c_double(0.0)
+    if obstacles is not None:
+        obstacles = np.ascontiguousarray(obstacles, np.int32)
+        assert obstacles.size == terms.size
+    assert lib().oracle_exact_sum(_d(terms), _i(obstacles) if obstacles is not None else None, terms.size, C.byref(out)) == 0
+    return out.value
+
+
+def run_sums(p, obstacles: np.ndarray, n_steps: int, cells0: np.ndarray | None = None, nthreads: int = 1):
+    """oracle_run_sums: the whole run from the rest state of the deck, or from cells0 (ny, nx, 9).  Returns cells, av_exact (as `run`)
+    and sum_exact: per step the exactly rounded sum of the free cells' double terms, not divided by the number of free cells."""
+    cp = cparams(p)
+    obstacles = np.ascontiguousarray(obstacles, np.int32)
+    free = int(obstacles.size - np.count_nonzero(obstacles))
+    cells = np.empty((p.ny, p.nx, Q), np.float32)
+    av = np.zeros(max(n_steps, 1), np.float32)
+    ex = np.zeros(max(n_steps, 1), np.float64)
+    sm = np.zeros(max(n_steps, 1), np.float64)
+    start = None
+    if cells0 is not None:
+        start = np.ascontiguousarray(cells0, np.float32)
+        assert start.shape == (p.ny, p.nx, Q)
+    rc = lib().oracle_run_sums(C.byref(cp), _i(obstacles), free, n_steps, nthreads, _f(start) if start is not None else None,
+                               _f(cells), _f(av), _d(ex), _d(sm))
+    assert rc == 0
+    return cells, ex[:n_steps], sm[:n_steps]
 
 
 def run_fast(p, obstacles: np.ndarray, n_steps: int, nthreads: int = 1):
@@ -214,9 +247,10 @@ class OraclePartition:
         return self.cells[1:-1].copy()
 
 
-def run_from(p, obstacles: np.ndarray, cells0: np.ndarray, n_steps: int):
+def run_from(p, obstacles: np.ndarray, cells0: np.ndarray, n_steps: int, sums: bool = False, keep_terms: bool = False):
     """d2q9-bgk.c:315-394 for one rank starting from an arbitrary state (small grids: Python loop
-    over steps, C restatement for the rows).  Returns cells, av_exact (float64 per step)."""
+    over steps, C restatement for the rows).  Returns cells, av_exact (float64 per step); with sums=True also the per-step exactly
+    rounded sums of the free cells' terms (oracle_exact_sum), and with keep_terms=True the per-step (ny, nx) term arrays as well."""
     cp = cparams(p)
     ny, nx = p.ny, p.nx
     free = int(obstacles.size - np.count_nonzero(obstacles))
@@ -227,12 +261,21 @@ def run_from(p, obstacles: np.ndarray, cells0: np.ndarray, n_steps: int):
     obst = np.zeros((ny + 2, nx), np.int32)
     obst[1:-1] = obstacles
     terms = np.zeros((ny + 2, nx), np.float64)
-    out = []
+    out, exact, kept = [], [], []
     for _ in range(n_steps):
         cells[ny + 1] = cells[1]          # self exchange (:245-247, :295-303)
         cells[0] = cells[ny]
         lib().oracle_accelerate_row(C.byref(cp), _f(cells[ny - 1]), _i(obst[ny - 1]))
         lib().oracle_timestep_rows(C.byref(cp), _f(cells), _f(tmp), _i(obst), 1, ny + 1, _d(terms))
         out.append(terms[1:-1].sum(axis=1).sum() * np.float64(inv))
+        if sums:
+            exact.append(exact_sum(terms[1:-1], obst[1:-1]))
+        if keep_terms:
+            kept.append(terms[1:-1].copy())
         cells, tmp = tmp, cells
-    return cells[1:-1].copy(), np.asarray(out)
+    result = (cells[1:-1].copy(), np.asarray(out))
+    if sums:
+        result += (np.asarray(exact, np.float64),)
+    if keep_terms:
+        result += (kept,)
+    return result
