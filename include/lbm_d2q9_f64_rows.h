@@ -1,0 +1,99 @@
+/*
+ * lbm_d2q9_f64_rows.h — C ABI of ROW-PARTITIONED runs of the double-precision mode (liblbm_d2q9.so, csrc/lbm_rows64.hip): the
+ * reference's row decomposition with a halo exchange (d2q9-bgk.c:244-251, 295-313, 326-328, 364, 834-862) over one or several GPUs of
+ * one process, in the arithmetic lbm_d2q9_f64.h states.  Opt-in, under names of its own: nothing of lbm_d2q9_f64.h changes with it.
+ *
+ * One object, lbm_rows64, is the whole run; one host thread drives it.  The rows are dealt to `nranks` ranks by lbm_decompose (the
+ * reference's rule, :834-862); rank r keeps its rows on the device it was given — ranks may share a device — as two grids of
+ * ny_local + 2 storage rows: a ghost row below the owned rows and one above.  A step of a rank is one launch of
+ * lbm_rows_kernel_f64<CELLS, NT> (csrc/kernels/rows64.h), the partition form of lbm_step_kernel_f64: the same lane forms (an x-pair per
+ * lane where nx is even, else a cell), the same cell update, the same chunks of 256 units per block — over rows that do not wrap:
+ * the rows above and below an edge row are the ghost rows.  After its step kernel a rank runs lbm64_push_rows_kernel, which stores
+ * the three populations that cross each cut into the neighbours' ghost rows of the grid just written: populations 4, 7, 8 of its
+ * first owned row into the ghost row above the rank below, populations 2, 5, 6 of its last owned row into the ghost row below the rank
+ * above (the ring is periodic; with one rank the rank is its own neighbour, with two both neighbours are the other rank; a rank of
+ * one row sends that row both ways).  Between devices these are plain vector stores into the peer's memory (peer access, xGMI).  The
+ * other six planes of a ghost row are never read and never written.
+ *
+ * ORDER.  Everything is ordered by stream events at kernel boundaries: no kernel waits for another one, there is no flag, no spin
+ * and no time-out on the device.  Per step t, in rank order, the host enqueues on the rank's stream: a wait for both neighbours'
+ * push events of step t-1, the step kernel, the push, the record of this rank's push event of step t.  The price is a serial chain
+ * kernel -> push -> neighbour's kernel per step: next to a rank kernel of hundreds of microseconds it is small, on a tiny grid it
+ * is most of the step (DESIGN.md section 5 has the measured figures): this mode is for grids too large or too slow for one GPU.
+ *
+ * WHAT IS COMPUTED.  The populations are the bits lbm64_run gives on the whole grid, for EVERY rank count.  av_vels[t] is the sum
+ * over the ranks, in rank order on the host, of each rank's sum of step t, times 1.0 / free_cells.  A rank's sum is formed as
+ * lbm_d2q9_f64.h describes for lbm_step_kernel_f64 (per-lane sums, a fixed tree per block, block 0 of the next launch folds the
+ * blocks' sums); adding the ranks' sums is one more serial level of that tree, nranks - 1 additions.  No atomics: the same state and
+ * the same rank count give the same bits in every run.
+ *
+ * Conventions are those of lbm_d2q9.h: 0 on success, otherwise lbm_last_error() has the message for the calling thread; cells cross
+ * the boundary as AoS, 9 doubles per cell of the WHOLE grid, row-major, x fastest; obstacles as the reference's int map of the whole
+ * grid.  The host half of lbm_d2q9_f64.h (lbm64_read_params, lbm64_av_velocity_obs, lbm64_reynolds, the writers) serves these runs as
+ * it is.
+ *
+ * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; several steps per exchange
+ * (LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused); overlap of a rank's interior rows with the exchange.
+ */
+#ifndef LBM_D2Q9_F64_ROWS_H
+#define LBM_D2Q9_F64_ROWS_H
+
+#include <stddef.h>
+
+#include "lbm_d2q9_f64.h"           /* lbm64_params, LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES, lbm_last_error */
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define LBM_ROWS64_ABI_VERSION 1
+#define LBM_ROWS64_MAX_RANKS 64     /* MPI_PROCS, d2q9-bgk.c:67 */
+
+typedef struct lbm_rows64 lbm_rows64;   /* opaque: the device state of every rank of one run */
+
+int lbm_rows64_abi_version(void);
+
+/* A whole periodic nx x ny grid (ny >= 3) in the initial state of d2q9-bgk.c:880-902, its rows dealt to `nranks` ranks.
+ * obstacles_all = ny*nx ints, the whole grid's map.  devices = nranks HIP ordinals, or NULL: rank r on device r % (device count).
+ * Ranks may share a device.  flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default
+ * once a RANK's two grids exceed the Infinity Cache).
+ * Refused, with a message and before the first HIP call: nranks outside 1..LBM_ROWS64_MAX_RANKS; a decomposition that leaves a rank
+ * without a row, or the last rank fewer than 3 (d2q9-bgk.c:848-849; ny = 5 on 3 ranks is 2, 1, 2); the shapes lbm64_create refuses;
+ * free_cells < 1; any other flag — LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS among them: several steps per exchange are not
+ * built.  Refused after it: two ranks on distinct devices that hipDeviceCanAccessPeer denies. */
+int lbm_rows64_create(lbm_rows64** run, const lbm64_params* params, int free_cells, const int* obstacles_all, int nranks,
+                      const int* devices, unsigned flags);
+int lbm_rows64_destroy(lbm_rows64* run);
+
+/* n_steps iterations of d2q9-bgk.c:315-394 on every rank; av_vels[t] (may be NULL) as described above.  May be called repeatedly; the
+ * state it leaves is the post-step state, NOT yet accelerated for a next step, exactly as lbm64_run.  Returns when every rank is
+ * idle. */
+int lbm_rows64_run(lbm_rows64* run, int n_steps, double* av_vels);
+
+/* The state of the whole grid, AoS: ny*nx*9 doubles, gathered from / scattered to the ranks' owned rows in chunks of rows.  Bits
+ * travel unchanged both ways (NaN payloads, signed zeros, denormals). */
+int lbm_rows64_get_cells(lbm_rows64* run, double* cells_aos);
+int lbm_rows64_set_cells(lbm_rows64* run, const double* cells_aos);
+
+/* {u_x, u_y, u, pressure} per cell of the whole grid as lbm64_get_observables gives them: ny*nx*4 doubles. */
+int lbm_rows64_get_observables(lbm_rows64* run, double* obs);
+
+/* av_velocity()'s sum over the free cells (d2q9-bgk.c:716-751) of the current state: each rank sums its rows as
+ * lbm64_av_velocity_sum does (per lane, per block), the host adds the blocks' sums, rank after rank. */
+int lbm_rows64_av_velocity_sum(lbm_rows64* run, double* tot_u);
+
+/* Device time of the last lbm_rows64_run: events around each rank's step and push launches, the largest span over the ranks; and
+ * the number of step launches of the run (n_steps * nranks). */
+int lbm_rows64_last_run_ms(lbm_rows64* run, double* ms, int* launches);
+
+/* What a step looks like: the kernel's name ("lbm_rows_kernel_f64<2>", "lbm_rows_kernel_f64<1>", or with non-temporal stores
+ * "lbm_rows_kernel_f64<2,nt>"), the rank count, and of the rank with the most work blocks: those blocks (one more block folds the
+ * previous step's sums) and the cells a block advances; the bytes of all ranks' grids, ghost rows included. */
+int lbm_rows64_describe(const lbm_rows64* run, char* kernel_name, size_t len, int* nranks, long long* blocks, long long* cells_per_block,
+                        long long* state_bytes);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* LBM_D2Q9_F64_ROWS_H */

@@ -19,6 +19,11 @@
  * a small grid advances several steps per launch, the same populations and files) and 1024 (LBM64_FLAG_MULTI_STEPS: the same for a
  * large grid that 32 x 16 tiles cover, with lbm_multi_kernel_f64), in any sum, and has no other default.  LBM_DESCRIBE=1 adds one
  * line on stderr: the kernel that advanced the grid (lbm64_describe) and the step launches of the run.
+ * LBM_PRECISION=double LBM64_RANKS=N (N >= 1) runs the same deck as N row blocks (include/lbm_d2q9_f64_rows.h): the rows are
+ * partitioned by the reference's rule, rank r lives on device LBM_DEVICES[r] (a comma list; default r % device count; ranks may share
+ * a device), one host thread drives all of them and the edge rows travel as peer-to-peer stores ordered by stream events.  The same
+ * five lines and two files; final_state.dat is the same bytes for every N.  Of LBM_FLAGS it takes 0, 1 and 2 only.  LBM64_RANKS
+ * without LBM_PRECISION=double is refused.
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
  * the reference's rule (d2q9-bgk.c:834-862), rank r lives on device LBM_DEVICES[r] (a comma list; default r), one host
@@ -39,6 +44,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_d2q9_f64.h"
+#include "lbm_d2q9_f64_rows.h"
 #include "lbm_d2q9_p2p.h"
 
 static void die(const char* message, const int line, const char* file)   /* d2q9-bgk.c:1145-1151 */
@@ -94,11 +100,15 @@ static void* rank_main(void* arg)
   return NULL;
 }
 
-/* LBM_PRECISION=double: main() below with lbm64_* in place of lbm_* and doubles in place of floats. */
+/* LBM_PRECISION=double: main() below with lbm64_* in place of lbm_* and doubles in place of floats; with LBM64_RANKS=N, with
+ * lbm_rows64_* (N row blocks) in place of lbm64_*. */
 static int main_double(char* argv[])
 {
   lbm64_params params;
   lbm64_ctx* ctx = NULL;
+  lbm_rows64* rows = NULL;
+  const char* ranks_text = getenv("LBM64_RANKS");
+  const int nranks = (ranks_text && *ranks_text) ? atoi(ranks_text) : 0;      /* 0: one context, lbm64_* */
   int* obstacles;
   int free_cells = 0;
   double* av_vels;
@@ -108,6 +118,7 @@ static int main_double(char* argv[])
   size_t nx;
 
   if (env_int("LBM_GPUS", 1) > 1) die("LBM_PRECISION=double: double precision runs on one GPU (unset LBM_GPUS)", __LINE__, __FILE__);
+  if (ranks_text && *ranks_text && (nranks < 1 || nranks > LBM_ROWS64_MAX_RANKS)) die("LBM64_RANKS: expected 1 to 64 ranks (MPI_PROCS, d2q9-bgk.c:67)", __LINE__, __FILE__);
   if (lbm64_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);
   if (params.nx <= 0 || params.ny <= 0 || params.max_iters < 0) die("could not read param file: nx", __LINE__, __FILE__);
   nx = (size_t)params.nx;
@@ -116,21 +127,56 @@ static int main_double(char* argv[])
   av_vels = (double*)xmalloc(sizeof(double) * ((size_t)params.max_iters + 1));
   obs = (double*)xmalloc(sizeof(double) * nx * (size_t)params.ny * 4);
 
-  if (lbm64_create(&ctx, &params, free_cells, obstacles, env_int("LBM_DEVICE", 0), (unsigned)env_int("LBM_FLAGS", 0)))
-    die(lbm_last_error(), __LINE__, __FILE__);
-  tic = wall_seconds();                                                    /* :278-279 */
-  if (lbm64_run(ctx, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
-  toc = wall_seconds();                                                    /* :397-398 */
-  if (lbm64_get_observables(ctx, obs)) die(lbm_last_error(), __LINE__, __FILE__);
-  if (env_int("LBM_DESCRIBE", 0)) {
-    char kernel[128];
-    double ms = 0.0;
-    int launches = 0;
-    if (lbm64_describe(ctx, kernel, sizeof kernel, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
-    if (params.max_iters > 0 && lbm64_last_run_kernel_ms(ctx, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
-    fprintf(stderr, "kernel: %s, %d launches\n", kernel, launches);
+  if (nranks > 0) {
+    /* ---- N row blocks of the reference's decomposition in one lbm_rows64, one host thread ------------------------------------ */
+    const int flags = env_int("LBM_FLAGS", 0);
+    const char* list = getenv("LBM_DEVICES");
+    int* device = NULL;
+    int r;
+    if (flags < 0 || flags > 2) die("LBM_FLAGS: with LBM64_RANKS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES)", __LINE__, __FILE__);
+    if (list && *list) {
+      device = (int*)xmalloc(sizeof(int) * (size_t)nranks);
+      for (r = 0; r < nranks; ++r) {
+        device[r] = r;
+        if (list && *list) {
+          device[r] = atoi(list);
+          list = strchr(list, ',');
+          if (list) ++list;
+        }
+      }
+    }
+    if (lbm_rows64_create(&rows, &params, free_cells, obstacles, nranks, device, (unsigned)flags)) die(lbm_last_error(), __LINE__, __FILE__);
+    free(device);
+    tic = wall_seconds();                                                  /* :278-279 */
+    if (lbm_rows64_run(rows, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
+    toc = wall_seconds();                                                  /* :397-398 */
+    if (lbm_rows64_get_observables(rows, obs)) die(lbm_last_error(), __LINE__, __FILE__);   /* rank order, as the ranks append (:1049-1057) */
+    if (env_int("LBM_DESCRIBE", 0)) {
+      char kernel[128];
+      double ms = 0.0;
+      int launches = 0;
+      if (lbm_rows64_describe(rows, kernel, sizeof kernel, NULL, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
+      if (params.max_iters > 0 && lbm_rows64_last_run_ms(rows, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "kernel: %s on %d ranks, %d launches\n", kernel, nranks, launches);
+    }
+    lbm_rows64_destroy(rows);
+  } else {
+    if (lbm64_create(&ctx, &params, free_cells, obstacles, env_int("LBM_DEVICE", 0), (unsigned)env_int("LBM_FLAGS", 0)))
+      die(lbm_last_error(), __LINE__, __FILE__);
+    tic = wall_seconds();                                                  /* :278-279 */
+    if (lbm64_run(ctx, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
+    toc = wall_seconds();                                                  /* :397-398 */
+    if (lbm64_get_observables(ctx, obs)) die(lbm_last_error(), __LINE__, __FILE__);
+    if (env_int("LBM_DESCRIBE", 0)) {
+      char kernel[128];
+      double ms = 0.0;
+      int launches = 0;
+      if (lbm64_describe(ctx, kernel, sizeof kernel, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
+      if (params.max_iters > 0 && lbm64_last_run_kernel_ms(ctx, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "kernel: %s, %d launches\n", kernel, launches);
+    }
+    lbm64_destroy(ctx);
   }
-  lbm64_destroy(ctx);
   getrusage(RUSAGE_SELF, &ru);                                             /* :399-403 */
   usrtim = ru.ru_utime.tv_sec + ru.ru_utime.tv_usec / 1000000.0;
   systim = ru.ru_stime.tv_sec + ru.ru_stime.tv_usec / 1000000.0;
@@ -142,7 +188,8 @@ static int main_double(char* argv[])
   printf("Elapsed user CPU time:\t\t%.6lf (s)\n", usrtim);
   printf("Elapsed system CPU time:\t%.6lf (s)\n", systim);
   mlups = (double)params.nx * params.ny * params.max_iters / (toc - tic) / 1e6;
-  printf("MLUPS:\t\t\t\t%.1f (1 GPU, double precision)\n", mlups);
+  if (nranks > 0) printf("MLUPS:\t\t\t\t%.1f (%d ranks, double precision)\n", mlups, nranks);
+  else printf("MLUPS:\t\t\t\t%.1f (1 GPU, double precision)\n", mlups);
   printf("HBM roofline (144 B/cell-step @ 8.0 TB/s = 55556 MLUPS per GPU):\t%.1f %%\n", 100.0 * mlups / (8.0e12 / 144.0 / 1e6));
 
   if (!env_int("LBM_NO_OUTPUT", 0)) {                                      /* :419-421 */
@@ -172,6 +219,7 @@ int main(int argc, char* argv[])
     const char* precision = getenv("LBM_PRECISION");
     if (precision && strcmp(precision, "double") == 0) return main_double(argv);
     if (precision && *precision && strcmp(precision, "float") != 0) die("LBM_PRECISION: expected float or double", __LINE__, __FILE__);
+    if (getenv("LBM64_RANKS") && *getenv("LBM64_RANKS")) die("LBM64_RANKS: row blocks in double precision need LBM_PRECISION=double", __LINE__, __FILE__);
   }
 
   if (lbm_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);

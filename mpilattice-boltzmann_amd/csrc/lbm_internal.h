@@ -1,4 +1,4 @@
-// lbm_internal.h — shared between the host-only (lbm_host.cpp, lbm_plan.cpp) and device (lbm_kernels.hip, lbm_f64.hip)
+// lbm_internal.h — shared between the host-only (lbm_host.cpp, lbm_plan.cpp) and device (lbm_kernels.hip, lbm_f64.hip, lbm_rows64.hip)
 // units of liblbm_d2q9.so.  Not part of the ABI.
 #pragma once
 #include <cstddef>
@@ -113,6 +113,33 @@ int plan64_multi_next_steps(const PlanMulti64& plan, int left);
 // The flags lbm64_create takes: a store form, LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS.
 constexpr unsigned kFlags64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS;
 
+// One rank of a row-partitioned double-precision run (include/lbm_d2q9_f64_rows.h; lbm_rows64.hip allocates and launches by it): the
+// rows lbm_decompose gives the rank, the one-step launch over them by plan64_whole's rules, and the sizes of its two grids of
+// ny_local + 2 storage rows (one ghost row below, one above).  Plain data in this order — tests/test_f64_rows_host.py mirrors it field
+// for field and refuses a library whose lbm_plan64_rows_sizeof() differs.  Beside Plan64 and PlanMulti64, whose layouts do not change.
+struct PlanRows64 {
+  unsigned flags;                    // as lbm_rows64_create took them
+  int nranks, rank;
+  int y0, ny_local;                  // first owned row of the grid, owned rows (d2q9-bgk.c:834-862)
+  // lbm_rows_kernel_f64: non-temporal stores (the rule of plan64_whole on the RANK's two grids); cells per lane (2: x-pairs, nx even; 1);
+  // pairs or cells of the owned rows; 256-unit chunks per block; work blocks of a launch
+  int nt_stores, lane_cells;
+  unsigned units;
+  int iters, blocks;
+  int partials_cap;                  // doubles of each partials buffer: blocks + 1
+  int mask_words;                    // words of the obstacle bitfield of the owned rows
+  int accel_rank, accel_row;         // of the whole run: the rank that owns row ny-2 of the grid, and that row's index among its owned rows
+  long long ps, grid_doubles;        // plane stride of (ny_local + 2) * nx cells; one grid's allocation, in doubles
+};
+static_assert(sizeof(PlanRows64) == 14 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
+constexpr int kMaxRows64Ranks = 64;  // MPI_PROCS, d2q9-bgk.c:67
+// The flags lbm_rows64_create takes: a store form.
+constexpr unsigned kFlagsRows64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES;
+// Fills *out for rank `rank` of `nranks`; checks every argument itself.  0, or 1 and the message in lbm_last_error(): nranks outside
+// 1..64, a rank without a row, a last rank with fewer than 3 rows, the shapes lbm64_create refuses, any flag outside kFlagsRows64.
+int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanRows64* out);
+void plan64_rows_kernel_name(const PlanRows64& plan, char* kernel_name, size_t len);
+
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
 // up to at most the ghost rows, group_max at most.  Launch i of a group advances, besides the owned rows, ext(i) = the steps of the
@@ -192,3 +219,8 @@ extern "C" int lbm_plan64_multi_sizeof(void);
 extern "C" int lbm_plan64_multi(const lbm64_params* p, unsigned flags, lbm_internal::PlanMulti64* out);
 extern "C" int lbm_plan64_multi_kernel_name(const lbm_internal::PlanMulti64* plan, char* kernel_name, size_t len);
 extern "C" int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* plan, int n_steps, int* steps, int* full, int cap);
+// And for a row-partitioned run: the PlanRows64 rank `rank` of `nranks` would get (0, or 1 where lbm_rows64_create refuses the
+// arguments, the message in lbm_last_error()), and its kernel's name.
+extern "C" int lbm_plan64_rows_sizeof(void);
+extern "C" int lbm_plan64_rows(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRows64* out);
+extern "C" int lbm_plan64_rows_kernel_name(const lbm_internal::PlanRows64* plan, char* kernel_name, size_t len);

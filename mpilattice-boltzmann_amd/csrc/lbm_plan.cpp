@@ -533,6 +533,59 @@ int plan64_multi_next_steps(const PlanMulti64& m, int left)
   return std::min(m.K, left);
 }
 
+// One rank of a row-partitioned double-precision run (lbm_rows64_create).  Rows by the reference's rule; the launch over the rank's
+// ny_local * nx owned cells by plan64_whole's rules (the same lane form, chunking and store rule, the latter on the RANK's two grids,
+// ghost rows included); grids of ny_local + 2 storage rows.  Row ny-2, which accelerate_flow works on, lies in the last rank (the rule
+// gives it at least 3 rows or the run is refused), and is neither that rank's first nor its last row: no edge row is ever accelerated
+// after it was sent.
+int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanRows64* out)
+{
+  if (!p || !out) { set_error("lbm_rows64: null argument"); return 1; }
+  if (p->nx < 1) { set_error("lbm_rows64: nx must be positive"); return 1; }
+  if (p->ny < 3) { set_error("lbm_rows64: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
+  if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { set_error("lbm_rows64: grid too large for 32-bit cell indices"); return 1; }
+  if ((flags & (LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS)) != 0u) {
+    set_error("lbm_rows64: LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused: a row partition exchanges its edge rows after every step (several steps per exchange are not built)");
+    return 1;
+  }
+  if ((flags & ~kFlagsRows64) != 0u) { set_error("lbm_rows64: a row partition takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only"); return 1; }
+  if (nranks < 1 || nranks > kMaxRows64Ranks) { set_error("lbm_rows64: nranks must be 1..64 (MPI_PROCS, d2q9-bgk.c:67)"); return 1; }
+  if (rank < 0 || rank >= nranks) { set_error("lbm_rows64: rank outside 0..nranks-1"); return 1; }
+  int nyl[kMaxRows64Ranks], dis[kMaxRows64Ranks];
+  if (lbm_decompose(p->ny, nranks, nyl, dis)) return 1;                                  // d2q9-bgk.c:834-862
+  for (int r = 0; r < nranks; ++r)
+    if (nyl[r] < 1) { set_error("lbm_rows64: ny = " + std::to_string(p->ny) + " on " + std::to_string(nranks) + " ranks leaves rank " + std::to_string(r) + " without a row"); return 1; }
+  if (nyl[nranks - 1] < 3) {                                                               // :848-849
+    set_error("lbm_rows64: ny = " + std::to_string(p->ny) + " on " + std::to_string(nranks) + " ranks leaves the last rank fewer than 3 rows (d2q9-bgk.c:848-849)");
+    return 1;
+  }
+  PlanRows64 c{};
+  c.flags = flags;
+  c.nranks = nranks; c.rank = rank;
+  c.y0 = dis[rank]; c.ny_local = nyl[rank];
+  const size_t owned = static_cast<size_t>(p->nx) * c.ny_local, storage = static_cast<size_t>(p->nx) * (c.ny_local + 2);
+  c.ps = static_cast<long long>(plane_stride_floats(storage, knobs.skew));     // always even (the pair form's aligned 16-byte accesses)
+  c.grid_doubles = 9 * c.ps + 128;
+  c.nt_stores = 2 * 9 * storage * sizeof(double) > (192u << 20);                // plan64_whole's rule
+  if (flags & LBM_FLAG_NT_STORES) c.nt_stores = 1;
+  if (flags & LBM_FLAG_NO_NT_STORES) c.nt_stores = 0;
+  c.lane_cells = (p->nx % kPairCells == 0) ? kPairCells : 1;
+  c.units = static_cast<unsigned>(owned / c.lane_cells);
+  c.iters = pick_iters(c.units, std::max(knobs.maxblocks, 1));
+  c.blocks = blocks_for(c.units, c.iters);
+  c.partials_cap = c.blocks + 1;
+  c.mask_words = static_cast<int>((owned + 31) / 32 + 4);
+  c.accel_rank = nranks - 1;
+  c.accel_row = p->ny - 2 - dis[nranks - 1];
+  *out = c;
+  return 0;
+}
+
+void plan64_rows_kernel_name(const PlanRows64& c, char* kernel_name, size_t len)
+{
+  std::snprintf(kernel_name, len, c.nt_stores ? "lbm_rows_kernel_f64<%d,nt>" : "lbm_rows_kernel_f64<%d>", c.lane_cells);
+}
+
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
 
 // Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
@@ -903,6 +956,18 @@ int lbm_plan64_run_launches(const lbm_internal::Plan64* plan, int n_steps, int* 
     left -= k;
   }
   return n;
+}
+
+int lbm_plan64_rows_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanRows64)); }
+int lbm_plan64_rows(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRows64* out)
+{
+  return lbm_internal::plan64_rows(knobs_from_env(), p, nranks, rank, flags, out);
+}
+int lbm_plan64_rows_kernel_name(const lbm_internal::PlanRows64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_rows_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_rows_kernel_name(*plan, kernel_name, len);
+  return 0;
 }
 
 int lbm_plan_edge_rows_suffice(const ContextPlan* plan, int left)

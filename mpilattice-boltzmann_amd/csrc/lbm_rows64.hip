@@ -1,0 +1,512 @@
+// lbm_rows64.hip — row-partitioned runs of the double-precision mode: the entry points of include/lbm_d2q9_f64_rows.h and, through
+// kernels/rows64.h, their gfx950 kernels.  A translation unit of its own: the code objects of lbm_kernels.hip and lbm_f64.hip do not
+// change with it.  What each rank gets is decided in lbm_plan.cpp (PlanRows64, lbm_internal.h); this unit allocates and launches by
+// the plans.
+//
+// One lbm_rows64 holds every rank of a run and one host thread drives it.  Rank r owns the rows lbm_decompose gives it, on its device,
+// as two grids of ny_local + 2 storage rows (kernels/rows64.h has the layout), with a stream of its own and two "pushed" events.
+// A step of a rank is lbm_rows_kernel_f64 from grid A (the current one) into grid B, then lbm64_push_rows_kernel, which stores B's edge
+// rows into the neighbours' ghost rows of THEIR grid B, then the record of the rank's pushed event of that step.
+//
+// THE ORDER, and why nothing else is needed.  lbm_rows64_run enqueues, after the accelerate pre-pass on the rank that owns row ny-2,
+// one push of the CURRENT grid's edge rows by every rank ("push -1": every ghost row is then right whatever set_cells or an earlier
+// run left), and then per step t, rank after rank: a hipStreamWaitEvent on both neighbours' pushed events of step t-1, kernel t, push
+// t, the record of pushed[t & 1].  No kernel waits on the device, no flag, no spin.  With A the source and B the destination of step t:
+//   - kernel t of rank r reads A's ghost rows: the neighbours' pushes t-1 wrote them, and kernel t waited for exactly those.
+//   - push t of rank r writes the ghost rows of a neighbour's B.  The last reader of those was the neighbour's kernel t-1 (B was its
+//     source).  Rank r's kernel t waited for that neighbour's push t-1, which follows the neighbour's kernel t-1 on its stream, and
+//     push t follows kernel t on r's stream: the neighbour's kernel t-1 has finished.
+//   - kernel t of rank r writes B's owned rows.  Their readers were r's own kernel t-1 and push t-2, earlier on the same stream; no
+//     other rank ever reads them (the exchange is push only).  The neighbours' pushes t write B's ghost rows meanwhile: other rows.
+//   - an event is recorded again two steps later; every wait on its earlier record was enqueued before that (the waits of step t+1
+//     come before the records of step t+2 in this one host thread), and a wait refers to the record that was current when it was made.
+//   - row ny-2, which the pre-pass and the kernels' epilogue accelerate, is an interior row of the last rank (at least 3 rows): no push
+//     reads it.
+// Every enqueued item depends only on items enqueued before it, so ranks that share a device (and its hardware queues) cannot block
+// each other.  A run ends with every stream synchronised: the next call finds all ranks idle.
+//
+// av_vels[t]: each rank's sums[t] (folded as lbm64_run folds them) copied to the host and added there in rank order, times
+// 1.0 / free_cells: one more serial level of the summation tree, nranks - 1 additions, the same bits in every run.
+//
+// gfx950 only: 64-wide wavefronts (block_sum).
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "lbm_d2q9_f64_rows.h"
+#include "lbm_internal.h"
+#include "lbm_knobs.h"
+#include "kernels/rows64.h"
+
+namespace {
+
+#define HIP_TRY(expr)                                                                        \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
+      return 1;                                                                              \
+    }                                                                                        \
+  } while (0)
+
+struct Rank64 {
+  lbm_internal::PlanRows64 plan{};   // written once (lbm_plan.cpp plan64_rows)
+  int device = 0;
+  size_t ncells = 0, ps = 0;                 // owned cells; plane stride
+  double* grid_alloc[2] = {nullptr, nullptr};
+  double* grid[2] = {nullptr, nullptr};      // plane 0 STORAGE row 0 (after the front guard)
+  uint32_t* mask = nullptr;
+  double* partials[2] = {nullptr, nullptr};
+  double* sums = nullptr;
+  int sums_cap = 0;
+  int* counter = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t pushed[2] = {nullptr, nullptr}; // this rank's push of step t has finished: pushed[t & 1]
+  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
+  std::vector<double> host_sums;
+};
+
+}  // namespace
+
+struct lbm_rows64 {
+  Knobs knobs;
+  lbm64_params p{};
+  int free_cells = 0;
+  double free_cells_inv = 0.0;
+  int nranks = 0;
+  int cur = 0;                               // the current grid of EVERY rank
+  double accel_w1 = 0.0, accel_w2 = 0.0;
+  std::vector<Rank64> ranks;
+  int current_device = -1;                   // of this call, once set
+  int ev_launches = 0;
+  bool ev_valid = false;
+};
+
+namespace {
+
+using Rows64Kernel = void (*)(RowsStep64Args);
+// every instantiation of the rank kernel, by [one cell per lane][non-temporal stores]
+constexpr Rows64Kernel kRows64Kernels[2][2] = {
+  {&lbm_rows_kernel_f64<kPairCells, false>, &lbm_rows_kernel_f64<kPairCells, true>},
+  {&lbm_rows_kernel_f64<1, false>, &lbm_rows_kernel_f64<1, true>},
+};
+
+// hipSetDevice where the device changes: every launch, record and copy of a rank is made with its device current
+int use_device(lbm_rows64* c, int device)
+{
+  if (c->current_device == device) return 0;
+  HIP_TRY(hipSetDevice(device));
+  c->current_device = device;
+  return 0;
+}
+
+int ensure_sums(Rank64& k, int n, int max_iters)
+{
+  if (n <= k.sums_cap) return 0;
+  n = std::max(n, std::max(max_iters, 4096));
+  double* dev = nullptr;
+  HIP_TRY(hipMalloc(&dev, sizeof(double) * static_cast<size_t>(n)));
+  if (k.sums) (void)hipFree(k.sums);         // between runs: the stream is idle
+  k.sums = dev;
+  k.sums_cap = n;
+  return 0;
+}
+
+// cells of whole rows that the chunked copies (cells, observables) move at a time
+size_t chunk_cells(const lbm_rows64* c, const Rank64& k)
+{
+  const size_t nx = static_cast<size_t>(c->p.nx);
+  return std::min(k.ncells, std::max<size_t>(1, static_cast<size_t>(std::max(c->knobs.obs_chunk_cells, 1)) / nx) * nx);
+}
+
+// The first owned cell of a rank's grid: storage row 1.
+double* owned(const lbm_rows64* c, const Rank64& k, int g) { return k.grid[g] + c->p.nx; }
+
+// Rank r's push of grid `g`: its edge rows into the ghost rows of the neighbours' grid `g`.
+int enqueue_push(lbm_rows64* c, int r, int g)
+{
+  Rank64& k = c->ranks[r];
+  const Rank64& down = c->ranks[(r + c->nranks - 1) % c->nranks];
+  const Rank64& up = c->ranks[(r + 1) % c->nranks];
+  RowsPush64Args a{};
+  a.grid = k.grid[g];
+  a.ps = k.ps;
+  a.nx = static_cast<uint32_t>(c->p.nx); a.nyl = static_cast<uint32_t>(k.plan.ny_local);
+  a.down = down.grid[g]; a.down_ps = down.ps; a.down_nyl = static_cast<uint32_t>(down.plan.ny_local);
+  a.up = up.grid[g]; a.up_ps = up.ps;
+  const bool wide = k.plan.lane_cells == kPairCells;
+  const unsigned accesses = 6u * (a.nx / (wide ? kPairCells : 1));
+  const dim3 blocks((accesses + kBlock - 1) / kBlock);
+  if (wide) lbm64_push_rows_kernel<true><<<blocks, dim3(kBlock), 0, k.stream>>>(a);
+  else lbm64_push_rows_kernel<false><<<blocks, dim3(kBlock), 0, k.stream>>>(a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lbm_rows64_abi_version(void) { return LBM_ROWS64_ABI_VERSION; }
+
+int lbm_rows64_destroy(lbm_rows64* c)
+{
+  if (!c) return 0;
+  for (Rank64& k : c->ranks) {
+    if (!k.stream && !k.grid_alloc[0]) continue;             // never reached its device
+    (void)hipSetDevice(k.device);
+    if (k.stream) (void)hipStreamSynchronize(k.stream);
+  }
+  for (Rank64& k : c->ranks) {
+    if (!k.stream && !k.grid_alloc[0]) continue;
+    (void)hipSetDevice(k.device);
+    for (int g = 0; g < 2; ++g) if (k.grid_alloc[g]) (void)hipFree(k.grid_alloc[g]);
+    if (k.mask) (void)hipFree(k.mask);
+    for (int i = 0; i < 2; ++i) if (k.partials[i]) (void)hipFree(k.partials[i]);
+    if (k.sums) (void)hipFree(k.sums);
+    if (k.counter) (void)hipFree(k.counter);
+    for (int i = 0; i < 2; ++i) if (k.pushed[i]) (void)hipEventDestroy(k.pushed[i]);
+    if (k.ev_begin) (void)hipEventDestroy(k.ev_begin);
+    if (k.ev_end) (void)hipEventDestroy(k.ev_end);
+    if (k.stream) (void)hipStreamDestroy(k.stream);
+  }
+  delete c;
+  return 0;
+}
+
+int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, const int* obstacles, int nranks, const int* devices, unsigned flags)
+{
+  if (!out || !p || !obstacles) { lbm_internal::set_error("lbm_rows64_create: null argument"); return 1; }
+  *out = nullptr;
+  const Knobs knobs = knobs_from_env();
+  {
+    lbm_internal::PlanRows64 first;
+    if (lbm_internal::plan64_rows(knobs, p, nranks, 0, flags, &first)) return 1;      // every refusal that needs no device
+  }
+  if (free_cells <= 0) { lbm_internal::set_error("lbm_rows64_create: free_cells must be positive"); return 1; }
+  lbm_rows64* c = new lbm_rows64();
+  c->knobs = knobs;
+  c->p = *p;
+  c->free_cells = free_cells;
+  c->free_cells_inv = 1.0 / free_cells;                                      // d2q9-bgk.c:950 in double
+  c->nranks = nranks;
+  c->accel_w1 = p->density * p->accel * 0.111111111111111111111111;         // d2q9-bgk.c:445
+  c->accel_w2 = p->density * p->accel * 0.0277777777777777777777778;        // d2q9-bgk.c:446
+  c->ranks.resize(static_cast<size_t>(nranks));
+  auto fail = [&](void) { lbm_rows64_destroy(c); return 1; };
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    if (lbm_internal::plan64_rows(knobs, p, nranks, r, flags, &k.plan)) return fail();
+    k.ncells = static_cast<size_t>(p->nx) * k.plan.ny_local;
+    k.ps = static_cast<size_t>(k.plan.ps);
+  }
+#define HIP_TRY_C(expr)                                                                      \
+  do {                                                                                       \
+    hipError_t e_ = (expr);                                                                  \
+    if (e_ != hipSuccess) {                                                                  \
+      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
+      return fail();                                                                         \
+    }                                                                                        \
+  } while (0)
+
+  if (devices) {
+    for (int r = 0; r < nranks; ++r) c->ranks[r].device = devices[r];
+  } else {
+    int count = 0;
+    HIP_TRY_C(hipGetDeviceCount(&count));
+    if (count < 1) { lbm_internal::set_error("lbm_rows64_create: no GPU"); return fail(); }
+    for (int r = 0; r < nranks; ++r) c->ranks[r].device = r % count;
+  }
+  for (int r = 0; r < nranks; ++r) {
+    const int device = c->ranks[r].device;
+    HIP_TRY_C(hipSetDevice(device));
+  }
+  // neighbours on distinct devices store into each other's grids: peer access, both ways
+  for (int r = 0; r < nranks; ++r) {
+    const int a = c->ranks[r].device, b = c->ranks[(r + 1) % nranks].device;
+    if (a == b) continue;
+    for (int way = 0; way < 2; ++way) {
+      const int from = way ? b : a, to = way ? a : b;
+      int can = 0;
+      HIP_TRY_C(hipDeviceCanAccessPeer(&can, from, to));
+      if (!can) {
+        lbm_internal::set_error("lbm_rows64_create: device " + std::to_string(from) + " cannot access device " + std::to_string(to) + " (hipDeviceCanAccessPeer): the ranks' edge rows travel as peer-to-peer stores");
+        return fail();
+      }
+      HIP_TRY_C(hipSetDevice(from));
+      const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
+        lbm_internal::set_error(std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
+        return fail();
+      }
+      (void)hipGetLastError();
+    }
+  }
+  const double w0 = p->density * 4.0 / 9.0, w1 = p->density / 9.0, w2 = p->density / 36.0;   // d2q9-bgk.c:880-882
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    const lbm_internal::PlanRows64& plan = k.plan;
+    HIP_TRY_C(hipSetDevice(k.device));
+    HIP_TRY_C(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; ++i) HIP_TRY_C(hipEventCreateWithFlags(&k.pushed[i], hipEventDisableTiming));
+    HIP_TRY_C(hipEventCreate(&k.ev_begin));
+    HIP_TRY_C(hipEventCreate(&k.ev_end));
+    for (int g = 0; g < 2; ++g) {
+      HIP_TRY_C(hipMalloc(&k.grid_alloc[g], sizeof(double) * static_cast<size_t>(plan.grid_doubles)));
+      HIP_TRY_C(hipMemsetAsync(k.grid_alloc[g], 0, sizeof(double) * static_cast<size_t>(plan.grid_doubles), k.stream));
+      k.grid[g] = k.grid_alloc[g] + 64;
+    }
+    {
+      // obstacle bitfield of the owned rows: bit c of the owned-cell index
+      std::vector<uint32_t> bits(static_cast<size_t>(plan.mask_words), 0u);
+      const int* mine = obstacles + static_cast<size_t>(plan.y0) * p->nx;
+      for (size_t i = 0; i < k.ncells; ++i)
+        if (mine[i]) bits[i >> 5] |= 1u << (i & 31);
+      HIP_TRY_C(hipMalloc(&k.mask, sizeof(uint32_t) * bits.size()));
+      HIP_TRY_C(hipMemcpy(k.mask, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
+    }
+    for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&k.partials[i], sizeof(double) * static_cast<size_t>(plan.partials_cap)));
+    HIP_TRY_C(hipMalloc(&k.counter, sizeof(int)));
+    HIP_TRY_C(hipMemsetAsync(k.counter, 0, sizeof(int), k.stream));
+    if (ensure_sums(k, 1, p->max_iters)) return fail();
+    const unsigned blocks = static_cast<unsigned>((k.ncells + 255) / 256);
+    hipLaunchKernelGGL(lbm64_init_kernel, dim3(blocks), dim3(256), 0, k.stream, owned(c, k, 0), k.ps, k.ncells, w0, w1, w2);
+    HIP_TRY_C(hipGetLastError());
+  }
+  for (int r = 0; r < nranks; ++r) {
+    HIP_TRY_C(hipSetDevice(c->ranks[r].device));
+    HIP_TRY_C(hipStreamSynchronize(c->ranks[r].stream));
+  }
+#undef HIP_TRY_C
+  *out = c;
+  return 0;
+}
+
+int lbm_rows64_run(lbm_rows64* c, int n_steps, double* av_vels)
+{
+  if (!c) { lbm_internal::set_error("lbm_rows64_run: null run"); return 1; }
+  if (n_steps < 0) { lbm_internal::set_error("lbm_rows64_run: negative step count"); return 1; }
+  if (n_steps == 0) return 0;
+  c->current_device = -1;
+  const int nranks = c->nranks;
+  const uint32_t nx = static_cast<uint32_t>(c->p.nx);
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    if (ensure_sums(k, n_steps, c->p.max_iters)) return 1;
+  }
+  {
+    // accelerate_flow of the first step (d2q9-bgk.c:345-348) on the rank that owns row ny-2: every later one is the epilogue of the step before it
+    Rank64& k = c->ranks[c->ranks[0].plan.accel_rank];
+    if (use_device(c, k.device)) return 1;
+    hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, k.stream, owned(c, k, c->cur), k.ps, k.mask, nx,
+                       static_cast<uint32_t>(k.plan.accel_row), c->accel_w1, c->accel_w2);
+    HIP_TRY(hipGetLastError());
+  }
+  // push -1: the current grid's edge rows into the neighbours' ghost rows (all ranks are idle: the last call synchronised them)
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    if (use_device(c, k.device)) return 1;
+    if (enqueue_push(c, r, c->cur)) return 1;
+    HIP_TRY(hipEventRecord(k.pushed[1], k.stream));
+  }
+  int parity = 0;
+  for (int t = 0; t < n_steps; ++t) {
+    const int before = (t + 1) & 1, now = t & 1;            // the pushed events of step t-1 and of step t
+    for (int r = 0; r < nranks; ++r) {
+      Rank64& k = c->ranks[r];
+      const lbm_internal::PlanRows64& plan = k.plan;
+      const int down = (r + nranks - 1) % nranks, up = (r + 1) % nranks;
+      if (use_device(c, k.device)) return 1;
+      if (down != r) HIP_TRY(hipStreamWaitEvent(k.stream, c->ranks[down].pushed[before], 0));
+      if (up != r && up != down) HIP_TRY(hipStreamWaitEvent(k.stream, c->ranks[up].pushed[before], 0));
+      if (t == 0) HIP_TRY(hipEventRecord(k.ev_begin, k.stream));
+      RowsStep64Args a{};
+      a.src = k.grid[c->cur];
+      a.dst = k.grid[c->cur ^ 1];
+      a.mask = k.mask;
+      a.ps = k.ps;
+      a.nx = nx;
+      a.units = plan.units;
+      a.iters = plan.iters;
+      a.omega = c->p.omega;
+      a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+      a.accel_row = (r == plan.accel_rank && t + 1 < n_steps) ? plan.accel_row : -1;
+      a.partials_out = k.partials[parity];
+      a.prev_partials = k.partials[parity ^ 1];
+      a.n_prev = t > 0 ? plan.blocks : 0;
+      a.sums = k.sums;
+      a.counter = k.counter;
+      kRows64Kernels[plan.lane_cells == 1][plan.nt_stores]<<<dim3(plan.blocks + 1), dim3(kBlock), 0, k.stream>>>(a);   // + the fold block
+      HIP_TRY(hipGetLastError());
+      if (enqueue_push(c, r, c->cur ^ 1)) return 1;
+      HIP_TRY(hipEventRecord(k.pushed[now], k.stream));
+    }
+    parity ^= 1;
+    c->cur ^= 1;
+  }
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    if (use_device(c, k.device)) return 1;
+    HIP_TRY(hipEventRecord(k.ev_end, k.stream));
+    hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, k.stream, k.partials[parity ^ 1], k.plan.blocks, 1, k.sums, k.counter);
+    HIP_TRY(hipGetLastError());
+    if (av_vels) {
+      k.host_sums.resize(static_cast<size_t>(n_steps));
+      HIP_TRY(hipMemcpyAsync(k.host_sums.data(), k.sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, k.stream));
+    }
+  }
+  c->ev_launches = n_steps * nranks;
+  c->ev_valid = true;
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    if (use_device(c, k.device)) return 1;
+    HIP_TRY(hipStreamSynchronize(k.stream));
+  }
+  if (av_vels) {
+    for (int t = 0; t < n_steps; ++t) {
+      double s = c->ranks[0].host_sums[t];
+      for (int r = 1; r < nranks; ++r) s += c->ranks[r].host_sums[t];        // rank order: nranks - 1 additions
+      av_vels[t] = s * c->free_cells_inv;                                    // d2q9-bgk.c:367
+    }
+  }
+  return 0;
+}
+
+int lbm_rows64_get_cells(lbm_rows64* c, double* cells_aos)
+{
+  if (!c || !cells_aos) { lbm_internal::set_error("lbm_rows64_get_cells: null argument"); return 1; }
+  c->current_device = -1;
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
+    unsigned long long* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
+    hipError_t e = hipSuccess;
+    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
+      const size_t n = std::min(chunk, k.ncells - c0);
+      hipLaunchKernelGGL(lbm64_soa_to_aos_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, k.stream,
+                         reinterpret_cast<const unsigned long long*>(owned(c, k, c->cur) + c0), tmp, k.ps, n);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(cells_aos + 9 * (first + c0), tmp, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, k.stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
+    }
+    (void)hipFree(tmp);
+    HIP_TRY(e);
+  }
+  return 0;
+}
+
+int lbm_rows64_set_cells(lbm_rows64* c, const double* cells_aos)
+{
+  if (!c || !cells_aos) { lbm_internal::set_error("lbm_rows64_set_cells: null argument"); return 1; }
+  c->current_device = -1;
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
+    unsigned long long* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
+    hipError_t e = hipSuccess;
+    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
+      const size_t n = std::min(chunk, k.ncells - c0);
+      e = hipMemcpyAsync(tmp, cells_aos + 9 * (first + c0), sizeof(double) * 9 * n, hipMemcpyHostToDevice, k.stream);
+      if (e == hipSuccess) {
+        hipLaunchKernelGGL(lbm64_aos_to_soa_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, k.stream,
+                           tmp, reinterpret_cast<unsigned long long*>(owned(c, k, c->cur) + c0), k.ps, n);
+        e = hipGetLastError();
+      }
+      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
+    }
+    (void)hipFree(tmp);
+    HIP_TRY(e);
+  }
+  return 0;
+}
+
+int lbm_rows64_get_observables(lbm_rows64* c, double* obs)
+{
+  if (!c || !obs) { lbm_internal::set_error("lbm_rows64_get_observables: null argument"); return 1; }
+  c->current_device = -1;
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
+    double* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 4 * chunk));
+    hipError_t e = hipSuccess;
+    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
+      const size_t n = std::min(chunk, k.ncells - c0);
+      hipLaunchKernelGGL(lbm64_observables_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, k.stream,
+                         owned(c, k, c->cur) + c0, k.ps, n, tmp);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipMemcpyAsync(obs + 4 * (first + c0), tmp, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, k.stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
+    }
+    (void)hipFree(tmp);
+    HIP_TRY(e);
+  }
+  return 0;
+}
+
+int lbm_rows64_av_velocity_sum(lbm_rows64* c, double* tot_u)
+{
+  if (!c || !tot_u) { lbm_internal::set_error("lbm_rows64_av_velocity_sum: null argument"); return 1; }
+  c->current_device = -1;
+  double s = 0.0;
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    const int blocks = static_cast<int>(std::min<size_t>((k.ncells + kBlock - 1) / kBlock, 1024));
+    double* part = nullptr;
+    HIP_TRY(hipMalloc(&part, sizeof(double) * blocks));
+    hipLaunchKernelGGL(lbm64_av_velocity_kernel, dim3(blocks), dim3(kBlock), 0, k.stream, owned(c, k, c->cur), k.ps, k.mask, k.ncells, part);
+    std::vector<double> host(blocks);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), part, sizeof(double) * blocks, hipMemcpyDeviceToHost, k.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
+    (void)hipFree(part);
+    HIP_TRY(e);
+    for (double v : host) s += v;            // the blocks' sums, rank after rank
+  }
+  *tot_u = s;
+  return 0;
+}
+
+int lbm_rows64_last_run_ms(lbm_rows64* c, double* ms, int* launches)
+{
+  if (!c || !ms) { lbm_internal::set_error("lbm_rows64_last_run_ms: null argument"); return 1; }
+  if (!c->ev_valid) { lbm_internal::set_error("lbm_rows64_last_run_ms: no run yet"); return 1; }
+  c->current_device = -1;
+  double most = 0.0;
+  for (Rank64& k : c->ranks) {
+    if (use_device(c, k.device)) return 1;
+    float t = 0.f;
+    HIP_TRY(hipEventElapsedTime(&t, k.ev_begin, k.ev_end));
+    most = std::max(most, static_cast<double>(t));
+  }
+  *ms = most;
+  if (launches) *launches = c->ev_launches;
+  return 0;
+}
+
+int lbm_rows64_describe(const lbm_rows64* c, char* kernel_name, size_t len, int* nranks, long long* blocks, long long* cells_per_block, long long* state_bytes)
+{
+  if (!c) { lbm_internal::set_error("lbm_rows64_describe: null run"); return 1; }
+  const Rank64* most = &c->ranks[0];
+  long long bytes = 0;
+  for (const Rank64& k : c->ranks) {
+    if (k.plan.blocks > most->plan.blocks) most = &k;
+    bytes += static_cast<long long>(2 * 9 * sizeof(double)) * c->p.nx * (k.plan.ny_local + 2);
+  }
+  if (kernel_name && len > 0) lbm_internal::plan64_rows_kernel_name(most->plan, kernel_name, len);
+  if (nranks) *nranks = c->nranks;
+  if (blocks) *blocks = most->plan.blocks;
+  if (cells_per_block) *cells_per_block = static_cast<long long>(kBlock) * most->plan.iters * most->plan.lane_cells;
+  if (state_bytes) *state_bytes = bytes;
+  return 0;
+}
+
+}  // extern "C"

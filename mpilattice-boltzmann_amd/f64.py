@@ -11,6 +11,9 @@
 The reference's arithmetic with every float object a double (the contract is in the header): whole periodic grids on one GPU, one
 step per launch of lbm_step_kernel_f64 or, with `flags=f64.FLAG_TILE_STEPS` on a small grid, several per launch of lbm_tile_kernel_f64,
 with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_multi_kernel_f64 (the same populations, bit for bit).  There is no CPU fallback: a missing library or symbol raises.
+
+`f64.Rows64(p, obst, nranks, devices=None)` is the same grid as `nranks` row blocks over one or several GPUs of this process
+(include/lbm_d2q9_f64_rows.h): Grid64's methods, Grid64's populations bit for bit for every rank count.
 """
 from __future__ import annotations
 
@@ -188,4 +191,134 @@ class Grid64:
         return {"kernel": name.value.decode(), "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
 
 
-__all__ = ["ABI_VERSION", "EXPORTS", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "CParams64", "Grid64", "LbmError", "load_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]
+# ---- row-partitioned runs (include/lbm_d2q9_f64_rows.h): a signature table of their own, beside EXPORTS, which stays as it is ----
+ROWS_ABI_VERSION = 1
+_ROWS_SIGNATURES = {
+    "lbm_rows64_abi_version": (C.c_int, []),
+    "lbm_rows64_create": (C.c_int, [_P(_ctx), _P(CParams64), C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_uint]),
+    "lbm_rows64_destroy": (C.c_int, [_ctx]),
+    "lbm_rows64_run": (C.c_int, [_ctx, C.c_int, _P(C.c_double)]),
+    "lbm_rows64_get_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_rows64_set_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_rows64_get_observables": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_rows64_av_velocity_sum": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_rows64_last_run_ms": (C.c_int, [_ctx, _P(C.c_double), _P(C.c_int)]),
+    "lbm_rows64_describe": (C.c_int, [_ctx, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_longlong), _P(C.c_longlong), _P(C.c_longlong)]),
+}
+ROWS_EXPORTS = tuple(_ROWS_SIGNATURES)
+
+_rows_typed = None
+
+
+def load_rows_library() -> C.CDLL:
+    """liblbm_d2q9.so with the lbm64_* and the lbm_rows64_* prototypes set.  Raises if the library or one of the symbols is absent."""
+    global _rows_typed
+    if _rows_typed is None:
+        lib = load_library()
+        for name, (res, args) in _ROWS_SIGNATURES.items():
+            fn = getattr(lib, name)           # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
+        if lib.lbm_rows64_abi_version() != ROWS_ABI_VERSION:
+            raise RuntimeError(f"liblbm_d2q9.so row-partition ABI {lib.lbm_rows64_abi_version()} != binding {ROWS_ABI_VERSION}: rebuild")
+        _rows_typed = lib
+    return _rows_typed
+
+
+class Rows64:
+    """A whole periodic grid in double precision, its rows dealt to `nranks` ranks on one or several GPUs — one `lbm_rows64`.
+    `devices`: one HIP ordinal per rank (ranks may share a device), or None: rank r on device r % (device count).  Grid64's methods;
+    the populations are Grid64's bits for every rank count."""
+
+    def __init__(self, params, obstacles: np.ndarray, nranks: int, devices=None, flags: int = 0):
+        self._lib = load_rows_library()
+        self.params = params
+        self.nranks = int(nranks)
+        self.obstacles = np.ascontiguousarray(obstacles, dtype=np.int32)
+        if self.obstacles.shape != (params.ny, params.nx):
+            raise ValueError("obstacles must be (ny, nx)")
+        self.free_cells = int(self.obstacles.size - np.count_nonzero(self.obstacles))
+        self._cp = _cparams(params)
+        self._run = _ctx()
+        dev = None
+        if devices is not None:
+            devices = [int(d) for d in devices]
+            if len(devices) != self.nranks:
+                raise ValueError("devices must name one device per rank")
+            dev = (C.c_int * max(len(devices), 1))(*devices)
+        check(self._lib.lbm_rows64_create(C.byref(self._run), C.byref(self._cp), self.free_cells, _capi.as_int_ptr(self.obstacles), self.nranks, dev, flags))
+
+    def close(self) -> None:
+        if getattr(self, "_run", None):
+            self._lib.lbm_rows64_destroy(self._run)
+            self._run = None
+
+    def __enter__(self) -> "Rows64":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, n_steps: Optional[int] = None) -> np.ndarray:
+        """n_steps iterations (default max_iters) on every rank; returns av_vels, float64 (n_steps,)."""
+        n = self.params.max_iters if n_steps is None else int(n_steps)
+        av = np.zeros(max(n, 1), dtype=np.float64)
+        check(self._lib.lbm_rows64_run(self._run, n, _capi.as_double_ptr(av)))
+        return av[:n]
+
+    def get_cells(self) -> np.ndarray:
+        """(ny, nx, 9) float64 of the whole grid, the reference's AoS layout."""
+        cells = np.empty((self.params.ny, self.params.nx, 9), dtype=np.float64)
+        check(self._lib.lbm_rows64_get_cells(self._run, _capi.as_double_ptr(cells)))
+        return cells
+
+    def set_cells(self, cells: np.ndarray) -> None:
+        cells = np.ascontiguousarray(cells, dtype=np.float64)
+        if cells.size != self.params.ny * self.params.nx * 9:
+            raise ValueError("cells must hold ny * nx * 9 doubles")
+        check(self._lib.lbm_rows64_set_cells(self._run, _capi.as_double_ptr(cells)))
+
+    def get_observables(self) -> np.ndarray:
+        """(ny, nx, 4) float64 = {u_x, u_y, u, pressure} per cell, the fluid-cell formula for every cell."""
+        obs = np.empty((self.params.ny, self.params.nx, 4), dtype=np.float64)
+        check(self._lib.lbm_rows64_get_observables(self._run, _capi.as_double_ptr(obs)))
+        return obs
+
+    def av_velocity_sum(self) -> float:
+        """av_velocity()'s sum over the free cells, summed on the devices, the blocks' sums added rank after rank."""
+        tot = C.c_double(0.0)
+        check(self._lib.lbm_rows64_av_velocity_sum(self._run, C.byref(tot)))
+        return tot.value
+
+    def reynolds(self) -> float:
+        """calc_reynolds (`d2q9-bgk.c:1005-1007`) of the current state, the sum taken in the reference's cell order on the host: the
+        bits Grid64.reynolds gives."""
+        obs = self.get_observables()
+        tot = self._lib.lbm64_av_velocity_obs(C.byref(self._cp), _capi.as_double_ptr(obs), _capi.as_int_ptr(self.obstacles), self.params.ny)
+        return self._lib.lbm64_reynolds(C.byref(self._cp), tot * (1.0 / self.free_cells))
+
+    def write_values(self, final_state_path: str, av_vels_path: str, av_vels: np.ndarray) -> None:
+        """write_values (`d2q9-bgk.c:1054-1139`): both output files."""
+        write_final_state_obs64(final_state_path, self.params, self.get_observables(), self.obstacles)
+        write_av_vels64(av_vels_path, av_vels)
+
+    def last_run_ms(self) -> tuple[float, int]:
+        """(device ms of the last run: the largest span over the ranks from its first step kernel to its last push, step launches)."""
+        ms, n = C.c_double(0.0), C.c_int(0)
+        check(self._lib.lbm_rows64_last_run_ms(self._run, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def describe(self) -> dict:
+        name = C.create_string_buffer(256)
+        nranks, blocks, per_block, nbytes = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.lbm_rows64_describe(self._run, name, 256, C.byref(nranks), C.byref(blocks), C.byref(per_block), C.byref(nbytes)))
+        return {"kernel": name.value.decode(), "nranks": nranks.value, "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
+
+
+__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
+           "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]

@@ -3,12 +3,15 @@
 tests/golden/check/ (tolerance 1 %) and to the Reynolds number the reference published (tests/golden/f64_published.json), with the
 largest relative distance of av_vels from the shipped file beside it.
 
-    python scripts/check_f64_decks.py [--decks 128x128,128x256] [--flags 512] [--out profiles/r07/check_f64_decks.txt]
+    python scripts/check_f64_decks.py [--decks 128x128,128x256] [--flags 512] [--ranks 4] [--out profiles/r07/check_f64_decks.txt]
 
 LBM_TUNE_TILE64_MAX and LBM_TUNE_TILE64_GEOM of the caller's environment reach the CLI; every other LBM_* variable is dropped.  Each
 deck's report ends with the kernel that ran and its launches (LBM_DESCRIBE=1).
 
 --flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS, 1024 = LBM64_FLAG_MULTI_STEPS, 1536 = both: several steps per launch where the grid is eligible).
+
+--ranks N: LBM64_RANKS of the CLI: the deck as N row blocks (include/lbm_d2q9_f64_rows.h), rank r on device r % (device count); then
+--flags takes 0, 1 or 2 only.
 
 One CLI process per deck, each under a time limit; the first failure ends the script (exit status 1)."""
 import argparse
@@ -35,19 +38,22 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per deck")
     ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS, 1024: LBM64_FLAG_MULTI_STEPS, 1536: both)")
+    ap.add_argument("--ranks", type=int, default=0, help="LBM64_RANKS: the deck as this many row blocks (0: one context)")
     a = ap.parse_args()
     lbm.build()
     with open(os.path.join(GOLDEN, "f64_published.json")) as fh:
         published = json.load(fh)["reynolds"]
-    lines = [f"# LBM_PRECISION=double{f' LBM_FLAGS={a.flags}' if a.flags else ''} bin/d2q9-bgk on the shipped decks (full length), then checker.check_files against tests/golden/check/ (tolerance 1 %)",
+    lines = [f"# LBM_PRECISION=double{f' LBM_FLAGS={a.flags}' if a.flags else ''}{f' LBM64_RANKS={a.ranks}' if a.ranks else ''} bin/d2q9-bgk on the shipped decks (full length), then checker.check_files against tests/golden/check/ (tolerance 1 %)",
              "# and the Reynolds line against the number the reference published"]
     ok = True
     for name in a.decks.split(","):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("LBM_") or k in ("LBM_TUNE_TILE64_MAX", "LBM_TUNE_TILE64_GEOM", "LBM_TUNE_MULTI64_K", "LBM_TUNE_MULTI64_MIN")}
+        env = {k: v for k, v in os.environ.items() if not k.startswith(("LBM_", "LBM64_")) or k in ("LBM_TUNE_TILE64_MAX", "LBM_TUNE_TILE64_GEOM", "LBM_TUNE_MULTI64_K", "LBM_TUNE_MULTI64_MIN")}
         env["LBM_PRECISION"] = "double"
         env["LBM_DESCRIBE"] = "1"                      # one line on stderr: the kernel that ran and its launches
         if a.flags:
             env["LBM_FLAGS"] = str(a.flags)
+        if a.ranks:
+            env["LBM64_RANKS"] = str(a.ranks)
         with tempfile.TemporaryDirectory() as tmp:
             cmd = [lbm.CLI_PATH, os.path.join(GOLDEN, "decks", f"input_{name}.params"), os.path.join(GOLDEN, "decks", f"obstacles_{name}.dat")]
             r = subprocess.run(cmd, cwd=tmp, env=env, capture_output=True, text=True, timeout=a.timeout)

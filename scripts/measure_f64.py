@@ -35,7 +35,16 @@ compared for equal bits (host-bound, about 13 GB of host memory); its line goes 
     timeout -k 10 180 python scripts/measure_f64.py --multi --baseline-lib $B --work 4096x4096 --out $F &&
     timeout -k 10 120 python scripts/measure_f64.py --multi --baseline-lib $B --work 2048x2048 --out $F &&
     timeout -k 10 120 python scripts/measure_f64.py --multi --baseline-lib $B --work 1024x1024 --out $F &&
-    timeout -k 10 300 python scripts/measure_f64.py --multi-bits 3 --out $F"""
+    timeout -k 10 300 python scripts/measure_f64.py --multi-bits 3 --out $F
+
+--ranks N[,N] [--devices LIST] [--steps S]: row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count beside
+the one-context one-step and LBM64_FLAG_MULTI_STEPS runs of the same grid (--work NXxNY, default 8192x8192), alternating: device and
+wall time per step.  With all ranks on one device this measures the loop's overhead, not a speed-up; --out appends.
+
+    F=profiles/r14/f64_rows.txt; rm -f $F
+    timeout -k 10 400 python scripts/measure_f64.py --ranks 1,2,8 --work 8192x8192 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1 --work 8192x1024 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 8 --work 1024x1024 --steps 2000 --out $F"""
 import argparse
 import ctypes as C
 import os
@@ -266,6 +275,48 @@ def multi_bits(ks, lines):
             raise SystemExit("8192x7296: the populations differ")
 
 
+def measure_rows(name, ranks, devices, steps, reps, lines):
+    """Row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count of `ranks` beside the one-context one-step
+    kernel and the one-context LBM64_FLAG_MULTI_STEPS run of the same grid: per step, the device time (events: for a partitioned run
+    the largest span over the ranks) and the host's wall time around run(), which ends in a synchronise.  The contexts alternate run by
+    run.  With all ranks on one device their kernels serialise: the difference to the one-context figure is the loop's overhead."""
+    import time
+    p, obst = deck(name)
+    n0 = len(lines)
+    runs = {"one context, one step": f64.Grid64(p, obst)}
+    multi = f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS)
+    if multi.describe()["kernel"].startswith("lbm_multi_kernel_f64<"):
+        runs["one context, multi-step"] = multi
+    else:
+        multi.close()
+    for n in ranks:
+        dev = None if devices is None else [devices[r % len(devices)] for r in range(n)]
+        runs[f"{n} rank{'s' if n > 1 else ''}"] = f64.Rows64(p, obst, n, devices=dev)
+    shapes = {k: q.describe() for k, q in runs.items()}
+    first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
+    base = first["one context, one step"]
+    for k, av in first.items():                            # the same run: av_vels agree to the order of their additions
+        if not np.allclose(av, base, rtol=1e-12, atol=0.0):
+            raise SystemExit(f"{name}, {k}: av_vels differ from the one-step context's by {np.max(np.abs(av - base) / base):.3e}")
+    dev_us, wall_us = {k: [] for k in runs}, {k: [] for k in runs}
+    for _ in range(reps):
+        for k, q in runs.items():                          # alternate: all see the same drift of the card
+            t0 = time.perf_counter()
+            q.run(steps)
+            wall_us[k].append(1e6 * (time.perf_counter() - t0) / steps)
+            ms = q.last_run_ms()[0] if isinstance(q, f64.Rows64) else q.last_run_kernel_ms()[0]
+            dev_us[k].append(1e3 * ms / steps)
+    for q in runs.values():
+        q.close()
+    where = "the library's default (rank r on device r % device count)" if devices is None else f"devices {devices}, cycled"
+    lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; ranks on {where}; us per step")
+    for k in runs:
+        d, w = dev_us[k], wall_us[k]
+        lines.append(f"  {k:24s} {shapes[k]['kernel']:28s} {shapes[k]['blocks']:6d} blocks   device median {statistics.median(d):9.3f}  min {min(d):9.3f}  max {max(d):9.3f}"
+                     f"   wall median {statistics.median(w):9.3f}  min {min(w):9.3f}  max {max(w):9.3f}")
+    print("\n".join(lines[n0:]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small step counts (a functional check of this script)")
@@ -275,8 +326,22 @@ def main():
     ap.add_argument("--multi", action="store_true", help="LBM64_FLAG_MULTI_STEPS with every built K against --baseline-lib's one-step path; --work: a size")
     ap.add_argument("--multi-bits", metavar="K[,K]", help="the 8192 x 7296 bit comparison of lbm_multi_kernel_f64<K> with the one-step kernel (--out appends)")
     ap.add_argument("--baseline-lib", help="liblbm_d2q9.so of the parent commit")
+    ap.add_argument("--ranks", metavar="N[,N]", help="row-partitioned runs (f64.Rows64) with these rank counts beside the one-context runs; --work: NXxNY (default 8192x8192)")
+    ap.add_argument("--devices", metavar="LIST", help="with --ranks: HIP ordinals, rank r on LIST[r %% len(LIST)] (default: the library's, r %% device count)")
+    ap.add_argument("--steps", type=int, help="with --ranks: steps per run (default 200)")
     a = ap.parse_args()
     lbm.build()
+    if a.ranks:
+        lines = [] if a.out and os.path.exists(a.out) else [
+            "# scripts/measure_f64.py --ranks: row-partitioned double-precision runs (lbm_rows_kernel_f64 + lbm64_push_rows_kernel per rank-step) beside the one-context runs",
+            "# device: events around a run's step launches, over its steps (partitioned: the largest span over the ranks); wall: the host's clock around run()"]
+        measure_rows(a.work or "8192x8192", [int(v) for v in a.ranks.split(",")], [int(v) for v in a.devices.split(",")] if a.devices else None,
+                     a.steps or (12 if a.quick else 200), 3 if a.quick else 5, lines)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
     if a.multi_bits:
         lines = []
         multi_bits([int(v) for v in a.multi_bits.split(",")], lines)

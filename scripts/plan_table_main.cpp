@@ -1,6 +1,6 @@
 // plan_table_main.cpp — the planning unit under the host sanitizers: the three plan functions over the table of tests/plan_cases.py and
 // over the refusals, printed one line per context, and under each context every launch of its runs of 11 and 20 steps, both schedules
-// (lbm_plan_run_launches), one line per launch.  Host-only code, no GPU and no Python (of lbm_host.cpp the planner needs set_error and
+// (lbm_plan_run_launches), one line per launch; then the row blocks of the double-precision mode (lbm_plan64_rows), one line per rank.  Host-only code, no GPU and no Python (of lbm_host.cpp the planner needs set_error and
 // the two decompositions only):
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I mpilattice-boltzmann_amd/csrc
 //       scripts/plan_table_main.cpp mpilattice-boltzmann_amd/csrc/lbm_plan.cpp mpilattice-boltzmann_amd/csrc/lbm_host.cpp -pthread -o plan_table && ./plan_table
@@ -55,6 +55,20 @@ int main()
     for (int r = 0; r < t[2] * t[3]; ++r) show("tile", t[0], t[1], lbm_plan_tile(&p, 1000, t[2], t[3], r, 0, &plan), plan);
   }
   show("null", 0, 0, lbm_plan_whole(nullptr, 1, 0, 1, 0, 0, &plan), plan);
+  // the row blocks of the double-precision mode (plan64_rows): every rank of the shapes tests/test_f64_rows.py runs, and the refusals
+  const int rows[][3] = {{1, 3, 1}, {2, 6, 3}, {7, 5, 2}, {32, 16, 5}, {64, 48, 8}, {258, 33, 4}, {8192, 8192, 8}, {8, 5, 3}, {8, 3, 3}, {8, 16, 0}, {8, 16, 65}, {0, 16, 2}, {65536, 32768, 2}};
+  for (const auto& g : rows)
+    for (unsigned f : {0u, unsigned(LBM_FLAG_NT_STORES), unsigned(LBM64_FLAG_MULTI_STEPS), unsigned(LBM_FLAG_FUSED_ARITH)}) {
+      const lbm64_params p{g[0], g[1], 11, 10, 0.1, 0.005, 1.85};
+      for (int r = 0; r < (g[2] > 0 && g[2] <= 64 ? g[2] : 1); ++r, ++shown) {
+        lbm_internal::PlanRows64 q;
+        char name[64] = "";
+        const int rc = lbm_plan64_rows(&p, g[2], r, f, &q);
+        if (rc == 0) lbm_plan64_rows_kernel_name(&q, name, sizeof name);
+        if (rc == 0) std::printf("rows  %6d x %-6d rank %d of %d: rows %d + %d, %s, %u units in %d blocks x %d, ps %lld\n", g[0], g[1], r, g[2], q.y0, q.ny_local, name, q.units, q.blocks, q.iters, q.ps);
+        else std::printf("rows  %6d x %-6d rank %d of %d: %s\n", g[0], g[1], r, g[2], lbm_last_error());
+      }
+    }
   std::printf("%d plans, %d launches, clean\n", shown, launches);
   return 0;
 }
