@@ -98,7 +98,9 @@ int lbm_decompose(int ny, int size, int* ny_local, int* displs);
  * steps launch (or macro-step) i makes.  K at a time; with `four_rows` (a whole periodic grid, or a partition that
  * keeps four ghost rows) a count K does not divide is split into 4s and 3s where that avoids a 1- or 2-step launch at
  * the end (K = 4: n = 4a + 3, 4a + 6, 4a + 9; K = 3: n = 3a + 4, 3a + 8).  A function of its arguments only — every rank
- * of a partitioned run plans the same sequence.  Returns the number of launches (at most `cap` entries are written),
+ * of a partitioned run plans the same sequence.  K = 1 .. 4: what a partition's launches make.  (A whole periodic grid of
+ * 8192 x 8192 cells or more makes FIVE steps per launch, which lbm_run cuts by the same rule: 5s, then 4 + 3 or 3 + 3; this
+ * function does not plan those runs and refuses K = 5.)  Returns the number of launches (at most `cap` entries are written),
  * or -1 on a bad argument. */
 int lbm_plan_steps(int K, int four_rows, int n_steps, int* steps, int cap);
 /* A row-partitioned run exchanges halo rows (d2q9-bgk.c:326-328,364) once per GROUP of launches: the launches lbm_plan_steps gives

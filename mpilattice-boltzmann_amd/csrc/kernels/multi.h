@@ -28,6 +28,9 @@ namespace {
 // lanes, one per lane and sub-step, so that each in-LDS sub-step is a single read / barrier / write.
 // What is not the dealing itself — the source pull, the kept / counted tests, the flag byte, the frame read,
 // the destination index — is written once at kernel scope (pull, classify, pair_flag_bits, read_pair, kept_cell).
+// K = 5 (whole periodic grids, tall geometry, plain form only) runs owned_substeps on the same tile with a 72 x 32 frame that
+// holds populations 1 - 8: population 0 of a ring pair lives in a compact array by the pair's index in sub-step 1's ring
+// (MultiGeom::compact0, ring0_at), which keeps the block at two per CU.
 //
 // Rows outside the partition: `y_periodic` wraps (self-contained domain); otherwise the storage has
 // `ghost` extra rows below and above the owned rows, filled by the neighbours before the launch.
@@ -47,14 +50,20 @@ struct MultiGeom {
   static constexpr int EY = K - 1, EX = multi_ex(K - 1);            // growth of the first sub-step
   static constexpr int W = TX + 2 * EX, H = TY + 2 * EY;            // LDS frame
   static constexpr int cells = W * H;
-  static constexpr size_t lds_bytes = sizeof(float) * 9 * cells + sizeof(double) * K * (LANES / 64) + (K >= 2 ? cells / 2 : 0);   // + a flag byte per x-pair
+  // population 0 out of the frame (the five-step launch of whole grids, lbm_geometry.h multi_compact0): planes 1 - 8, then a float pair per ring pair of sub-step 1
+  static constexpr bool compact0 = multi_compact0(K, GEOM);
+  static constexpr int planes = compact0 ? 8 : 9, first_plane = compact0 ? 1 : 0;
+  static constexpr int ring0_floats = compact0 ? 2 * multi_ring_pairs(K, GEOM, 1) : 0;
+  static constexpr size_t lds_bytes = multi_lds_bytes(K, GEOM);     // planes (+ ring pairs' population 0) + reduction scratch + a flag byte per x-pair
+  static_assert(lds_bytes == sizeof(float) * (planes * cells + ring0_floats) + sizeof(double) * K * (LANES / 64) + (K >= 2 ? cells / 2 : 0), "the kernel's layout and lbm_geometry.h agree");
+  static_assert(W == multi_frame_w(K, GEOM) && H == multi_frame_h(K, GEOM), "the frame of lbm_geometry.h");
   // waves per SIMD the kernel is compiled for: what its LDS frame lets a CU hold, LBM_MWAVES at most
   static constexpr int blocks_per_cu = lds_bytes * 8 <= 160 * 1024 ? 8 : static_cast<int>(160 * 1024 / lds_bytes);
   static constexpr int waves_per_simd = blocks_per_cu * (LANES / 64) / 4 < LBM_MWAVES ? (blocks_per_cu * (LANES / 64) / 4 < 1 ? 1 : blocks_per_cu * (LANES / 64) / 4) : LBM_MWAVES;
-  // lanes dealt one owned x-pair each for the whole launch (the tall K = 4 geometry: 32 x 24 pairs on 768 lanes; see owned_substeps)
-  static constexpr bool owned_lanes = K == 4 && GEOM == kGeomTall;
+  // lanes dealt one owned x-pair each for the whole launch (the tall geometry at K = 4 and K = 5: 32 x 24 pairs on 768 lanes; see owned_substeps)
+  static constexpr bool owned_lanes = K >= 4 && GEOM == kGeomTall;
   // x-pairs of sub-step j's region outside the owned tile: ey rows below and above it, multi_ex(ey) / 2 pairs on each side of its rows
-  static constexpr int ring_pairs(int j) { return 2 * (K - j) * (TX / 2 + multi_ex(K - j)) + TY * multi_ex(K - j); }
+  static constexpr int ring_pairs(int j) { return multi_ring_pairs(K, GEOM, j); }
 };
 
 struct MultiArgs {
@@ -169,8 +178,11 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
 {
   using G = MultiGeom<K, GEOM>;
   constexpr int TX = G::TX, EX = G::EX, EY = G::EY, W = G::W, WH = G::W / 2, kCells = G::cells, kLanes = G::LANES, kWaves = kLanes / 64, TY = G::TY;
-  extern __shared__ __attribute__((aligned(16))) float lds[];      // [9][kCells], then [K][kWaves] doubles
-  double* red = reinterpret_cast<double*>(lds + 9 * kCells);
+  // plane k of the frame is lds + (k - kPl) * kCells: nine planes from population 0, or (G::compact0) eight from population 1 and
+  // behind them ring0, population 0 of the ring pairs by their index in sub-step 1's ring
+  constexpr int kPlanes = G::planes, kPl = G::first_plane;
+  extern __shared__ __attribute__((aligned(16))) float lds[];      // [kPlanes][kCells] (+ ring0), then [K][kWaves] doubles
+  double* red = reinterpret_cast<double*>(lds + kPlanes * kCells + G::ring0_floats);
   uint8_t* pair_flags = reinterpret_cast<uint8_t*>(red + K * kWaves);   // a flag byte (kPair*) per x-pair of the frame
   const int tid = threadIdx.x;
 
@@ -342,14 +354,14 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   auto read_pair = [&](const int rd, const int fx, const int fy, f2 (&p)[9]) __attribute__((always_inline)) {
     const int ci = fy * W + fx - rd;                                   // interleaved planes: cell (fx, fy)
     const int cs = fy * W + (fx >> 1) - rd;                            // split planes: O[i] of row fy; E[i] is WH further
-    p[2] = *reinterpret_cast<const f2*>(lds + 2 * kCells + ci - W);
-    p[4] = *reinterpret_cast<const f2*>(lds + 4 * kCells + ci + W);
-    p[1] = f2{lds[1 * kCells + cs - 1], lds[1 * kCells + cs + WH]};
-    p[5] = f2{lds[5 * kCells + cs - W - 1], lds[5 * kCells + cs - W + WH]};
-    p[8] = f2{lds[8 * kCells + cs + W - 1], lds[8 * kCells + cs + W + WH]};
-    p[3] = f2{lds[3 * kCells + cs], lds[3 * kCells + cs + WH + 1]};
-    p[6] = f2{lds[6 * kCells + cs - W], lds[6 * kCells + cs - W + WH + 1]};
-    p[7] = f2{lds[7 * kCells + cs + W], lds[7 * kCells + cs + W + WH + 1]};
+    p[2] = *reinterpret_cast<const f2*>(lds + (2 - kPl) * kCells + ci - W);
+    p[4] = *reinterpret_cast<const f2*>(lds + (4 - kPl) * kCells + ci + W);
+    p[1] = f2{lds[(1 - kPl) * kCells + cs - 1], lds[(1 - kPl) * kCells + cs + WH]};
+    p[5] = f2{lds[(5 - kPl) * kCells + cs - W - 1], lds[(5 - kPl) * kCells + cs - W + WH]};
+    p[8] = f2{lds[(8 - kPl) * kCells + cs + W - 1], lds[(8 - kPl) * kCells + cs + W + WH]};
+    p[3] = f2{lds[(3 - kPl) * kCells + cs], lds[(3 - kPl) * kCells + cs + WH + 1]};
+    p[6] = f2{lds[(6 - kPl) * kCells + cs - W], lds[(6 - kPl) * kCells + cs - W + WH + 1]};
+    p[7] = f2{lds[(7 - kPl) * kCells + cs + W], lds[(7 - kPl) * kCells + cs + W + WH + 1]};
   };
   // Cell index of a kept pair in the destination grid: it lies inside the grid, so its index needs no periodic wrap.
   auto kept_cell = [&](const int fx, const int fy) __attribute__((always_inline)) { return tile_row_base + __mul24(fy - EY, nx) + x0 + fx - EX; };
@@ -462,7 +474,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   // item after the owned pass; sub-step j < K relaxes the owned pair and, on those lanes, reads one ring pair, meets at ONE barrier,
   // then relaxes the ring pair and writes both (the dealing above takes two passes for each of sub-steps 1 - 3, every pair with the
   // term code).  Each lane adds exactly one pair's term per sub-step: acc[j-1] is that term, its compensated low part already added.
-  // Plane 0 and the flag byte are kept in LDS for ring pairs only.
+  // Plane 0 and the flag byte are kept in LDS for ring pairs only (K = 5: no plane 0 at all, the ring pairs' population 0 in ring0).
   // Sub-step 1 has an interior form for tiles that are `inner` and hold no uncounted rows or columns (all but the edge tiles of a
   // launch), chosen by a block-uniform branch.  Every owned pair is then computed, kept and counted, no source wraps and no row is
   // missing, so it is two straight-line sections (the owned pair, then the ring pair of the first lanes) instead of one rolled body
@@ -487,6 +499,15 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         fy = EY + ry;
         fx = EX - ex + 2 * (c < ep ? c : c + TP);
       }
+    };
+    // G::compact0: where population 0 of the ring pair at frame position (fx, fy) lives — its index in sub-step 1's ring, the inverse of
+    // ring_pos<1> (the later rings are subsets of the first).  Only the pair at the same position ever reads it back: population 0 does not stream.
+    [[maybe_unused]] f2* const ring0 = reinterpret_cast<f2*>(lds + kPlanes * kCells);
+    [[maybe_unused]] auto ring0_at = [&](const int fx, const int fy) __attribute__((always_inline)) -> f2* {
+      constexpr int ep = EX / 2, wp = TP + ep * 2, band = EY * wp;        // sub-step 1: ey = EY, ex = EX
+      const int rp = fx >> 1;
+      const int i = fy < EY ? fy * wp + rp : fy >= EY + TY ? band + (fy - EY - TY) * wp + rp : 2 * band + (fy - EY) * (2 * ep) + (rp < ep ? rp : rp - TP);
+      return ring0 + i;
     };
     // relaxation, bounce-back and accelerate_flow of one pair; returns its sum|u| term (0 where skip = 3)
     auto relax = [&](const f2 (&p)[9], const uint32_t mbits, const bool accel, const uint32_t skip, f2 (&out)[9]) __attribute__((always_inline)) {
@@ -530,7 +551,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         const bool accel_row_here = on_accel_row(sy0 + py);
         acc[0] = relax(p, mbits, accel_row_here, mbits, out);
   #pragma unroll
-        for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, ofy * W, ofx, out[k]);
+        for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, ofy * W, ofx, out[k]);
         own0 = out[0];
         ofl = pair_flag_bits(mbits, true, accel_row_here, false);
       }
@@ -543,7 +564,8 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         const bool accel_row_here = on_accel_row(sy0 + fy - EY);
         relax(p, mbits, accel_row_here, 3u, out);
   #pragma unroll
-        for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
+        for (int k = kPl; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, fy * W, fx, out[k]);
+        if constexpr (G::compact0) ring0[tid] = out[0];
         pair_flags[(fy * W + fx) >> 1] = static_cast<uint8_t>(pair_flag_bits(mbits, false, accel_row_here, false));
       }
     } else {
@@ -564,11 +586,13 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         f2 out[9];
         const double term = relax(p, mbits, accel_row_here, counted ? mbits : 3u, out);
   #pragma unroll
-        for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, fy * W, fx, out[k]);
+        for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, fy * W, fx, out[k]);
         fl = pair_flag_bits(mbits, kept, accel_row_here, COUNT && counted);
         if (own) {
           acc[0] = term;
           own0 = out[0];
+        } else if constexpr (G::compact0) {
+          ring0[tid] = out[0];
         } else {
           store_pair<W>(lds, 0, fy * W, fx, out[0]);
         }
@@ -598,24 +622,27 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         f2 q[9];
         int rfx = 0, rfy = 0;
         uint32_t rfl = 0;
+        [[maybe_unused]] f2* r0 = nullptr;
         const bool ring = tid < G::ring_pairs(j);
         if (ring) {
           ring_pos(jc, tid, rfx, rfy);
           rfl = pair_flags[(rfy * W + rfx) >> 1];
           read_pair(rd, rfx, rfy, q);
-          q[0] = *reinterpret_cast<const f2*>(lds + rfy * W + rfx - rd);
+          if constexpr (G::compact0) { r0 = ring0_at(rfx, rfy); q[0] = *r0; }
+          else q[0] = *reinterpret_cast<const f2*>(lds + rfy * W + rfx - rd);
         }
         __syncthreads();                       // every lane has read its neighbours
         if (ofl & kPairComputed) {
   #pragma unroll
-          for (int k = 1; k < 9; ++k) store_pair<W>(lds + k * kCells, k, ofy * W - wr, ofx, outs[k]);
+          for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, ofy * W - wr, ofx, outs[k]);
         }
         if (ring) {
           f2 routs[9];
           relax(q, rfl & kPairObstacles, (rfl & kPairAccelRow) != 0u, 3u, routs);
           if (rfl & kPairComputed) {
   #pragma unroll
-            for (int k = 0; k < 9; ++k) store_pair<W>(lds + k * kCells, k, rfy * W - wr, rfx, routs[k]);
+            for (int k = kPl; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, rfy * W - wr, rfx, routs[k]);
+            if constexpr (G::compact0) *r0 = routs[0];
           }
         }
         __syncthreads();
@@ -629,6 +656,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     in_lds_substep(std::integral_constant<int, 2>{});
     if constexpr (K >= 3) in_lds_substep(std::integral_constant<int, K >= 3 ? 3 : 2>{});
     if constexpr (K >= 4) in_lds_substep(std::integral_constant<int, K >= 4 ? 4 : 2>{});
+    if constexpr (K >= 5) in_lds_substep(std::integral_constant<int, K >= 5 ? 5 : 2>{});
   };
   auto substeps = [&](auto count_c) __attribute__((always_inline)) {
     if constexpr (G::owned_lanes) owned_substeps(count_c);
@@ -653,11 +681,18 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
   if constexpr (K == 1) {
     const double w = wave_sum(acc[0]);
     if ((tid & 63) == 0) red[tid >> 6] = w;
-  } else {
-    static_assert(K <= 4, "wave_sum_vec4 carries four steps");
+  } else if constexpr (K <= 4) {
     const double w = wave_sum_vec4(acc[0], acc[1], K > 2 ? acc[2] : 0.0, K > 3 ? acc[K > 3 ? 3 : 0] : 0.0);
     const int q = wave_sum_slot<4>(tid & 63);
     if ((tid & 15) == 0 && q < K) red[q * kWaves + (tid >> 6)] = w;
+  } else {
+    static_assert(K <= 8, "wave_sum_vec8 carries eight steps");
+    double acc8[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc8[i] = i < K ? acc[i < K ? i : 0] : 0.0;
+    const double w = wave_sum_vec8(acc8);
+    const int q = wave_sum_slot<8>(tid & 63);
+    if ((tid & 7) == 0 && q < K) red[q * kWaves + (tid >> 6)] = w;
   }
   lds_barrier();                 // LDS only: the block does not wait for its own global stores to complete
   if (tid < ksteps) {

@@ -72,7 +72,8 @@ static_assert(tile64_lds_bytes(16, 8) <= 160 * 1024 && tile64_lds_bytes(8, 4) <=
 #define LBM_MLANES4T 768
 #endif
 constexpr int kMTX = 64, kMTXNarrow = 32, kMTY = LBM_MTY, kMTY4 = LBM_MTY4, kMTY4Tall = LBM_MTY4T, kMLanes = LBM_MLANES, kMLanes4Tall = LBM_MLANES4T,
-              kMaxMultiSteps = 4,
+              kMaxMultiSteps = 4,      // most steps of a launch of a partition, and of every geometry but the tall one
+              kMaxWholeGridSteps = 5,  // ... of a whole periodic grid on the tall geometry: lbm_multi_kernel<5, TERMS, kGeomTall, kPartPlain> (multi_compact0 below)
               kMaxGhost = 32,      // most ghost rows / columns a K-step partition keeps per side: the steps of a group of launches between two halo exchanges (32: column blocks)
               kMaxGroup = 8;       // most launches of such a group
 constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall) : (kMTY4 < kMTY4Tall ? kMTY4 : kMTY4Tall);
@@ -80,7 +81,10 @@ constexpr int kMinMultiTY = kMTY < kMTY4 ? (kMTY < kMTY4Tall ? kMTY : kMTY4Tall)
 //   kGeomStd     64-wide tiles.  K <= 3: 64 x 16, 512 lanes (K = 3: 68 x 20 frame, 48.7 KB, three blocks per CU).  K = 4: 64 x 13 (72 x 19 frame,
 //                49.0 KB, three blocks per CU).
 //   kGeomTall    K = 4 on 64 x 24 tiles with 768-lane blocks: 72 x 30 frame = 77.4 KB, TWO blocks of twelve waves per CU (the same 24 waves);
-//                the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.
+//                the host picks it from 2^20 cells up.  K <= 3: as kGeomStd.  K = 5 (whole periodic grids only, kMaxWholeGridSteps): the same
+//                64 x 24 tiles and 768 lanes on a 72 x 32 frame of EIGHT planes — population 0 never streams, so the owned pairs keep it in a
+//                register and the ring pairs of sub-step 1 (384) in a compact array of their own: 76.6 KB, still two blocks per CU (nine
+//                planes of 72 x 32 floats alone would be 82.9 KB).
 //   kGeomNarrow  32-wide tiles, heights as kGeomStd: partitions so small that a launch is one round of blocks (twice the tiles, each
 //                with half the dependent work — a 1024 x 128-row partition keeps 256 CUs busy instead of 128).
 // The measurements behind each choice, round by round: DESIGN_APPENDIX.md R8.1.
@@ -99,6 +103,22 @@ constexpr int geom_for(int k, int g) { return (g == kGeomTall && k < 4) ? kGeomS
 // inside the frame) and never kept or counted.  (Rounds 1 - 4 grew the columns by 2(k-j): K = 4 regions
 // 76 / 72 / 68 / 64 wide instead of 72 / 68 / 68 / 64, frames 12 columns wider than needed.)
 constexpr int multi_ex(int ey) { return 2 * ((ey + 1) / 2); }
+
+// A block's LDS, in bytes: the frame's planes, the reduction scratch (a double per step and wave) and a flag byte per x-pair of the frame.
+// The kernel (MultiGeom::lds_bytes, kernels/multi.h) and the planner (lbm_plan.cpp) read this one definition.
+// multi_compact0: the frame holds populations 1 - 8 only; population 0 of a ring pair lives in an array of one float pair per ring pair
+// of sub-step 1 (the later rings are subsets of the first), between the planes and the reduction scratch.
+constexpr bool multi_compact0(int k, int g) { return k == kMaxWholeGridSteps && g == kGeomTall; }
+constexpr int multi_frame_w(int k, int g) { return geom_tx(g) + 2 * multi_ex(k - 1); }
+constexpr int multi_frame_h(int k, int g) { return multi_ty(k, g) + 2 * (k - 1); }
+// x-pairs of sub-step j's region outside the owned tile: k - j rows below and above it, multi_ex(k - j) / 2 pairs on each side of its rows
+constexpr int multi_ring_pairs(int k, int g, int j) { return 2 * (k - j) * (geom_tx(g) / 2 + multi_ex(k - j)) + multi_ty(k, g) * multi_ex(k - j); }
+constexpr int multi_lds_bytes(int k, int g)
+{
+  const int cells = multi_frame_w(k, g) * multi_frame_h(k, g);
+  return 4 * (multi_compact0(k, g) ? 8 : 9) * cells + (multi_compact0(k, g) ? 8 * multi_ring_pairs(k, g, 1) : 0) + 8 * k * (multi_lanes(k, g) / 64) + (k >= 2 ? cells / 2 : 0);
+}
+static_assert(multi_lds_bytes(kMaxWholeGridSteps, kGeomTall) * 2 <= 160 * 1024, "two blocks of the five-step launch per CU");
 
 // ---- lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h): lbm_multi_kernel's scheme with every object a double ----
 // A block of kMulti64Lanes lanes owns a kMulti64TX x kMulti64TY tile, one owned cell per lane in the last sub-step.  The LDS frame is ONE
@@ -133,6 +153,9 @@ constexpr int kPartPlain = 0, kPartGhost = 1, kPartReady = 2, kPartTile = 3;
 constexpr int kMultiTermsFused = 3;
 constexpr int kMultiTerms = 4, kMultiParts = 4, kMultiGeoms = 3, kMultiRowsPerGeom = kMaxMultiSteps * kMultiTerms * kMultiParts;
 constexpr int multi_row(int k, int geom, int terms, int part) { return ((geom * kMaxMultiSteps + k - 1) * kMultiTerms + terms) * kMultiParts + part; }
+// ... and behind those rows the five-step launch of whole grids, tall geometry and plain form only: one row per terms index
+constexpr int kMultiRows = kMultiGeoms * kMultiRowsPerGeom, kMultiRowsTotal = kMultiRows + kMultiTerms;
+constexpr int multi_row5(int terms) { return kMultiRows + terms; }
 // lbm_tile_kernel: one row per (geometry, FULL, terms).  The terms index of a row: double-precision sum|u| terms, float ones
 // (LBM_FLAG_FAST_AVVELS), the fused arithmetic (LBM_FLAG_FUSED_ARITH; never with the float terms: plan_context).
 constexpr int kTileTermsFused = 2, kTileTerms = 3, kTileRows = 4 * 2 * kTileTerms;

@@ -201,6 +201,7 @@ extern "C" int lbm_plan_kernel_name(const lbm_internal::ContextPlan* plan, char*
 // One launch of a context of that plan, and every step-kernel launch of a run of n_steps in the order a serial-schedule run enqueues them
 // (schedule kScheduleSerial: each launch over all its tiles; kScheduleEdge: the first launch of a group as interior + edge, adjacent) —
 // lbm_run, the split-phase calls and the peer-to-peer loop alike.  Returns the number of launches (the first `cap` are written), -1 on a bad argument.
+extern "C" int lbm_plan_multi_lds_bytes(int k, int geom);   // a block's dynamic LDS in a launch of k steps on that geometry (-1: not built)
 extern "C" int lbm_plan_launch_sizeof(void);
 extern "C" int lbm_plan_launch(const lbm_internal::ContextPlan* plan, int k, int ext, int which, int says_ready, lbm_internal::LaunchPlan* out);
 extern "C" int lbm_plan_run_launches(const lbm_internal::ContextPlan* plan, int n_steps, int schedule, lbm_internal::LaunchPlan* out, int cap);

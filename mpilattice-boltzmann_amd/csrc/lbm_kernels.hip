@@ -245,9 +245,22 @@ constexpr MultiKernel multi_kernel_row()
   static_assert(MultiGeom<K, GEOM>::LANES == multi_lanes(K, ROW / kMultiRowsPerGeom), "LaunchPlan::lanes is the row's block size");
   return {&lbm_multi_kernel<K, TERMS == kMultiTermsFused ? (kTermsCompensated | kTermsFused) : TERMS, GEOM, PART>, MultiGeom<K, GEOM>::lds_bytes};
 }
+// ... and behind them (multi_row5) the five-step launch of whole grids: tall geometry, plain form, one row per terms index.
+template <int TERMS>
+constexpr MultiKernel multi_kernel_row5()
+{
+  using G = MultiGeom<kMaxWholeGridSteps, kGeomTall>;
+  static_assert(G::LANES == multi_lanes(kMaxWholeGridSteps, kGeomTall) && G::owned_lanes && G::compact0, "the tall tile, one owned pair per lane, population 0 out of the frame");
+  return {&lbm_multi_kernel<kMaxWholeGridSteps, TERMS == kMultiTermsFused ? (kTermsCompensated | kTermsFused) : TERMS, kGeomTall, kPartPlain>, G::lds_bytes};
+}
 template <size_t... ROW>
-constexpr std::array<MultiKernel, sizeof...(ROW)> multi_kernel_rows(std::index_sequence<ROW...>) { return {{multi_kernel_row<static_cast<int>(ROW)>()...}}; }
-constexpr auto kMultiKernels = multi_kernel_rows(std::make_index_sequence<kMultiGeoms * kMultiRowsPerGeom>{});
+constexpr std::array<MultiKernel, sizeof...(ROW) + kMultiTerms> multi_kernel_rows(std::index_sequence<ROW...>)
+{
+  static_assert(kMultiTerms == 4 && multi_row5(3) == sizeof...(ROW) + 3, "the four rows below");
+  return {{multi_kernel_row<static_cast<int>(ROW)>()..., multi_kernel_row5<0>(), multi_kernel_row5<1>(), multi_kernel_row5<2>(), multi_kernel_row5<3>()}};
+}
+constexpr auto kMultiKernels = multi_kernel_rows(std::make_index_sequence<kMultiRows>{});
+static_assert(kMultiKernels.size() == kMultiRowsTotal, "every row a LaunchPlan can name");
 
 // Kernels whose dynamic LDS is above the default limit (lbm_multi_kernel's tall geometry: 79 KB; lbm_tile_kernel<16, 8>: 74 KB) need the limit
 // raised — per DEVICE (a function attribute belongs to the device's copy of the code object): called from lbm_create on the context's
@@ -264,7 +277,35 @@ hipError_t raise_lds_limits(const Table& rows, int first, int end)
 }
 hipError_t raise_multi_lds_limits_for(int geom)          // every instantiation a context of this geometry may launch (K = 3 tails of the tall one: standard)
 {
-  return raise_lds_limits(kMultiKernels, geom * kMultiRowsPerGeom, (geom + 1) * kMultiRowsPerGeom);
+  const hipError_t e = raise_lds_limits(kMultiKernels, geom * kMultiRowsPerGeom, (geom + 1) * kMultiRowsPerGeom);
+  if (e != hipSuccess || geom != kGeomTall) return e;
+  return raise_lds_limits(kMultiKernels, kMultiRows, kMultiRowsTotal);   // the five-step launch of whole grids
+}
+
+// Does the device hold two blocks of the five-step launch per CU ?  Its 76.6 KB of LDS are sized for exactly that (lbm_geometry.h); a
+// device whose LDS allocation rounds them past half a CU's would run one block of twelve waves per CU, at which the four-step launch is
+// the faster form.  Asked once per context that plans the form (lbm_create / lbm_create_global), with the context's device current.
+bool five_step_launch_fits(int terms_row)
+{
+  const MultiKernel& k = kMultiKernels[multi_row5(terms_row)];
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(k.fn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(k.lds_bytes)) != hipSuccess) { (void)hipGetLastError(); return false; }
+  int blocks = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, reinterpret_cast<const void*>(k.fn), multi_lanes(kMaxWholeGridSteps, kGeomTall), k.lds_bytes) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return blocks >= 2;
+}
+
+// A whole-grid plan that names the five-step launch holds only if the device fits it twice per CU; otherwise the context is planned again
+// as LBM_TUNE_MULTI_K=4 would plan it.
+int plan_whole_on_device(const Knobs& knobs, const lbm_params* p, int free_cells, int y0, int ny_local, unsigned flags, bool has_global_map, int device,
+                         lbm_internal::ContextPlan* plan)
+{
+  const int status = lbm_internal::plan_whole(knobs, p, free_cells, y0, ny_local, flags, has_global_map, plan);
+  if (status != lbm_internal::kPlanOk || plan->multi_K != kMaxWholeGridSteps) return status;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return status; }          // create_impl reports a bad device
+  if (five_step_launch_fits(plan->fused ? kMultiTermsFused : plan->multi_terms)) return status;
+  Knobs four = knobs;
+  four.multi_k = kMaxMultiSteps;
+  return lbm_internal::plan_whole(four, p, free_cells, y0, ny_local, flags, has_global_map, plan);
 }
 
 using lbm_internal::LaunchPlan;
@@ -573,7 +614,7 @@ int lbm_create(lbm_ctx** out, const lbm_params* p, int free_cells, const int* ob
   *out = nullptr;
   const Knobs knobs = knobs_from_env();
   lbm_internal::ContextPlan plan;
-  const int status = lbm_internal::plan_whole(knobs, p, free_cells, y0, ny_local, flags, false, &plan);
+  const int status = plan_whole_on_device(knobs, p, free_cells, y0, ny_local, flags, false, device, &plan);
   return create_impl(out, status, plan, knobs, p, free_cells, obstacles_rows, nullptr, nullptr, device);
 }
 
@@ -585,7 +626,7 @@ int lbm_create_global(lbm_ctx** out, const lbm_params* p, int free_cells, const 
   *out = nullptr;
   const Knobs knobs = knobs_from_env();
   lbm_internal::ContextPlan plan;
-  const int status = lbm_internal::plan_whole(knobs, p, free_cells, y0, ny_local, flags, true, &plan);
+  const int status = plan_whole_on_device(knobs, p, free_cells, y0, ny_local, flags, true, device, &plan);
   return create_impl(out, status, plan, knobs, p, free_cells, obstacles_all + static_cast<size_t>(y0) * p->nx, obstacles_all, nullptr, device);
 }
 

@@ -33,6 +33,7 @@ inline int knob_or(int v, int fallback) { return v == kKnobUnset ? fallback : v;
   X(LBM_TUNE_MULTI64_K,         multi64_k,         kKnobUnset, std::atoi)                   \
   X(LBM_TUNE_MULTI64_MIN,       multi64_min,       1 << 20,    std::atoi)                   \
   X(LBM_TUNE_MULTI_K,           multi_k,           kKnobUnset, std::atoi)                   \
+  X(LBM_TUNE_MULTI5_MIN,        multi5_min,        1 << 26,    std::atoi)                   \
   X(LBM_TUNE_MULTI_TAIL4,       multi_tail4,       1,          std::atoi)                   \
   X(LBM_TUNE_MULTI_TILE,        multi_tile,        kKnobUnset, std::atoi)                   \
   X(LBM_TUNE_NARROW_TILE_MAX,   narrow_tile_max,   1 << 17,    std::atoi)                   \

@@ -245,7 +245,16 @@ void plan_multi(const Knobs& knobs, bool tile_rank, ContextPlan& c)
   }
   c.multi_tx = geom_tx(c.multi_geom);
   c.multi_tiles_x = (c.nx + c.multi_tx - 1) / c.multi_tx;
-  if (c.multi_K > 0) c.partials_cap = std::max(c.partials_cap, kMaxMultiSteps * c.multi_tiles_x * ((c.nyl + 2 * c.ghost_rows + kMinMultiTY - 1) / kMinMultiTY) + 1);
+  // (a context of the five-step launch: five vectors, over the tiles of its shortest tail's geometry)
+  const int vecs = c.multi_K > kMaxMultiSteps ? c.multi_K : kMaxMultiSteps;
+  if (c.multi_K > 0) c.partials_cap = std::max(c.partials_cap, vecs * c.multi_tiles_x * ((c.nyl + 2 * c.ghost_rows + kMinMultiTY - 1) / kMinMultiTY) + 1);
+}
+
+// Five steps per launch (lbm_multi_kernel<5, TERMS, kGeomTall, kPartPlain>, lbm_geometry.h kMaxWholeGridSteps) is built for whole periodic
+// grids on the tall geometry only: no ghost rows to advance, no ready words, no ghost columns.
+bool five_steps_eligible(const ContextPlan& c, unsigned flags)
+{
+  return c.self_periodic && c.ghost == 0 && c.ghost_x == 0 && !c.tile_kernel && !(flags & LBM_FLAG_ONE_STEP) && c.multi_geom == kGeomTall;
 }
 
 // The one function that decides: lbm_create / lbm_create_global / lbm_create_rank / lbm_create_tile all end here.  The obstacle flags of
@@ -386,7 +395,13 @@ int plan_context(const Knobs& knobs, const lbm_params* p, int free_cells, bool h
     // round 3, 4-step launch on 64 x 13 tiles: K = 3 / K = 4 8192x8192 346.6 / 324.0, 4096x4096 87.2 / 78.4, 2048x2048 24.0 / 21.6,
     // 1536x1536 14.2 / 13.8, 1024x1024 8.16 / 7.07, 768x768 5.39 / 4.63, 1024x512 4.51 / 4.72, 512x1024 4.39 / 4.62, 640x640 4.01 / 4.13,
     // 512x512 3.11 / 3.45 -> K = 4 from 768 x 768 cells up (profiles/r03/ab_k3_k4.txt, ab_k3_k4_threshold.txt)
-    c.multi_K = std::min(std::max(knob_or(knobs.multi_k, ncells >= size_t(768) * 768 ? 4 : 3), 0), kMaxMultiSteps);
+    // K = 5 (five_steps_eligible: whole grids on the tall geometry; population 0 out of the LDS frame keeps two blocks per CU): the default from
+    // LBM_TUNE_MULTI5_MIN cells up, the measurements behind that number in DESIGN.md section 4.2 (profiles/r15); LBM_TUNE_MULTI_K=5 asks for it at any
+    // eligible size and falls back to 4 elsewhere.
+    c.multi_geom = pick_geom(knobs, ncells);                  // (plan_multi's choice for a whole grid)
+    const bool five_ok = five_steps_eligible(c, flags);
+    const int by_size = (five_ok && knobs.multi5_min > 0 && ncells >= static_cast<size_t>(knobs.multi5_min)) ? kMaxWholeGridSteps : ncells >= size_t(768) * 768 ? 4 : 3;
+    c.multi_K = std::min(std::max(knob_or(knobs.multi_k, by_size), 0), five_ok ? kMaxWholeGridSteps : kMaxMultiSteps);
     plan_multi(knobs, false, c);
   } else if (c.tile_kernel) {
     c.partials_cap = std::max(c.partials_cap, kMaxTileSteps * c.n_tiles + 1);
@@ -703,6 +718,10 @@ void plan_launch(const ContextPlan& c, const Knobs& knobs, int k, int ext, int w
   const int steps = std::min(k, static_cast<int>(kMaxMultiSteps));       // k <= multi_K, or 4 in the tail of a K = 3 run (next_multi_k)
   a.row = multi_row(steps, c.multi_geom, c.fused ? kMultiTermsFused : c.multi_terms, a.part);
   a.lanes = multi_lanes(steps, c.multi_geom);
+  if (k == kMaxWholeGridSteps && c.multi_K == kMaxWholeGridSteps) {      // the five-step launch of a whole grid (five_steps_eligible: tall, plain): its own rows
+    a.row = multi_row5(c.fused ? kMultiTermsFused : c.multi_terms);
+    a.lanes = multi_lanes(k, c.multi_geom);
+  }
   *out = a;
 }
 
@@ -750,6 +769,9 @@ int lbm_plan_next(int K, int four_rows, int tail4, int left)
   if (!four_rows || !tail4) return k;
   if (K == 3 && ((left % 3 == 1 && left >= 4) || (left % 3 == 2 && left >= 8))) k = 4;
   if (K == 4 && ((left % 4 == 3) || (left % 4 == 2 && left >= 6) || (left % 4 == 1 && left >= 9))) k = 3;
+  // K = 5 (whole grids): 5s for as long as what they leave is 0 or at least 3, then 4 + 3 or 3 + 3 — ceil(left / 5) launches, the fewest
+  // that 5s, 4s and 3s can make, and none shorter than 3 (11 = 5 + 3 + 3, 12 = 5 + 4 + 3, 7 = 4 + 3, 6 = 3 + 3)
+  if (K == 5 && left >= 3) k = (left == 5 || left >= 8) ? 5 : left == 7 ? 4 : left == 6 ? 3 : left;
   return k;
 }
 
@@ -859,10 +881,17 @@ int lbm_plan_kernel_name(const ContextPlan* plan, char* kernel_name, size_t len)
   return 0;
 }
 
+// A block's dynamic LDS in a launch of k steps on geometry `geom` (lbm_geometry.h multi_lds_bytes, which the kernels are sized by); -1: not built.
+int lbm_plan_multi_lds_bytes(int k, int geom)
+{
+  if (geom < kGeomStd || geom > kGeomTall || k < 1 || k > (geom == kGeomTall ? kMaxWholeGridSteps : kMaxMultiSteps)) return -1;
+  return multi_lds_bytes(k, geom_for(k, geom));
+}
+
 int lbm_plan_launch_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::LaunchPlan)); }
 int lbm_plan_launch(const ContextPlan* plan, int k, int ext, int which, int says_ready, lbm_internal::LaunchPlan* out)
 {
-  if (!plan || !out || plan->multi_tiles_x <= 0 || k < 1 || k > kMaxMultiSteps || ext < 0 || ext > kMaxGhost || which < lbm_internal::kLaunchWhole || which > lbm_internal::kLaunchEdge) {
+  if (!plan || !out || plan->multi_tiles_x <= 0 || k < 1 || k > (plan->multi_K == kMaxWholeGridSteps ? kMaxWholeGridSteps : kMaxMultiSteps) || ext < 0 || ext > kMaxGhost || which < lbm_internal::kLaunchWhole || which > lbm_internal::kLaunchEdge) {
     set_error("lbm_plan_launch: bad argument");
     return 1;
   }
