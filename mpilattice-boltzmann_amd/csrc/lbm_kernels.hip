@@ -49,6 +49,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_internal.h"
+#include "lbm_hip_try.h"
 #include "lbm_knobs.h"
 #include "kernels/common.h"
 #include "kernels/step.h"
@@ -62,16 +63,6 @@ namespace {
 // ------------------------------------------------------------------------------------------------
 // host side of the device ABI
 // ------------------------------------------------------------------------------------------------
-
-// A failed HIP call leaves "<the call as written>: <HIP's words>" in lbm_last_error() and takes the exit `on_fail` (HIP_TRY: return 1).
-// (Both stringify their own argument: passed on through another macro, constants that are macros themselves would be spelled out.)
-bool hip_failed(hipError_t e, const char* call)
-{
-  if (e != hipSuccess) lbm_internal::set_error(std::string(call) + ": " + hipGetErrorString(e));
-  return e != hipSuccess;
-}
-#define HIP_TRY_OR(expr, on_fail) do { if (hip_failed((expr), #expr)) { on_fail; } } while (0)
-#define HIP_TRY(expr) do { if (hip_failed((expr), #expr)) return 1; } while (0)
 
 size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 

@@ -29,6 +29,7 @@
 
 #include "lbm_d2q9_rccl.h"
 #include "lbm_internal.h"
+#include "lbm_hip_try.h"
 #include "lbm_knobs.h"
 
 struct lbm_comm {
@@ -46,15 +47,6 @@ struct lbm_comm {
   bool three_queues = true;        // edge rows on their own stream beside the interior kernel; LBM_RCCL_SCHEDULE=serial
                                    // puts them on the compute stream after the interior kernel instead
 };
-
-#define HIP_TRY(expr)                                                                    \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) {                                                              \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));        \
-      return 1;                                                                          \
-    }                                                                                    \
-  } while (0)
 
 #define NCCL_TRY(expr)                                                                   \
   do {                                                                                   \

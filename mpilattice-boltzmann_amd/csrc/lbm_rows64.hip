@@ -1,7 +1,7 @@
 // lbm_rows64.hip — row-partitioned runs of the double-precision mode: the entry points of include/lbm_d2q9_f64_rows.h and, through
 // kernels/rows64.h, their gfx950 kernels.  A translation unit of its own: the code objects of lbm_kernels.hip and lbm_f64.hip do not
 // change with it.  What each rank gets is decided in lbm_plan.cpp (PlanRows64, lbm_internal.h); this unit allocates and launches by
-// the plans.
+// the plans.  A rank's device state and its read-outs are lbm_f64.hip's for a whole grid: the Slab64 of lbm_f64_slab.h.
 //
 // One lbm_rows64 holds every rank of a run and one host thread drives it.  Rank r owns the rows lbm_decompose gives it, on its device,
 // as two grids of ny_local + 2 storage rows (kernels/rows64.h has the layout), with a stream of its own and two "pushed" events.
@@ -43,32 +43,14 @@
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 #include "kernels/rows64.h"
+#include "lbm_f64_slab.h"
 
 namespace {
 
-#define HIP_TRY(expr)                                                                        \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return 1;                                                                              \
-    }                                                                                        \
-  } while (0)
-
 struct Rank64 {
   lbm_internal::PlanRows64 plan{};   // written once (lbm_plan.cpp plan64_rows)
-  int device = 0;
-  size_t ncells = 0, ps = 0;                 // owned cells; plane stride
-  double* grid_alloc[2] = {nullptr, nullptr};
-  double* grid[2] = {nullptr, nullptr};      // plane 0 STORAGE row 0 (after the front guard)
-  uint32_t* mask = nullptr;
-  double* partials[2] = {nullptr, nullptr};
-  double* sums = nullptr;
-  int sums_cap = 0;
-  int* counter = nullptr;
-  hipStream_t stream = nullptr;
+  Slab64 slab;                       // the rank's row block on its device (lbm_f64_slab.h): grid[g] is plane 0 STORAGE row 0, the owned cells start one row on
   hipEvent_t pushed[2] = {nullptr, nullptr}; // this rank's push of step t has finished: pushed[t & 1]
-  hipEvent_t ev_begin = nullptr, ev_end = nullptr;
   std::vector<double> host_sums;
 };
 
@@ -106,48 +88,29 @@ int use_device(lbm_rows64* c, int device)
   return 0;
 }
 
-int ensure_sums(Rank64& k, int n, int max_iters)
-{
-  if (n <= k.sums_cap) return 0;
-  n = std::max(n, std::max(max_iters, 4096));
-  double* dev = nullptr;
-  HIP_TRY(hipMalloc(&dev, sizeof(double) * static_cast<size_t>(n)));
-  if (k.sums) (void)hipFree(k.sums);         // between runs: the stream is idle
-  k.sums = dev;
-  k.sums_cap = n;
-  return 0;
-}
-
-// cells of whole rows that the chunked copies (cells, observables) move at a time
-size_t chunk_cells(const lbm_rows64* c, const Rank64& k)
-{
-  const size_t nx = static_cast<size_t>(c->p.nx);
-  return std::min(k.ncells, std::max<size_t>(1, static_cast<size_t>(std::max(c->knobs.obs_chunk_cells, 1)) / nx) * nx);
-}
-
-// The first owned cell of a rank's grid: storage row 1.
-double* owned(const lbm_rows64* c, const Rank64& k, int g) { return k.grid[g] + c->p.nx; }
-
 // Rank r's push of grid `g`: its edge rows into the ghost rows of the neighbours' grid `g`.
 int enqueue_push(lbm_rows64* c, int r, int g)
 {
-  Rank64& k = c->ranks[r];
+  const Rank64& k = c->ranks[r];
   const Rank64& down = c->ranks[(r + c->nranks - 1) % c->nranks];
   const Rank64& up = c->ranks[(r + 1) % c->nranks];
   RowsPush64Args a{};
-  a.grid = k.grid[g];
-  a.ps = k.ps;
+  a.grid = k.slab.grid[g];
+  a.ps = k.slab.ps;
   a.nx = static_cast<uint32_t>(c->p.nx); a.nyl = static_cast<uint32_t>(k.plan.ny_local);
-  a.down = down.grid[g]; a.down_ps = down.ps; a.down_nyl = static_cast<uint32_t>(down.plan.ny_local);
-  a.up = up.grid[g]; a.up_ps = up.ps;
+  a.down = down.slab.grid[g]; a.down_ps = down.slab.ps; a.down_nyl = static_cast<uint32_t>(down.plan.ny_local);
+  a.up = up.slab.grid[g]; a.up_ps = up.slab.ps;
   const bool wide = k.plan.lane_cells == kPairCells;
   const unsigned accesses = 6u * (a.nx / (wide ? kPairCells : 1));
   const dim3 blocks((accesses + kBlock - 1) / kBlock);
-  if (wide) lbm64_push_rows_kernel<true><<<blocks, dim3(kBlock), 0, k.stream>>>(a);
-  else lbm64_push_rows_kernel<false><<<blocks, dim3(kBlock), 0, k.stream>>>(a);
+  if (wide) lbm64_push_rows_kernel<true><<<blocks, dim3(kBlock), 0, k.slab.stream>>>(a);
+  else lbm64_push_rows_kernel<false><<<blocks, dim3(kBlock), 0, k.slab.stream>>>(a);
   HIP_TRY(hipGetLastError());
   return 0;
 }
+
+// The whole grid's index of a rank's first owned cell.
+size_t first_cell(const lbm_rows64* c, const Rank64& k) { return static_cast<size_t>(k.plan.y0) * c->p.nx; }
 
 }  // namespace
 
@@ -158,23 +121,16 @@ int lbm_rows64_abi_version(void) { return LBM_ROWS64_ABI_VERSION; }
 int lbm_rows64_destroy(lbm_rows64* c)
 {
   if (!c) return 0;
-  for (Rank64& k : c->ranks) {
-    if (!k.stream && !k.grid_alloc[0]) continue;             // never reached its device
-    (void)hipSetDevice(k.device);
-    if (k.stream) (void)hipStreamSynchronize(k.stream);
+  for (Rank64& k : c->ranks) {                 // every stream first: a rank's last push stores into its neighbours' grids
+    if (!k.slab.stream) continue;              // never reached its device
+    (void)hipSetDevice(k.slab.device);
+    (void)hipStreamSynchronize(k.slab.stream);
   }
   for (Rank64& k : c->ranks) {
-    if (!k.stream && !k.grid_alloc[0]) continue;
-    (void)hipSetDevice(k.device);
-    for (int g = 0; g < 2; ++g) if (k.grid_alloc[g]) (void)hipFree(k.grid_alloc[g]);
-    if (k.mask) (void)hipFree(k.mask);
-    for (int i = 0; i < 2; ++i) if (k.partials[i]) (void)hipFree(k.partials[i]);
-    if (k.sums) (void)hipFree(k.sums);
-    if (k.counter) (void)hipFree(k.counter);
+    if (!k.slab.stream) continue;
+    (void)hipSetDevice(k.slab.device);
     for (int i = 0; i < 2; ++i) if (k.pushed[i]) (void)hipEventDestroy(k.pushed[i]);
-    if (k.ev_begin) (void)hipEventDestroy(k.ev_begin);
-    if (k.ev_end) (void)hipEventDestroy(k.ev_end);
-    if (k.stream) (void)hipStreamDestroy(k.stream);
+    slab64_destroy(k.slab);
   }
   delete c;
   return 0;
@@ -203,43 +159,35 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
     if (lbm_internal::plan64_rows(knobs, p, nranks, r, flags, &k.plan)) return fail();
-    k.ncells = static_cast<size_t>(p->nx) * k.plan.ny_local;
-    k.ps = static_cast<size_t>(k.plan.ps);
+    k.slab.ncells = static_cast<size_t>(p->nx) * k.plan.ny_local;
+    k.slab.first = static_cast<size_t>(p->nx);                 // storage row 1
+    k.slab.ps = static_cast<size_t>(k.plan.ps);
   }
-#define HIP_TRY_C(expr)                                                                      \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess) {                                                                  \
-      lbm_internal::set_error(std::string(#expr) + ": " + hipGetErrorString(e_));            \
-      return fail();                                                                         \
-    }                                                                                        \
-  } while (0)
-
   if (devices) {
-    for (int r = 0; r < nranks; ++r) c->ranks[r].device = devices[r];
+    for (int r = 0; r < nranks; ++r) c->ranks[r].slab.device = devices[r];
   } else {
     int count = 0;
-    HIP_TRY_C(hipGetDeviceCount(&count));
+    HIP_TRY_OR(hipGetDeviceCount(&count), return fail());
     if (count < 1) { lbm_internal::set_error("lbm_rows64_create: no GPU"); return fail(); }
-    for (int r = 0; r < nranks; ++r) c->ranks[r].device = r % count;
+    for (int r = 0; r < nranks; ++r) c->ranks[r].slab.device = r % count;
   }
   for (int r = 0; r < nranks; ++r) {
-    const int device = c->ranks[r].device;
-    HIP_TRY_C(hipSetDevice(device));
+    const int device = c->ranks[r].slab.device;
+    HIP_TRY_OR(hipSetDevice(device), return fail());
   }
   // neighbours on distinct devices store into each other's grids: peer access, both ways
   for (int r = 0; r < nranks; ++r) {
-    const int a = c->ranks[r].device, b = c->ranks[(r + 1) % nranks].device;
+    const int a = c->ranks[r].slab.device, b = c->ranks[(r + 1) % nranks].slab.device;
     if (a == b) continue;
     for (int way = 0; way < 2; ++way) {
       const int from = way ? b : a, to = way ? a : b;
       int can = 0;
-      HIP_TRY_C(hipDeviceCanAccessPeer(&can, from, to));
+      HIP_TRY_OR(hipDeviceCanAccessPeer(&can, from, to), return fail());
       if (!can) {
         lbm_internal::set_error("lbm_rows64_create: device " + std::to_string(from) + " cannot access device " + std::to_string(to) + " (hipDeviceCanAccessPeer): the ranks' edge rows travel as peer-to-peer stores");
         return fail();
       }
-      HIP_TRY_C(hipSetDevice(from));
+      HIP_TRY_OR(hipSetDevice(from), return fail());
       const hipError_t e = hipDeviceEnablePeerAccess(to, 0);
       if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) {
         lbm_internal::set_error(std::string("hipDeviceEnablePeerAccess: ") + hipGetErrorString(e));
@@ -248,42 +196,19 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
       (void)hipGetLastError();
     }
   }
-  const double w0 = p->density * 4.0 / 9.0, w1 = p->density / 9.0, w2 = p->density / 36.0;   // d2q9-bgk.c:880-882
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
     const lbm_internal::PlanRows64& plan = k.plan;
-    HIP_TRY_C(hipSetDevice(k.device));
-    HIP_TRY_C(hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) HIP_TRY_C(hipEventCreateWithFlags(&k.pushed[i], hipEventDisableTiming));
-    HIP_TRY_C(hipEventCreate(&k.ev_begin));
-    HIP_TRY_C(hipEventCreate(&k.ev_end));
-    for (int g = 0; g < 2; ++g) {
-      HIP_TRY_C(hipMalloc(&k.grid_alloc[g], sizeof(double) * static_cast<size_t>(plan.grid_doubles)));
-      HIP_TRY_C(hipMemsetAsync(k.grid_alloc[g], 0, sizeof(double) * static_cast<size_t>(plan.grid_doubles), k.stream));
-      k.grid[g] = k.grid_alloc[g] + 64;
-    }
-    {
-      // obstacle bitfield of the owned rows: bit c of the owned-cell index
-      std::vector<uint32_t> bits(static_cast<size_t>(plan.mask_words), 0u);
-      const int* mine = obstacles + static_cast<size_t>(plan.y0) * p->nx;
-      for (size_t i = 0; i < k.ncells; ++i)
-        if (mine[i]) bits[i >> 5] |= 1u << (i & 31);
-      HIP_TRY_C(hipMalloc(&k.mask, sizeof(uint32_t) * bits.size()));
-      HIP_TRY_C(hipMemcpy(k.mask, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice));
-    }
-    for (int i = 0; i < 2; ++i) HIP_TRY_C(hipMalloc(&k.partials[i], sizeof(double) * static_cast<size_t>(plan.partials_cap)));
-    HIP_TRY_C(hipMalloc(&k.counter, sizeof(int)));
-    HIP_TRY_C(hipMemsetAsync(k.counter, 0, sizeof(int), k.stream));
-    if (ensure_sums(k, 1, p->max_iters)) return fail();
-    const unsigned blocks = static_cast<unsigned>((k.ncells + 255) / 256);
-    hipLaunchKernelGGL(lbm64_init_kernel, dim3(blocks), dim3(256), 0, k.stream, owned(c, k, 0), k.ps, k.ncells, w0, w1, w2);
-    HIP_TRY_C(hipGetLastError());
+    HIP_TRY_OR(hipSetDevice(k.slab.device), return fail());
+    if (slab64_create(k.slab, static_cast<size_t>(plan.grid_doubles), static_cast<size_t>(plan.mask_words), static_cast<size_t>(plan.partials_cap),
+                      obstacles + first_cell(c, k), p->density, p->max_iters))
+      return fail();
+    for (int i = 0; i < 2; ++i) HIP_TRY_OR(hipEventCreateWithFlags(&k.pushed[i], hipEventDisableTiming), return fail());
   }
   for (int r = 0; r < nranks; ++r) {
-    HIP_TRY_C(hipSetDevice(c->ranks[r].device));
-    HIP_TRY_C(hipStreamSynchronize(c->ranks[r].stream));
+    HIP_TRY_OR(hipSetDevice(c->ranks[r].slab.device), return fail());
+    HIP_TRY_OR(hipStreamSynchronize(c->ranks[r].slab.stream), return fail());
   }
-#undef HIP_TRY_C
   *out = c;
   return 0;
 }
@@ -297,76 +222,79 @@ int lbm_rows64_run(lbm_rows64* c, int n_steps, double* av_vels)
   const int nranks = c->nranks;
   const uint32_t nx = static_cast<uint32_t>(c->p.nx);
   for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
-    if (ensure_sums(k, n_steps, c->p.max_iters)) return 1;
+    if (use_device(c, k.slab.device)) return 1;
+    if (slab64_ensure_sums(k.slab, n_steps, c->p.max_iters)) return 1;
   }
   {
     // accelerate_flow of the first step (d2q9-bgk.c:345-348) on the rank that owns row ny-2: every later one is the epilogue of the step before it
-    Rank64& k = c->ranks[c->ranks[0].plan.accel_rank];
-    if (use_device(c, k.device)) return 1;
-    hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, k.stream, owned(c, k, c->cur), k.ps, k.mask, nx,
+    const Rank64& k = c->ranks[c->ranks[0].plan.accel_rank];
+    const Slab64& s = k.slab;
+    if (use_device(c, s.device)) return 1;
+    hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, s.stream, s.owned(c->cur), s.ps, s.mask, nx,
                        static_cast<uint32_t>(k.plan.accel_row), c->accel_w1, c->accel_w2);
     HIP_TRY(hipGetLastError());
   }
   // push -1: the current grid's edge rows into the neighbours' ghost rows (all ranks are idle: the last call synchronised them)
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
-    if (use_device(c, k.device)) return 1;
+    if (use_device(c, k.slab.device)) return 1;
     if (enqueue_push(c, r, c->cur)) return 1;
-    HIP_TRY(hipEventRecord(k.pushed[1], k.stream));
+    HIP_TRY(hipEventRecord(k.pushed[1], k.slab.stream));
   }
   int parity = 0;
   for (int t = 0; t < n_steps; ++t) {
     const int before = (t + 1) & 1, now = t & 1;            // the pushed events of step t-1 and of step t
     for (int r = 0; r < nranks; ++r) {
       Rank64& k = c->ranks[r];
+      const Slab64& s = k.slab;
       const lbm_internal::PlanRows64& plan = k.plan;
       const int down = (r + nranks - 1) % nranks, up = (r + 1) % nranks;
-      if (use_device(c, k.device)) return 1;
-      if (down != r) HIP_TRY(hipStreamWaitEvent(k.stream, c->ranks[down].pushed[before], 0));
-      if (up != r && up != down) HIP_TRY(hipStreamWaitEvent(k.stream, c->ranks[up].pushed[before], 0));
-      if (t == 0) HIP_TRY(hipEventRecord(k.ev_begin, k.stream));
+      if (use_device(c, s.device)) return 1;
+      if (down != r) HIP_TRY(hipStreamWaitEvent(s.stream, c->ranks[down].pushed[before], 0));
+      if (up != r && up != down) HIP_TRY(hipStreamWaitEvent(s.stream, c->ranks[up].pushed[before], 0));
+      if (t == 0) HIP_TRY(hipEventRecord(s.ev_begin, s.stream));
       RowsStep64Args a{};
-      a.src = k.grid[c->cur];
-      a.dst = k.grid[c->cur ^ 1];
-      a.mask = k.mask;
-      a.ps = k.ps;
+      a.src = s.grid[c->cur];
+      a.dst = s.grid[c->cur ^ 1];
+      a.mask = s.mask;
+      a.ps = s.ps;
       a.nx = nx;
       a.units = plan.units;
       a.iters = plan.iters;
       a.omega = c->p.omega;
       a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
       a.accel_row = (r == plan.accel_rank && t + 1 < n_steps) ? plan.accel_row : -1;
-      a.partials_out = k.partials[parity];
-      a.prev_partials = k.partials[parity ^ 1];
+      a.partials_out = s.partials[parity];
+      a.prev_partials = s.partials[parity ^ 1];
       a.n_prev = t > 0 ? plan.blocks : 0;
-      a.sums = k.sums;
-      a.counter = k.counter;
-      kRows64Kernels[plan.lane_cells == 1][plan.nt_stores]<<<dim3(plan.blocks + 1), dim3(kBlock), 0, k.stream>>>(a);   // + the fold block
+      a.sums = s.sums;
+      a.counter = s.counter;
+      kRows64Kernels[plan.lane_cells == 1][plan.nt_stores]<<<dim3(plan.blocks + 1), dim3(kBlock), 0, s.stream>>>(a);   // + the fold block
       HIP_TRY(hipGetLastError());
       if (enqueue_push(c, r, c->cur ^ 1)) return 1;
-      HIP_TRY(hipEventRecord(k.pushed[now], k.stream));
+      HIP_TRY(hipEventRecord(k.pushed[now], s.stream));
     }
     parity ^= 1;
     c->cur ^= 1;
   }
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
-    if (use_device(c, k.device)) return 1;
-    HIP_TRY(hipEventRecord(k.ev_end, k.stream));
-    hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, k.stream, k.partials[parity ^ 1], k.plan.blocks, 1, k.sums, k.counter);
+    const Slab64& s = k.slab;
+    if (use_device(c, s.device)) return 1;
+    HIP_TRY(hipEventRecord(s.ev_end, s.stream));
+    hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, s.stream, s.partials[parity ^ 1], k.plan.blocks, 1, s.sums, s.counter);
     HIP_TRY(hipGetLastError());
     if (av_vels) {
       k.host_sums.resize(static_cast<size_t>(n_steps));
-      HIP_TRY(hipMemcpyAsync(k.host_sums.data(), k.sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, k.stream));
+      HIP_TRY(hipMemcpyAsync(k.host_sums.data(), s.sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s.stream));
     }
   }
   c->ev_launches = n_steps * nranks;
   c->ev_valid = true;
   for (int r = 0; r < nranks; ++r) {
-    Rank64& k = c->ranks[r];
-    if (use_device(c, k.device)) return 1;
-    HIP_TRY(hipStreamSynchronize(k.stream));
+    const Slab64& s = c->ranks[r].slab;
+    if (use_device(c, s.device)) return 1;
+    HIP_TRY(hipStreamSynchronize(s.stream));
   }
   if (av_vels) {
     for (int t = 0; t < n_steps; ++t) {
@@ -382,22 +310,9 @@ int lbm_rows64_get_cells(lbm_rows64* c, double* cells_aos)
 {
   if (!c || !cells_aos) { lbm_internal::set_error("lbm_rows64_get_cells: null argument"); return 1; }
   c->current_device = -1;
-  for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
-    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
-    unsigned long long* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
-    hipError_t e = hipSuccess;
-    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
-      const size_t n = std::min(chunk, k.ncells - c0);
-      hipLaunchKernelGGL(lbm64_soa_to_aos_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, k.stream,
-                         reinterpret_cast<const unsigned long long*>(owned(c, k, c->cur) + c0), tmp, k.ps, n);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(cells_aos + 9 * (first + c0), tmp, sizeof(double) * 9 * n, hipMemcpyDeviceToHost, k.stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
-    }
-    (void)hipFree(tmp);
-    HIP_TRY(e);
+  for (const Rank64& k : c->ranks) {
+    if (use_device(c, k.slab.device)) return 1;
+    if (slab64_get_cells(k.slab, c->cur, slab64_chunk_cells(k.slab, c->p.nx, c->knobs), cells_aos + 9 * first_cell(c, k))) return 1;
   }
   return 0;
 }
@@ -406,24 +321,9 @@ int lbm_rows64_set_cells(lbm_rows64* c, const double* cells_aos)
 {
   if (!c || !cells_aos) { lbm_internal::set_error("lbm_rows64_set_cells: null argument"); return 1; }
   c->current_device = -1;
-  for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
-    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
-    unsigned long long* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 9 * chunk));
-    hipError_t e = hipSuccess;
-    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
-      const size_t n = std::min(chunk, k.ncells - c0);
-      e = hipMemcpyAsync(tmp, cells_aos + 9 * (first + c0), sizeof(double) * 9 * n, hipMemcpyHostToDevice, k.stream);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(lbm64_aos_to_soa_kernel, dim3(static_cast<unsigned>((n * 9 + 255) / 256)), dim3(256), 0, k.stream,
-                           tmp, reinterpret_cast<unsigned long long*>(owned(c, k, c->cur) + c0), k.ps, n);
-        e = hipGetLastError();
-      }
-      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
-    }
-    (void)hipFree(tmp);
-    HIP_TRY(e);
+  for (const Rank64& k : c->ranks) {
+    if (use_device(c, k.slab.device)) return 1;
+    if (slab64_set_cells(k.slab, c->cur, slab64_chunk_cells(k.slab, c->p.nx, c->knobs), cells_aos + 9 * first_cell(c, k))) return 1;
   }
   return 0;
 }
@@ -432,22 +332,9 @@ int lbm_rows64_get_observables(lbm_rows64* c, double* obs)
 {
   if (!c || !obs) { lbm_internal::set_error("lbm_rows64_get_observables: null argument"); return 1; }
   c->current_device = -1;
-  for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
-    const size_t chunk = chunk_cells(c, k), first = static_cast<size_t>(k.plan.y0) * c->p.nx;
-    double* tmp = nullptr;
-    HIP_TRY(hipMalloc(&tmp, sizeof(double) * 4 * chunk));
-    hipError_t e = hipSuccess;
-    for (size_t c0 = 0; c0 < k.ncells && e == hipSuccess; c0 += chunk) {
-      const size_t n = std::min(chunk, k.ncells - c0);
-      hipLaunchKernelGGL(lbm64_observables_kernel, dim3(static_cast<unsigned>((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, k.stream,
-                         owned(c, k, c->cur) + c0, k.ps, n, tmp);
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipMemcpyAsync(obs + 4 * (first + c0), tmp, sizeof(double) * 4 * n, hipMemcpyDeviceToHost, k.stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
-    }
-    (void)hipFree(tmp);
-    HIP_TRY(e);
+  for (const Rank64& k : c->ranks) {
+    if (use_device(c, k.slab.device)) return 1;
+    if (slab64_get_observables(k.slab, c->cur, slab64_chunk_cells(k.slab, c->p.nx, c->knobs), obs + 4 * first_cell(c, k))) return 1;
   }
   return 0;
 }
@@ -457,19 +344,9 @@ int lbm_rows64_av_velocity_sum(lbm_rows64* c, double* tot_u)
   if (!c || !tot_u) { lbm_internal::set_error("lbm_rows64_av_velocity_sum: null argument"); return 1; }
   c->current_device = -1;
   double s = 0.0;
-  for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
-    const int blocks = static_cast<int>(std::min<size_t>((k.ncells + kBlock - 1) / kBlock, 1024));
-    double* part = nullptr;
-    HIP_TRY(hipMalloc(&part, sizeof(double) * blocks));
-    hipLaunchKernelGGL(lbm64_av_velocity_kernel, dim3(blocks), dim3(kBlock), 0, k.stream, owned(c, k, c->cur), k.ps, k.mask, k.ncells, part);
-    std::vector<double> host(blocks);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), part, sizeof(double) * blocks, hipMemcpyDeviceToHost, k.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(k.stream);
-    (void)hipFree(part);
-    HIP_TRY(e);
-    for (double v : host) s += v;            // the blocks' sums, rank after rank
+  for (const Rank64& k : c->ranks) {
+    if (use_device(c, k.slab.device)) return 1;
+    if (slab64_add_velocity_sum(k.slab, c->cur, &s)) return 1;        // the blocks' sums into the one accumulator, rank after rank
   }
   *tot_u = s;
   return 0;
@@ -481,10 +358,10 @@ int lbm_rows64_last_run_ms(lbm_rows64* c, double* ms, int* launches)
   if (!c->ev_valid) { lbm_internal::set_error("lbm_rows64_last_run_ms: no run yet"); return 1; }
   c->current_device = -1;
   double most = 0.0;
-  for (Rank64& k : c->ranks) {
-    if (use_device(c, k.device)) return 1;
+  for (const Rank64& k : c->ranks) {
+    if (use_device(c, k.slab.device)) return 1;
     float t = 0.f;
-    HIP_TRY(hipEventElapsedTime(&t, k.ev_begin, k.ev_end));
+    HIP_TRY(hipEventElapsedTime(&t, k.slab.ev_begin, k.slab.ev_end));
     most = std::max(most, static_cast<double>(t));
   }
   *ms = most;

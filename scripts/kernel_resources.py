@@ -4,7 +4,8 @@
 
     python scripts/kernel_resources.py [--unit lbm_f64.hip] [--out profiles/r02/kernel_resources.txt]
 
---unit: the translation unit under csrc/ (default lbm_kernels.hip; lbm_f64.hip: the double-precision mode).
+--unit: the translation unit under csrc/ (default lbm_kernels.hip; lbm_f64.hip: the double-precision mode; lbm_rows64.hip: its
+row-partitioned runs).
 
 Exit status 1 if any kernel uses scratch (spills or runtime-indexed private arrays)."""
 import argparse
