@@ -32,8 +32,24 @@
  * grid.  The host half of lbm_d2q9_f64.h (lbm64_read_params, lbm64_av_velocity_obs, lbm64_reynolds, the writers) serves these runs as
  * it is.
  *
- * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; several steps per exchange
- * (LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused); overlap of a rank's interior rows with the exchange.
+ * SEVERAL STEPS PER EXCHANGE (LBM_ROWS64_FLAG_MULTI_STEPS, opt-in).  Where 32 x 16 tiles cover every rank exactly (nx % 32 == 0 and
+ * every rank's rows a multiple of 16: ny % (16 * nranks) == 0) and the smallest rank owns at least LBM_TUNE_MULTI64_MIN cells, a rank
+ * keeps K = LBM_TUNE_MULTI64_K (2..4, default 4) ghost rows on each side instead of one, advances up to K steps per launch of
+ * lbm_rows_multi_kernel_f64<K, NT, FULL> (csrc/kernels/rows_multi64.h), the partition form of lbm_multi_kernel_f64 (lbm_d2q9_f64.h:
+ * the same tile, LDS frame, sub-steps, cell update and sums), and exchanges once per launch: lbm64_push_ghost_rows_kernel stores all
+ * nine planes of its first K owned rows into the upper ghost rows of the rank below and of its last K owned rows into the lower ghost
+ * rows of the rank above.  A run of n steps is floor(n / K) launches of K steps and at most one shorter one, the last.  The ORDER is the
+ * one above with "launch" for "step"; row ny-2 is now among the pushed rows (rank 0's lower ghost rows hold a copy of it, which the
+ * kernel accelerates between its sub-steps as it does the owned one), so the accelerate pre-pass and a launch's accelerating epilogue
+ * come before the push on the same stream.  The populations are the same bits.  av_vels[t]: per rank the tree lbm_d2q9_f64.h states
+ * for lbm_multi_kernel_f64 over the rank's tiles (a lane's at most two owned cells of a sub-step, the wave's halving butterflies, one
+ * lane over the eight waves, the fold over the tiles' sums by block 0 of the next launch or by the last fold of a run), then the
+ * nranks - 1 host additions in rank order: the same bits in every run.  On any other run the flag changes nothing: the one-step kernel,
+ * one ghost row, the same name from lbm_rows64_describe and the same av_vels bits as without it.
+ *
+ * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; uneven
+ * ranks under LBM_ROWS64_FLAG_MULTI_STEPS (they run the one-step kernel); overlap of a rank's interior rows or tiles with the exchange.
+ * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused.
  */
 #ifndef LBM_D2Q9_F64_ROWS_H
 #define LBM_D2Q9_F64_ROWS_H
@@ -48,6 +64,7 @@ extern "C" {
 
 #define LBM_ROWS64_ABI_VERSION 1
 #define LBM_ROWS64_MAX_RANKS 64     /* MPI_PROCS, d2q9-bgk.c:67 */
+#define LBM_ROWS64_FLAG_MULTI_STEPS 2048u   /* K steps per launch and exchange on K ghost rows where every rank is eligible; else no effect */
 
 typedef struct lbm_rows64 lbm_rows64;   /* opaque: the device state of every rank of one run */
 
@@ -56,11 +73,13 @@ int lbm_rows64_abi_version(void);
 /* A whole periodic nx x ny grid (ny >= 3) in the initial state of d2q9-bgk.c:880-902, its rows dealt to `nranks` ranks.
  * obstacles_all = ny*nx ints, the whole grid's map.  devices = nranks HIP ordinals, or NULL: rank r on device r % (device count).
  * Ranks may share a device.  flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default
- * once a RANK's two grids exceed the Infinity Cache).
+ * once a RANK's two grids exceed the Infinity Cache), each with or without LBM_ROWS64_FLAG_MULTI_STEPS (several steps per exchange,
+ * above; accepted, like the store forms, before the first HIP call).
  * Refused, with a message and before the first HIP call: nranks outside 1..LBM_ROWS64_MAX_RANKS; a decomposition that leaves a rank
  * without a row, or the last rank fewer than 3 (d2q9-bgk.c:848-849; ny = 5 on 3 ranks is 2, 1, 2); the shapes lbm64_create refuses;
- * free_cells < 1; any other flag — LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS among them: several steps per exchange are not
- * built.  Refused after it: two ranks on distinct devices that hipDeviceCanAccessPeer denies. */
+ * free_cells < 1; any other flag — LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS among them, with or without
+ * LBM_ROWS64_FLAG_MULTI_STEPS: they are the whole grid's.  Refused after it: two ranks on distinct devices that hipDeviceCanAccessPeer
+ * denies. */
 int lbm_rows64_create(lbm_rows64** run, const lbm64_params* params, int free_cells, const int* obstacles_all, int nranks,
                       const int* devices, unsigned flags);
 int lbm_rows64_destroy(lbm_rows64* run);
@@ -83,12 +102,14 @@ int lbm_rows64_get_observables(lbm_rows64* run, double* obs);
 int lbm_rows64_av_velocity_sum(lbm_rows64* run, double* tot_u);
 
 /* Device time of the last lbm_rows64_run: events around each rank's step and push launches, the largest span over the ranks; and
- * the number of step launches of the run (n_steps * nranks). */
+ * the number of step launches of the run (n_steps * nranks; under lbm_rows_multi_kernel_f64 ceil(n_steps / K) * nranks). */
 int lbm_rows64_last_run_ms(lbm_rows64* run, double* ms, int* launches);
 
 /* What a step looks like: the kernel's name ("lbm_rows_kernel_f64<2>", "lbm_rows_kernel_f64<1>", or with non-temporal stores
  * "lbm_rows_kernel_f64<2,nt>"), the rank count, and of the rank with the most work blocks: those blocks (one more block folds the
- * previous step's sums) and the cells a block advances; the bytes of all ranks' grids, ghost rows included. */
+ * previous step's sums) and the cells a block advances; the bytes of all ranks' grids, ghost rows included.  Under
+ * LBM_ROWS64_FLAG_MULTI_STEPS on an eligible run: "lbm_rows_multi_kernel_f64<K>" or "<K,nt>", the tiles of the rank with the most,
+ * 512 cells, and 2 * 9 * 8 * nx * (ny + 2 * K * nranks) bytes. */
 int lbm_rows64_describe(const lbm_rows64* run, char* kernel_name, size_t len, int* nranks, long long* blocks, long long* cells_per_block,
                         long long* state_bytes);
 

@@ -22,7 +22,8 @@
  * LBM_PRECISION=double LBM64_RANKS=N (N >= 1) runs the same deck as N row blocks (include/lbm_d2q9_f64_rows.h): the rows are
  * partitioned by the reference's rule, rank r lives on device LBM_DEVICES[r] (a comma list; default r % device count; ranks may share
  * a device), one host thread drives all of them and the edge rows travel as peer-to-peer stores ordered by stream events.  The same
- * five lines and two files; final_state.dat is the same bytes for every N.  Of LBM_FLAGS it takes 0, 1 and 2 only.  LBM64_RANKS
+ * five lines and two files; final_state.dat is the same bytes for every N.  Of LBM_FLAGS it takes 0, 1 and 2, each with or without
+ * 2048 (LBM_ROWS64_FLAG_MULTI_STEPS: several steps per launch and exchange where every rank is eligible, the same files).  LBM64_RANKS
  * without LBM_PRECISION=double is refused.
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
@@ -133,7 +134,8 @@ static int main_double(char* argv[])
     const char* list = getenv("LBM_DEVICES");
     int* device = NULL;
     int r;
-    if (flags < 0 || flags > 2) die("LBM_FLAGS: with LBM64_RANKS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES)", __LINE__, __FILE__);
+    if (flags < 0 || (flags & ~(int)LBM_ROWS64_FLAG_MULTI_STEPS) > 2)
+      die("LBM_FLAGS: with LBM64_RANKS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES), each with or without 2048 (LBM_ROWS64_FLAG_MULTI_STEPS)", __LINE__, __FILE__);
     if (list && *list) {
       device = (int*)xmalloc(sizeof(int) * (size_t)nranks);
       for (r = 0; r < nranks; ++r) {

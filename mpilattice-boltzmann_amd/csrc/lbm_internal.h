@@ -133,12 +133,36 @@ struct PlanRows64 {
 };
 static_assert(sizeof(PlanRows64) == 14 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
 constexpr int kMaxRows64Ranks = 64;  // MPI_PROCS, d2q9-bgk.c:67
-// The flags lbm_rows64_create takes: a store form.
-constexpr unsigned kFlagsRows64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES;
+// The flags lbm_rows64_create takes: a store form, LBM_ROWS64_FLAG_MULTI_STEPS (lbm_d2q9_f64_rows.h; lbm_plan.cpp holds the two equal).
+constexpr unsigned kFlagRows64MultiSteps = 2048u;
+constexpr unsigned kFlagsRows64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | kFlagRows64MultiSteps;
 // Fills *out for rank `rank` of `nranks`; checks every argument itself.  0, or 1 and the message in lbm_last_error(): nranks outside
 // 1..64, a rank without a row, a last rank with fewer than 3 rows, the shapes lbm64_create refuses, any flag outside kFlagsRows64.
+// LBM_ROWS64_FLAG_MULTI_STEPS changes nothing in *out but .flags: what it adds is PlanRowsMulti64's.
 int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanRows64* out);
 void plan64_rows_kernel_name(const PlanRows64& plan, char* kernel_name, size_t len);
+
+// lbm_rows_multi_kernel_f64<K, NT, FULL> (kernels/rows_multi64.h) for one rank of a row-partitioned run: LBM_ROWS64_FLAG_MULTI_STEPS on
+// a run whose EVERY rank TX x TY tiles cover exactly (nx % 32 == 0, every ny_local % 16 == 0) and whose smallest rank owns at least
+// LBM_TUNE_MULTI64_MIN cells (by default 2^17, measured for ranks: lbm_plan.cpp): one decision for all ranks.  The rank then keeps `ghost` = K ghost rows on each side, advances up to K
+// steps per launch and exchanges once per launch.  Plain data in this order (tests/test_plan64_rows_multi.py mirrors it); beside
+// PlanRows64, whose layout and values do not change.
+struct PlanRowsMulti64 {
+  int multi_kernel;                  // every rank of the run advances up to K steps per launch with it
+  int K, ghost;                      // steps of a full launch (LBM_TUNE_MULTI64_K); ghost rows on each side of the owned rows: K
+  int tiles_x, n_tiles;              // tiles per row; tiles of this rank (= work blocks of a launch); 0 where the tiles do not cover every rank
+  int block, lds_bytes;              // lanes and dynamic LDS bytes of a block
+  int nt_stores;                     // plan64_whole's rule on the RANK's two grids of ny_local + 2 * ghost rows, and the flags
+  int mask_words;                    // words of the window bitfield over the ny_local + 2 * ghost storage rows
+  int partials_cap;                  // doubles of each partials buffer this kernel needs: K * n_tiles + 1
+  long long ps, grid_doubles;        // plane stride of (ny_local + 2 * ghost) * nx cells; one grid's allocation, in doubles
+};
+static_assert(sizeof(PlanRowsMulti64) == 10 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
+// Fills *out for the rank whose PlanRows64 is `rows` (plan64_rows has checked the arguments).
+void plan64_rows_multi(const Knobs& knobs, const lbm64_params* p, const PlanRows64& rows, PlanRowsMulti64* out);
+void plan64_rows_multi_kernel_name(const PlanRowsMulti64& plan, char* kernel_name, size_t len);
+// Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
+int plan64_rows_multi_next_steps(const PlanRowsMulti64& plan, int left);
 
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
@@ -225,3 +249,9 @@ extern "C" int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* pl
 extern "C" int lbm_plan64_rows_sizeof(void);
 extern "C" int lbm_plan64_rows(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRows64* out);
 extern "C" int lbm_plan64_rows_kernel_name(const lbm_internal::PlanRows64* plan, char* kernel_name, size_t len);
+// And for lbm_rows_multi_kernel_f64: the PlanRowsMulti64 that rank would get (0, or 1 where lbm_rows64_create refuses the arguments), its
+// kernel's name ("" where multi_kernel is 0), and the launches of a run on one rank (full[i] = 1 where launch i makes exactly K steps).
+extern "C" int lbm_plan64_rows_multi_sizeof(void);
+extern "C" int lbm_plan64_rows_multi(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMulti64* out);
+extern "C" int lbm_plan64_rows_multi_kernel_name(const lbm_internal::PlanRowsMulti64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_rows_multi_run_launches(const lbm_internal::PlanRowsMulti64* plan, int n_steps, int* steps, int* full, int cap);

@@ -31,7 +31,7 @@ inline int knob_or(int v, int fallback) { return v == kKnobUnset ? fallback : v;
   X(LBM_TUNE_TILE64_MAX,        tile64_max,        1 << 20,    std::atoi)                   \
   X(LBM_TUNE_TILE64_GEOM,       tile64_geom,       kKnobUnset, std::atoi)                   \
   X(LBM_TUNE_MULTI64_K,         multi64_k,         kKnobUnset, std::atoi)                   \
-  X(LBM_TUNE_MULTI64_MIN,       multi64_min,       1 << 20,    std::atoi)                   \
+  X(LBM_TUNE_MULTI64_MIN,       multi64_min,       kKnobUnset, std::atoi)                   \
   X(LBM_TUNE_MULTI_K,           multi_k,           kKnobUnset, std::atoi)                   \
   X(LBM_TUNE_MULTI5_MIN,        multi5_min,        1 << 26,    std::atoi)                   \
   X(LBM_TUNE_MULTI_TAIL4,       multi_tail4,       1,          std::atoi)                   \

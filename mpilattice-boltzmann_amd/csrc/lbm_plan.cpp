@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "lbm_d2q9.h"
+#include "lbm_d2q9_f64_rows.h"
 #include "lbm_geometry.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
@@ -521,7 +522,7 @@ int plan64_next_steps(const Plan64& c, int left)
 void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMulti64* out)
 {
   PlanMulti64 m{};
-  constexpr int kDefaultK = 4;
+  constexpr int kDefaultK = 4, kDefaultMin = 1 << 20;                     // cells of a whole grid (a row partition has a default of its own: plan64_rows_multi)
   m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kDefaultK;     // a malformed or unbuilt value: the default
   m.TX = kMulti64TX; m.TY = kMulti64TY;
   m.block = kMulti64Lanes;
@@ -531,7 +532,7 @@ void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan,
   m.tiles_x = tiles ? p->nx / m.TX : 0;
   m.n_tiles = tiles ? m.tiles_x * (p->ny / m.TY) : 0;
   m.multi_kernel = (plan.flags & LBM64_FLAG_MULTI_STEPS) != 0u && !plan.tile_kernel && tiles &&
-                   static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knobs.multi64_min);
+                   static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knob_or(knobs.multi64_min, kDefaultMin));
   m.partials_cap = m.K * m.n_tiles + 1;
   *out = m;
 }
@@ -560,7 +561,7 @@ int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank,
   if (p->ny < 3) { set_error("lbm_rows64: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
   if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { set_error("lbm_rows64: grid too large for 32-bit cell indices"); return 1; }
   if ((flags & (LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS)) != 0u) {
-    set_error("lbm_rows64: LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused: a row partition exchanges its edge rows after every step (several steps per exchange are not built)");
+    set_error("lbm_rows64: LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused: they are the whole grid's, for whose kernels several steps per exchange are not built (a row partition takes LBM_ROWS64_FLAG_MULTI_STEPS, alone or with a store form)");
     return 1;
   }
   if ((flags & ~kFlagsRows64) != 0u) { set_error("lbm_rows64: a row partition takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only"); return 1; }
@@ -599,6 +600,62 @@ int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank,
 void plan64_rows_kernel_name(const PlanRows64& c, char* kernel_name, size_t len)
 {
   std::snprintf(kernel_name, len, c.nt_stores ? "lbm_rows_kernel_f64<%d,nt>" : "lbm_rows_kernel_f64<%d>", c.lane_cells);
+}
+
+// LBM_ROWS64_FLAG_MULTI_STEPS: lbm_rows_multi_kernel_f64 on every rank, or on none.  The shape rule is plan64_multi's on each rank's
+// owned rows (nx % TX == 0, every ny_local % TY == 0: under lbm_decompose, ny % (TY * nranks) == 0, so uneven ranks fall back), K and
+// the minimum size are plan64_multi's knobs, the minimum taken on the SMALLEST rank's owned cells.  Its default for ranks is measured
+// (profiles/r18/f64_rows_multi.txt, all ranks on one MI355X), by plan64_multi's rule: the smallest measured rank size at which the
+// flagged run beats the unflagged one by more than both max - min spreads together, us per step unflagged | flagged:
+//   8192x8192 on 8 ranks (2^23 cells a rank) 1697.0 | 682.2   4096x4096 on 8 (2^21) 449.9 | 182.3   2048x2048 on 8 (2^19) 146.5 | 46.3
+//   1024x1024 on 2 (2^19) 37.86 | 15.21   1024x1024 on 8 (2^17) 96.90 | 31.14, a gain of 65.76 us against spreads of 3.88 us
+// which is the smallest rank size measured: 2^17 cells a rank.  (A rank's launch adds 2 K rows of ring work and a push of 72 nx
+// doubles to a whole grid's, but it also saves K - 1 of every K exchanges, which weigh most on small ranks.)  Storage: K ghost rows on each side, K of a FULL launch, so that
+// a launch of k <= K steps finds the k rows it consumes; the tile rows are ny_local / TY >= 1, so ny_local >= 16 > 2 K: the rows a rank
+// pushes (its first and last K owned ones) and the ghost rows it receives are disjoint even where it is its own neighbour.
+static_assert(LBM_ROWS64_FLAG_MULTI_STEPS == kFlagRows64MultiSteps, "lbm_internal.h restates the header's flag");
+static_assert(kMulti64TY > 2 * kMulti64MaxK, "a rank's pushed rows and ghost rows are disjoint");
+void plan64_rows_multi(const Knobs& knobs, const lbm64_params* p, const PlanRows64& rows, PlanRowsMulti64* out)
+{
+  PlanRowsMulti64 m{};
+  constexpr int kDefaultK = 4, kDefaultMin = 1 << 17;                     // cells of the smallest rank
+  m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kDefaultK;     // a malformed or unbuilt value: the default
+  m.ghost = m.K;
+  m.block = kMulti64Lanes;
+  m.lds_bytes = multi64_lds_bytes(m.K);
+  int nyl[kMaxRows64Ranks], dis[kMaxRows64Ranks];
+  (void)lbm_decompose(p->ny, rows.nranks, nyl, dis);                       // plan64_rows made `rows` of it
+  bool tiles = p->nx % kMulti64TX == 0;
+  int smallest = nyl[0];
+  for (int r = 0; r < rows.nranks; ++r) {
+    tiles = tiles && nyl[r] % kMulti64TY == 0;
+    smallest = std::min(smallest, nyl[r]);
+  }
+  m.tiles_x = tiles ? p->nx / kMulti64TX : 0;
+  m.n_tiles = tiles ? m.tiles_x * (rows.ny_local / kMulti64TY) : 0;
+  m.multi_kernel = (rows.flags & kFlagRows64MultiSteps) != 0u && tiles &&
+                   static_cast<long long>(p->nx) * smallest >= static_cast<long long>(knob_or(knobs.multi64_min, kDefaultMin));
+  const size_t storage = static_cast<size_t>(p->nx) * (rows.ny_local + 2 * m.ghost);
+  m.ps = static_cast<long long>(plane_stride_floats(storage, knobs.skew));   // always even
+  m.grid_doubles = 9 * m.ps + 128;
+  m.nt_stores = 2 * 9 * storage * sizeof(double) > (192u << 20);             // plan64_whole's rule
+  if (rows.flags & LBM_FLAG_NT_STORES) m.nt_stores = 1;
+  if (rows.flags & LBM_FLAG_NO_NT_STORES) m.nt_stores = 0;
+  m.mask_words = static_cast<int>((storage + 31) / 32 + 4);
+  m.partials_cap = m.K * m.n_tiles + 1;
+  *out = m;
+}
+
+void plan64_rows_multi_kernel_name(const PlanRowsMulti64& m, char* kernel_name, size_t len)
+{
+  if (!m.multi_kernel) { kernel_name[0] = '\0'; return; }
+  std::snprintf(kernel_name, len, m.nt_stores ? "lbm_rows_multi_kernel_f64<%d,nt>" : "lbm_rows_multi_kernel_f64<%d>", m.K);
+}
+
+// As plan64_multi_next_steps: floor(n / K) launches of K steps and at most one shorter launch, the last.
+int plan64_rows_multi_next_steps(const PlanRowsMulti64& m, int left)
+{
+  return std::min(m.K, left);
 }
 
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
@@ -997,6 +1054,33 @@ int lbm_plan64_rows_kernel_name(const lbm_internal::PlanRows64* plan, char* kern
   if (!plan || !kernel_name || !len) { set_error("lbm_plan64_rows_kernel_name: null argument"); return 1; }
   lbm_internal::plan64_rows_kernel_name(*plan, kernel_name, len);
   return 0;
+}
+int lbm_plan64_rows_multi_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanRowsMulti64)); }
+int lbm_plan64_rows_multi(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMulti64* out)
+{
+  lbm_internal::PlanRows64 rows;
+  if (!out) { set_error("lbm_plan64_rows_multi: null argument"); return 1; }
+  const Knobs knobs = knobs_from_env();
+  if (lbm_internal::plan64_rows(knobs, p, nranks, rank, flags, &rows)) return 1;
+  lbm_internal::plan64_rows_multi(knobs, p, rows, out);
+  return 0;
+}
+int lbm_plan64_rows_multi_kernel_name(const lbm_internal::PlanRowsMulti64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_rows_multi_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_rows_multi_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_rows_multi_run_launches(const lbm_internal::PlanRowsMulti64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || !multi64_k_ok(plan->K) || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_rows_multi_run_launches: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_internal::plan64_rows_multi_next_steps(*plan, left);
+    if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
+    left -= k;
+  }
+  return n;
 }
 
 int lbm_plan_edge_rows_suffice(const ContextPlan* plan, int left)

@@ -28,6 +28,24 @@
 // av_vels[t]: each rank's sums[t] (folded as lbm64_run folds them) copied to the host and added there in rank order, times
 // 1.0 / free_cells: one more serial level of the summation tree, nranks - 1 additions, the same bits in every run.
 //
+// SEVERAL STEPS PER EXCHANGE (LBM_ROWS64_FLAG_MULTI_STEPS where PlanRowsMulti64.multi_kernel, the same on every rank).  Rank r then keeps
+// two grids of ny_local + 2 K storage rows (kernels/rows_multi64.h has the layout) and, beside the slab's bitfield of its owned rows,
+// a WINDOW bitfield over all its storage rows.  A launch of a rank is lbm_rows_multi_kernel_f64, k <= K steps from grid A into grid B,
+// then lbm64_push_ghost_rows_kernel, which stores all nine planes of B's first and last K owned rows into the neighbours' ghost rows of
+// THEIR grid B, then the record of pushed[launch & 1].  THE ORDER is the one above with "launch" for "step" and K rows for one, and
+// every item of it holds as it is written, for the same reasons — but the last:
+//   - row ny-2 IS among the pushed rows now (one of the last rank's last two rows, nyl >= 16): rank 0's lower ghost rows hold a copy of
+//     it.  The copy must be the accelerated row exactly when the owned row is.  Before launch 0 the pre-pass accelerates the owned row
+//     on its rank's stream and push -1 follows it ON THE SAME STREAM; a launch that another step follows accelerates the row in its
+//     epilogue (accel_last), and push t follows kernel t on the same stream; the last launch of a run does not, and neither does its
+//     push send an accelerated row: the next run's pre-pass and push -1 do.  Inside a launch the kernel accelerates every copy of the
+//     row (owned, ghost, ring: told by the whole grid's row index) between its sub-steps, as lbm_multi_kernel_f64 does.
+// A launch of k steps consumes k of the K ghost rows on each side; the K rows pushed after it are whole again.  Degenerate rings: with
+// one rank the rank is its own neighbour, with two both neighbours are the other rank; the rows a push reads (owned) and writes (ghost)
+// are disjoint in both, because ny_local >= 16 > 2 K.  av_vels[t]: per rank lbm_multi_kernel_f64's tree over the rank's tiles (the
+// last launch's vectors folded by lbm64_fold_kernel(..., n_tiles, k, ...)), then the same nranks - 1 host additions.
+// The one-step path's code and launches are what they were.
+//
 // gfx950 only: 64-wide wavefronts (block_sum).
 
 #include <hip/hip_runtime.h>
@@ -37,19 +55,23 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lbm_d2q9_f64_rows.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 #include "kernels/rows64.h"
+#include "kernels/rows_multi64.h"
 #include "lbm_f64_slab.h"
 
 namespace {
 
 struct Rank64 {
   lbm_internal::PlanRows64 plan{};   // written once (lbm_plan.cpp plan64_rows)
-  Slab64 slab;                       // the rank's row block on its device (lbm_f64_slab.h): grid[g] is plane 0 STORAGE row 0, the owned cells start one row on
+  lbm_internal::PlanRowsMulti64 multi{};   // lbm_rows_multi_kernel_f64's part of it (plan64_rows_multi): written once; multi_kernel is the same on every rank
+  uint32_t* window_mask = nullptr;   // multi_kernel: the obstacle bitfield over ALL storage rows of the rank, bit c of the storage cell c
+  Slab64 slab;                       // the rank's row block on its device (lbm_f64_slab.h): grid[g] is plane 0 STORAGE row 0, the owned cells start one row on (multi_kernel: K rows)
   hipEvent_t pushed[2] = {nullptr, nullptr}; // this rank's push of step t has finished: pushed[t & 1]
   std::vector<double> host_sums;
 };
@@ -78,6 +100,14 @@ constexpr Rows64Kernel kRows64Kernels[2][2] = {
   {&lbm_rows_kernel_f64<kPairCells, false>, &lbm_rows_kernel_f64<kPairCells, true>},
   {&lbm_rows_kernel_f64<1, false>, &lbm_rows_kernel_f64<1, true>},
 };
+
+using RowsMulti64Kernel = void (*)(RowsMulti64Args);
+// every instantiation of the rank's multi-step kernel, by multi64_row(K, NT, FULL) (lbm_geometry.h, as kMulti64Kernels of lbm_f64.hip)
+#define LBM_ROWS_MULTI64_ROWS(K) &lbm_rows_multi_kernel_f64<K, false, false>, &lbm_rows_multi_kernel_f64<K, false, true>, &lbm_rows_multi_kernel_f64<K, true, false>, &lbm_rows_multi_kernel_f64<K, true, true>
+constexpr RowsMulti64Kernel kRowsMulti64Kernels[kMulti64Rows] = {LBM_ROWS_MULTI64_ROWS(2), LBM_ROWS_MULTI64_ROWS(3), LBM_ROWS_MULTI64_ROWS(4)};
+#undef LBM_ROWS_MULTI64_ROWS
+static_assert(kMulti64MinK == 2 && kMulti64MaxK == 4 && multi64_row(2, false, true) == 1 && multi64_row(4, true, true) == 11, "the order of kRowsMulti64Kernels");
+static_assert(multi64_lds_bytes(kMulti64MaxK) <= 65536, "no launch asks for more dynamic LDS than a kernel gets without hipFuncSetAttribute");
 
 // hipSetDevice where the device changes: every launch, record and copy of a rank is made with its device current
 int use_device(lbm_rows64* c, int device)
@@ -109,6 +139,122 @@ int enqueue_push(lbm_rows64* c, int r, int g)
   return 0;
 }
 
+// Rank r's push of grid `g` in the multi-step mode: its first and last K owned rows into the neighbours' ghost rows of their grid `g`.
+int enqueue_push_ghost(lbm_rows64* c, int r, int g)
+{
+  const Rank64& k = c->ranks[r];
+  const Rank64& down = c->ranks[(r + c->nranks - 1) % c->nranks];
+  const Rank64& up = c->ranks[(r + 1) % c->nranks];
+  RowsPushGhost64Args a{};
+  a.grid = k.slab.grid[g];
+  a.ps = k.slab.ps;
+  a.nx = static_cast<uint32_t>(c->p.nx); a.nyl = static_cast<uint32_t>(k.plan.ny_local); a.ghost = static_cast<uint32_t>(k.multi.ghost);
+  a.down = down.slab.grid[g]; a.down_ps = down.slab.ps; a.down_nyl = static_cast<uint32_t>(down.plan.ny_local);
+  a.up = up.slab.grid[g]; a.up_ps = up.slab.ps;
+  const unsigned accesses = a.ghost * (a.nx / kPairCells);               // of one plane and way
+  lbm64_push_ghost_rows_kernel<<<dim3((accesses + kBlock - 1) / kBlock, 2 * 9), dim3(kBlock), 0, k.slab.stream>>>(a);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The end of every run: all streams synchronised, then the ranks' per-step sums added on the host.
+int finish_run(lbm_rows64* c, int n_steps, double* av_vels)
+{
+  const int nranks = c->nranks;
+  for (int r = 0; r < nranks; ++r) {
+    const Slab64& s = c->ranks[r].slab;
+    if (use_device(c, s.device)) return 1;
+    HIP_TRY(hipStreamSynchronize(s.stream));
+  }
+  if (av_vels) {
+    for (int t = 0; t < n_steps; ++t) {
+      double s = c->ranks[0].host_sums[t];
+      for (int r = 1; r < nranks; ++r) s += c->ranks[r].host_sums[t];        // rank order: nranks - 1 additions
+      av_vels[t] = s * c->free_cells_inv;                                    // d2q9-bgk.c:367
+    }
+  }
+  return 0;
+}
+
+// lbm_rows64_run where every rank advances with lbm_rows_multi_kernel_f64: the unit's header has the order.
+int run_multi(lbm_rows64* c, int n_steps, double* av_vels)
+{
+  const int nranks = c->nranks;
+  const uint32_t nx = static_cast<uint32_t>(c->p.nx);
+  {
+    // accelerate_flow of the first step on the rank that owns row ny-2, on its stream BEFORE its push -1, which sends that row
+    const Rank64& k = c->ranks[c->ranks[0].plan.accel_rank];
+    const Slab64& s = k.slab;
+    if (use_device(c, s.device)) return 1;
+    hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, s.stream, s.owned(c->cur), s.ps, s.mask, nx,
+                       static_cast<uint32_t>(k.plan.accel_row), c->accel_w1, c->accel_w2);
+    HIP_TRY(hipGetLastError());
+  }
+  for (int r = 0; r < nranks; ++r) {             // push -1 (all ranks are idle: the last call synchronised them)
+    Rank64& k = c->ranks[r];
+    if (use_device(c, k.slab.device)) return 1;
+    if (enqueue_push_ghost(c, r, c->cur)) return 1;
+    HIP_TRY(hipEventRecord(k.pushed[1], k.slab.stream));
+  }
+  int parity = 0, launches = 0, last_vecs = 0;
+  for (int left = n_steps; left > 0; ++launches) {
+    const int steps = lbm_internal::plan64_rows_multi_next_steps(c->ranks[0].multi, left);     // K is the same on every rank
+    left -= steps;
+    const int before = (launches + 1) & 1, now = launches & 1;     // the pushed events of launch - 1 and of this launch
+    for (int r = 0; r < nranks; ++r) {
+      Rank64& k = c->ranks[r];
+      const Slab64& s = k.slab;
+      const lbm_internal::PlanRowsMulti64& m = k.multi;
+      const int down = (r + nranks - 1) % nranks, up = (r + 1) % nranks;
+      if (use_device(c, s.device)) return 1;
+      if (down != r) HIP_TRY(hipStreamWaitEvent(s.stream, c->ranks[down].pushed[before], 0));
+      if (up != r && up != down) HIP_TRY(hipStreamWaitEvent(s.stream, c->ranks[up].pushed[before], 0));
+      if (launches == 0) HIP_TRY(hipEventRecord(s.ev_begin, s.stream));
+      RowsMulti64Args a{};
+      a.src = s.grid[c->cur];
+      a.dst = s.grid[c->cur ^ 1];
+      a.mask = k.window_mask;
+      a.ps = s.ps;
+      a.nx = c->p.nx; a.ny = c->p.ny;
+      a.ghost = m.ghost;
+      a.row0 = k.plan.y0 - m.ghost;
+      a.tiles_x = m.tiles_x;
+      a.ksteps = steps;
+      a.omega = c->p.omega;
+      a.accel_w1 = c->accel_w1; a.accel_w2 = c->accel_w2;
+      a.accel_row = c->p.ny - 2;
+      a.accel_last = left > 0;
+      a.partials_out = s.partials[parity];
+      a.prev_partials = s.partials[parity ^ 1];
+      a.n_prev = m.n_tiles; a.n_prev_vecs = last_vecs;
+      a.sums = s.sums;
+      a.counter = s.counter;
+      kRowsMulti64Kernels[multi64_row(m.K, m.nt_stores != 0, steps == m.K)]<<<dim3(m.n_tiles + 1), dim3(m.block), static_cast<size_t>(m.lds_bytes), s.stream>>>(a);   // + the fold block
+      HIP_TRY(hipGetLastError());
+      if (enqueue_push_ghost(c, r, c->cur ^ 1)) return 1;
+      HIP_TRY(hipEventRecord(k.pushed[now], s.stream));
+    }
+    last_vecs = steps;
+    parity ^= 1;
+    c->cur ^= 1;
+  }
+  for (int r = 0; r < nranks; ++r) {
+    Rank64& k = c->ranks[r];
+    const Slab64& s = k.slab;
+    if (use_device(c, s.device)) return 1;
+    HIP_TRY(hipEventRecord(s.ev_end, s.stream));
+    hipLaunchKernelGGL(lbm64_fold_kernel, dim3(1), dim3(kBlock), 0, s.stream, s.partials[parity ^ 1], k.multi.n_tiles, last_vecs, s.sums, s.counter);
+    HIP_TRY(hipGetLastError());
+    if (av_vels) {
+      k.host_sums.resize(static_cast<size_t>(n_steps));
+      HIP_TRY(hipMemcpyAsync(k.host_sums.data(), s.sums, sizeof(double) * n_steps, hipMemcpyDeviceToHost, s.stream));
+    }
+  }
+  c->ev_launches = launches * nranks;
+  c->ev_valid = true;
+  return 0;
+}
+
 // The whole grid's index of a rank's first owned cell.
 size_t first_cell(const lbm_rows64* c, const Rank64& k) { return static_cast<size_t>(k.plan.y0) * c->p.nx; }
 
@@ -130,6 +276,7 @@ int lbm_rows64_destroy(lbm_rows64* c)
     if (!k.slab.stream) continue;
     (void)hipSetDevice(k.slab.device);
     for (int i = 0; i < 2; ++i) if (k.pushed[i]) (void)hipEventDestroy(k.pushed[i]);
+    if (k.window_mask) (void)hipFree(k.window_mask);
     slab64_destroy(k.slab);
   }
   delete c;
@@ -159,9 +306,11 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
     if (lbm_internal::plan64_rows(knobs, p, nranks, r, flags, &k.plan)) return fail();
+    lbm_internal::plan64_rows_multi(knobs, p, k.plan, &k.multi);
+    const bool multi = k.multi.multi_kernel != 0;
     k.slab.ncells = static_cast<size_t>(p->nx) * k.plan.ny_local;
-    k.slab.first = static_cast<size_t>(p->nx);                 // storage row 1
-    k.slab.ps = static_cast<size_t>(k.plan.ps);
+    k.slab.first = static_cast<size_t>(p->nx) * (multi ? k.multi.ghost : 1);      // the first owned row: storage row 1, or K
+    k.slab.ps = static_cast<size_t>(multi ? k.multi.ps : k.plan.ps);
   }
   if (devices) {
     for (int r = 0; r < nranks; ++r) c->ranks[r].slab.device = devices[r];
@@ -200,9 +349,24 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
     Rank64& k = c->ranks[r];
     const lbm_internal::PlanRows64& plan = k.plan;
     HIP_TRY_OR(hipSetDevice(k.slab.device), return fail());
-    if (slab64_create(k.slab, static_cast<size_t>(plan.grid_doubles), static_cast<size_t>(plan.mask_words), static_cast<size_t>(plan.partials_cap),
-                      obstacles + first_cell(c, k), p->density, p->max_iters))
+    const lbm_internal::PlanRowsMulti64& multi = k.multi;
+    if (slab64_create(k.slab, static_cast<size_t>(multi.multi_kernel ? multi.grid_doubles : plan.grid_doubles), static_cast<size_t>(plan.mask_words),
+                      static_cast<size_t>(std::max(plan.partials_cap, multi.multi_kernel ? multi.partials_cap : 0)), obstacles + first_cell(c, k), p->density, p->max_iters))
       return fail();
+    if (multi.multi_kernel) {
+      // the window bitfield: storage row i is row (y0 - K + i) mod ny of the whole grid
+      std::vector<uint32_t> bits(static_cast<size_t>(multi.mask_words), 0u);
+      const size_t nx = static_cast<size_t>(p->nx);
+      for (int i = 0; i < plan.ny_local + 2 * multi.ghost; ++i) {
+        const int* row = obstacles + static_cast<size_t>(((plan.y0 - multi.ghost + i) % p->ny + p->ny) % p->ny) * nx;
+        for (size_t x = 0; x < nx; ++x) {
+          const size_t cell = static_cast<size_t>(i) * nx + x;
+          if (row[x]) bits[cell >> 5] |= 1u << (cell & 31);
+        }
+      }
+      HIP_TRY_OR(hipMalloc(&k.window_mask, sizeof(uint32_t) * bits.size()), return fail());
+      HIP_TRY_OR(hipMemcpy(k.window_mask, bits.data(), sizeof(uint32_t) * bits.size(), hipMemcpyHostToDevice), return fail());
+    }
     for (int i = 0; i < 2; ++i) HIP_TRY_OR(hipEventCreateWithFlags(&k.pushed[i], hipEventDisableTiming), return fail());
   }
   for (int r = 0; r < nranks; ++r) {
@@ -224,6 +388,10 @@ int lbm_rows64_run(lbm_rows64* c, int n_steps, double* av_vels)
   for (Rank64& k : c->ranks) {
     if (use_device(c, k.slab.device)) return 1;
     if (slab64_ensure_sums(k.slab, n_steps, c->p.max_iters)) return 1;
+  }
+  if (c->ranks[0].multi.multi_kernel) {
+    if (run_multi(c, n_steps, av_vels)) return 1;
+    return finish_run(c, n_steps, av_vels);
   }
   {
     // accelerate_flow of the first step (d2q9-bgk.c:345-348) on the rank that owns row ny-2: every later one is the epilogue of the step before it
@@ -291,19 +459,7 @@ int lbm_rows64_run(lbm_rows64* c, int n_steps, double* av_vels)
   }
   c->ev_launches = n_steps * nranks;
   c->ev_valid = true;
-  for (int r = 0; r < nranks; ++r) {
-    const Slab64& s = c->ranks[r].slab;
-    if (use_device(c, s.device)) return 1;
-    HIP_TRY(hipStreamSynchronize(s.stream));
-  }
-  if (av_vels) {
-    for (int t = 0; t < n_steps; ++t) {
-      double s = c->ranks[0].host_sums[t];
-      for (int r = 1; r < nranks; ++r) s += c->ranks[r].host_sums[t];        // rank order: nranks - 1 additions
-      av_vels[t] = s * c->free_cells_inv;                                    // d2q9-bgk.c:367
-    }
-  }
-  return 0;
+  return finish_run(c, n_steps, av_vels);
 }
 
 int lbm_rows64_get_cells(lbm_rows64* c, double* cells_aos)
@@ -372,6 +528,20 @@ int lbm_rows64_last_run_ms(lbm_rows64* c, double* ms, int* launches)
 int lbm_rows64_describe(const lbm_rows64* c, char* kernel_name, size_t len, int* nranks, long long* blocks, long long* cells_per_block, long long* state_bytes)
 {
   if (!c) { lbm_internal::set_error("lbm_rows64_describe: null run"); return 1; }
+  if (c->ranks[0].multi.multi_kernel) {
+    const Rank64* most = &c->ranks[0];
+    long long bytes = 0;
+    for (const Rank64& k : c->ranks) {
+      if (k.multi.n_tiles > most->multi.n_tiles) most = &k;
+      bytes += static_cast<long long>(2 * 9 * sizeof(double)) * c->p.nx * (k.plan.ny_local + 2 * k.multi.ghost);
+    }
+    if (kernel_name && len > 0) lbm_internal::plan64_rows_multi_kernel_name(most->multi, kernel_name, len);
+    if (nranks) *nranks = c->nranks;
+    if (blocks) *blocks = most->multi.n_tiles;
+    if (cells_per_block) *cells_per_block = static_cast<long long>(kMulti64TX) * kMulti64TY;
+    if (state_bytes) *state_bytes = bytes;
+    return 0;
+  }
   const Rank64* most = &c->ranks[0];
   long long bytes = 0;
   for (const Rank64& k : c->ranks) {

@@ -39,12 +39,17 @@ compared for equal bits (host-bound, about 13 GB of host memory); its line goes 
 
 --ranks N[,N] [--devices LIST] [--steps S]: row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count beside
 the one-context one-step and LBM64_FLAG_MULTI_STEPS runs of the same grid (--work NXxNY, default 8192x8192), alternating: device and
-wall time per step.  With all ranks on one device this measures the loop's overhead, not a speed-up; --out appends.
+wall time per step.  Each rank count runs twice, without and with LBM_ROWS64_FLAG_MULTI_STEPS (K steps per launch and exchange; the
+minimum size is lowered to 0 so that every size whose ranks the tiles cover is measured), and a line under the table holds the flagged
+run against the unflagged one: the median gain beside the two max - min spreads together.  With all ranks on one device this measures
+the loop's overhead, not a speed-up; --out appends.
 
-    F=profiles/r14/f64_rows.txt; rm -f $F
+    F=profiles/r18/f64_rows_multi.txt; rm -f $F
     timeout -k 10 400 python scripts/measure_f64.py --ranks 1,2,8 --work 8192x8192 --out $F &&
-    timeout -k 10 200 python scripts/measure_f64.py --ranks 1 --work 8192x1024 --out $F &&
-    timeout -k 10 200 python scripts/measure_f64.py --ranks 8 --work 1024x1024 --steps 2000 --out $F"""
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 4096x4096 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 2048x2048 --steps 400 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 1024x1024 --steps 2000 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1 --work 8192x1024 --out $F"""
 import argparse
 import ctypes as C
 import os
@@ -283,6 +288,7 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
     import time
     p, obst = deck(name)
     n0 = len(lines)
+    os.environ["LBM_TUNE_MULTI64_MIN"] = "0"              # read when a context is made: the multi-step kernels on every size the tiles cover
     runs = {"one context, one step": f64.Grid64(p, obst)}
     multi = f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS)
     if multi.describe()["kernel"].startswith("lbm_multi_kernel_f64<"):
@@ -291,7 +297,13 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
         multi.close()
     for n in ranks:
         dev = None if devices is None else [devices[r % len(devices)] for r in range(n)]
-        runs[f"{n} rank{'s' if n > 1 else ''}"] = f64.Rows64(p, obst, n, devices=dev)
+        key = f"{n} rank{'s' if n > 1 else ''}"
+        runs[key] = f64.Rows64(p, obst, n, devices=dev)
+        flagged = f64.Rows64(p, obst, n, devices=dev, flags=f64.FLAG_ROWS_MULTI_STEPS)
+        if flagged.describe()["kernel"].startswith("lbm_rows_multi_kernel_f64<"):
+            runs[key + ", multi-step"] = flagged
+        else:
+            flagged.close()                                # uneven ranks, or tiles that do not cover them: the flag changes nothing
     shapes = {k: q.describe() for k, q in runs.items()}
     first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
     base = first["one context, one step"]
@@ -312,8 +324,16 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
     lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; ranks on {where}; us per step")
     for k in runs:
         d, w = dev_us[k], wall_us[k]
-        lines.append(f"  {k:24s} {shapes[k]['kernel']:28s} {shapes[k]['blocks']:6d} blocks   device median {statistics.median(d):9.3f}  min {min(d):9.3f}  max {max(d):9.3f}"
+        lines.append(f"  {k:24s} {shapes[k]['kernel']:32s} {shapes[k]['blocks']:6d} blocks   device median {statistics.median(d):9.3f}  min {min(d):9.3f}  max {max(d):9.3f}"
                      f"   wall median {statistics.median(w):9.3f}  min {min(w):9.3f}  max {max(w):9.3f}")
+    for k in [k for k in runs if k.endswith(", multi-step") and k != "one context, multi-step"]:
+        off = k[:-len(", multi-step")]
+        med = {q: statistics.median(dev_us[q]) for q in (off, k)}
+        gain = med[off] - med[k]
+        spreads = (max(dev_us[off]) - min(dev_us[off])) + (max(dev_us[k]) - min(dev_us[k]))
+        cells = p.nx * (p.ny // int(off.split()[0]))
+        lines.append(f"  {k} against {off} ({cells} cells a rank): {med[off] / med[k]:.3f} x; median gain {gain:.3f} us against the two max - min spreads together "
+                     f"{spreads:.3f} us -> {'a win' if gain > spreads else 'no win'}")
     print("\n".join(lines[n0:]), flush=True)
 
 
@@ -333,7 +353,8 @@ def main():
     lbm.build()
     if a.ranks:
         lines = [] if a.out and os.path.exists(a.out) else [
-            "# scripts/measure_f64.py --ranks: row-partitioned double-precision runs (lbm_rows_kernel_f64 + lbm64_push_rows_kernel per rank-step) beside the one-context runs",
+            "# scripts/measure_f64.py --ranks: row-partitioned double-precision runs (lbm_rows_kernel_f64 + lbm64_push_rows_kernel per rank-step; \"multi-step\": "
+            "LBM_ROWS64_FLAG_MULTI_STEPS, lbm_rows_multi_kernel_f64 + lbm64_push_ghost_rows_kernel per rank-launch) beside the one-context runs",
             "# device: events around a run's step launches, over its steps (partitioned: the largest span over the ranks); wall: the host's clock around run()"]
         measure_rows(a.work or "8192x8192", [int(v) for v in a.ranks.split(",")], [int(v) for v in a.devices.split(",")] if a.devices else None,
                      a.steps or (12 if a.quick else 200), 3 if a.quick else 5, lines)

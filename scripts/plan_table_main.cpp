@@ -1,12 +1,15 @@
 // plan_table_main.cpp — the planning unit under the host sanitizers: the three plan functions over the table of tests/plan_cases.py and
 // over the refusals, printed one line per context, and under each context every launch of its runs of 11 and 20 steps, both schedules
-// (lbm_plan_run_launches), one line per launch; then the row blocks of the double-precision mode (lbm_plan64_rows), one line per rank.  Host-only code, no GPU and no Python (of lbm_host.cpp the planner needs set_error and
+// (lbm_plan_run_launches), one line per launch; then the row blocks of the double-precision mode (lbm_plan64_rows), one line per rank, and under LBM_ROWS64_FLAG_MULTI_STEPS their multi-step plans (lbm_plan64_rows_multi) with the launches of a run of 11 steps.  Host-only code, no GPU and no Python (of lbm_host.cpp the planner needs set_error and
 // the two decompositions only):
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I mpilattice-boltzmann_amd/csrc
 //       scripts/plan_table_main.cpp mpilattice-boltzmann_amd/csrc/lbm_plan.cpp mpilattice-boltzmann_amd/csrc/lbm_host.cpp -pthread -o plan_table && ./plan_table
 #include <cstdio>
 
+#include <cstdlib>
+
 #include "lbm_d2q9.h"
+#include "lbm_d2q9_f64_rows.h"
 #include "lbm_internal.h"
 
 static int shown = 0, launches = 0;
@@ -68,6 +71,32 @@ int main()
         if (rc == 0) std::printf("rows  %6d x %-6d rank %d of %d: rows %d + %d, %s, %u units in %d blocks x %d, ps %lld\n", g[0], g[1], r, g[2], q.y0, q.ny_local, name, q.units, q.blocks, q.iters, q.ps);
         else std::printf("rows  %6d x %-6d rank %d of %d: %s\n", g[0], g[1], r, g[2], lbm_last_error());
       }
+    }
+  // ... and their multi-step plans (plan64_rows_multi): the shapes tests/test_plan64_rows_multi.py checks, eligible and not, at the
+  // default minimum size and with it lowered to 0, every built K; under each eligible rank 0 the launches of a run of 11 steps
+  const int multi[][3] = {{32, 16, 1}, {32, 32, 2}, {64, 48, 3}, {1024, 1024, 8}, {8192, 8192, 8}, {8, 16, 2}, {30, 32, 2}, {32, 48, 2}, {32, 33, 2}, {32, 32, 0}};
+  for (const char* minimum : {"", "0"})
+    for (const char* k : {"", "2", "3", "4"}) {
+      if (*minimum) setenv("LBM_TUNE_MULTI64_MIN", minimum, 1); else unsetenv("LBM_TUNE_MULTI64_MIN");
+      if (*k) setenv("LBM_TUNE_MULTI64_K", k, 1); else unsetenv("LBM_TUNE_MULTI64_K");
+      for (const auto& g : multi)
+        for (unsigned f : {unsigned(LBM_ROWS64_FLAG_MULTI_STEPS), unsigned(LBM_ROWS64_FLAG_MULTI_STEPS | LBM_FLAG_NT_STORES), unsigned(LBM_ROWS64_FLAG_MULTI_STEPS | LBM64_FLAG_MULTI_STEPS), 0u}) {
+          const lbm64_params p{g[0], g[1], 11, 10, 0.1, 0.005, 1.85};
+          for (int r = 0; r < (g[2] > 0 ? g[2] : 1); ++r, ++shown) {
+            lbm_internal::PlanRowsMulti64 m;
+            char name[64] = "";
+            const int rc = lbm_plan64_rows_multi(&p, g[2], r, f, &m);
+            if (rc != 0) { std::printf("rows* %6d x %-6d rank %d of %d flags %u: %s\n", g[0], g[1], r, g[2], f, lbm_last_error()); continue; }
+            lbm_plan64_rows_multi_kernel_name(&m, name, sizeof name);
+            std::printf("rows* %6d x %-6d rank %d of %d flags %u min '%s': %s K %d ghost %d, %d tiles (%d a row) x %d lanes, LDS %d, nt %d, mask %d words, partials %d, ps %lld, grid %lld\n",
+                        g[0], g[1], r, g[2], f, minimum, m.multi_kernel ? name : "(falls back)", m.K, m.ghost, m.n_tiles, m.tiles_x, m.block, m.lds_bytes, m.nt_stores, m.mask_words, m.partials_cap, m.ps, m.grid_doubles);
+            if (r == 0 && m.multi_kernel) {
+              int steps[16], full[16];
+              const int n = lbm_plan64_rows_multi_run_launches(&m, 11, steps, full, 16);
+              for (int i = 0; i < n && i < 16; ++i, ++launches) std::printf("  11 steps  launch %d: k %d full %d\n", i, steps[i], full[i]);
+            }
+          }
+        }
     }
   std::printf("%d plans, %d launches, clean\n", shown, launches);
   return 0;
