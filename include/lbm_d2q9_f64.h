@@ -34,7 +34,8 @@
  * — a context is a whole periodic grid on one GPU (several steps per launch are opt-in: LBM64_FLAG_TILE_STEPS for small grids,
  * LBM64_FLAG_MULTI_STEPS for large ones that 32 x 16 tiles cover; without them, and on every grid they do not take, every step is one
  * launch of lbm_step_kernel_f64); the
- * fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH); a state digest (lbm_state_checksum) of doubles.
+ * fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH).  The state digest of doubles, lbm_state_checksum's
+ * counterpart, is lbm_digest64_grid of lbm_d2q9_f64_digest.h: one digest per row, under names of its own.
  */
 #ifndef LBM_D2Q9_F64_H
 #define LBM_D2Q9_F64_H

@@ -25,6 +25,9 @@
  * five lines and two files; final_state.dat is the same bytes for every N.  Of LBM_FLAGS it takes 0, 1 and 2, each with or without
  * 2048 (LBM_ROWS64_FLAG_MULTI_STEPS: several steps per launch and exchange where every rank is eligible, the same files).  LBM64_RANKS
  * without LBM_PRECISION=double is refused.
+ * LBM_PRECISION=double LBM_DIGEST=1, with or without LBM64_RANKS, adds one line on stderr after the run, "state digest: <16 hex digits>":
+ * the digest of the final populations (include/lbm_d2q9_f64_digest.h), the same for every way of advancing the same deck.  LBM_DIGEST=1
+ * without LBM_PRECISION=double is refused.
  *
  * LBM_GPUS=N (N > 1) plays the role of `mpirun -np N` (mpi_submit:63) inside ONE process: the rows are partitioned by
  * the reference's rule (d2q9-bgk.c:834-862), rank r lives on device LBM_DEVICES[r] (a comma list; default r), one host
@@ -46,6 +49,7 @@
 #include "lbm_d2q9.h"
 #include "lbm_d2q9_f64.h"
 #include "lbm_d2q9_f64_rows.h"
+#include "lbm_d2q9_f64_digest.h"
 #include "lbm_d2q9_p2p.h"
 
 static void die(const char* message, const int line, const char* file)   /* d2q9-bgk.c:1145-1151 */
@@ -161,6 +165,11 @@ static int main_double(char* argv[])
       if (params.max_iters > 0 && lbm_rows64_last_run_ms(rows, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
       fprintf(stderr, "kernel: %s on %d ranks, %d launches\n", kernel, nranks, launches);
     }
+    if (env_int("LBM_DIGEST", 0)) {
+      unsigned long long digest = 0;
+      if (lbm_digest64_rows(rows, 0, params.ny, NULL, &digest)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "state digest: %016llx\n", digest);
+    }
     lbm_rows64_destroy(rows);
   } else {
     if (lbm64_create(&ctx, &params, free_cells, obstacles, env_int("LBM_DEVICE", 0), (unsigned)env_int("LBM_FLAGS", 0)))
@@ -176,6 +185,11 @@ static int main_double(char* argv[])
       if (lbm64_describe(ctx, kernel, sizeof kernel, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
       if (params.max_iters > 0 && lbm64_last_run_kernel_ms(ctx, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
       fprintf(stderr, "kernel: %s, %d launches\n", kernel, launches);
+    }
+    if (env_int("LBM_DIGEST", 0)) {
+      unsigned long long digest = 0;
+      if (lbm_digest64_grid(ctx, 0, params.ny, NULL, &digest)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "state digest: %016llx\n", digest);
     }
     lbm64_destroy(ctx);
   }
@@ -222,6 +236,7 @@ int main(int argc, char* argv[])
     if (precision && strcmp(precision, "double") == 0) return main_double(argv);
     if (precision && *precision && strcmp(precision, "float") != 0) die("LBM_PRECISION: expected float or double", __LINE__, __FILE__);
     if (getenv("LBM64_RANKS") && *getenv("LBM64_RANKS")) die("LBM64_RANKS: row blocks in double precision need LBM_PRECISION=double", __LINE__, __FILE__);
+    if (env_int("LBM_DIGEST", 0)) die("LBM_DIGEST: the state digest is the double-precision mode's, it needs LBM_PRECISION=double", __LINE__, __FILE__);
   }
 
   if (lbm_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);

@@ -1,6 +1,7 @@
 // step64.h — the double-precision mode: lbm_step_kernel_f64<CELLS, NT> (one step per launch, an x-pair or one cell per lane) and its
-// small kernels (accelerate pre-pass, initial state, AoS<->SoA, observables, av_velocity, the last fold of a run).
-// Part of the translation unit lbm_f64.hip (device code of liblbm_d2q9.so, gfx950 only); include/lbm_d2q9_f64.h states the contract.
+// small kernels (accelerate pre-pass, initial state, AoS<->SoA, observables, av_velocity, the row digests, the last fold of a run).
+// Part of the translation unit lbm_f64.hip (device code of liblbm_d2q9.so, gfx950 only); include/lbm_d2q9_f64.h states the contract
+// (the digests': include/lbm_d2q9_f64_digest.h).
 // From common.h it takes kBlock, wave_sum, block_sum and lds_barrier, nothing of the float path's arithmetic.
 #pragma once
 #include "common.h"
@@ -357,6 +358,44 @@ __global__ void __launch_bounds__(kBlock) lbm64_observables_kernel(const double*
   }
   *reinterpret_cast<d2*>(obs + 4 * c) = d2{o[0], o[1]};
   *reinterpret_cast<d2*>(obs + 4 * c + 2) = d2{o[2], o[3]};
+}
+
+// The state digest of include/lbm_d2q9_f64_digest.h, one per row: block b digests the nx cells of row b of `grid` (already offset to
+// the first cell of the first row wanted), which is row global_row0 + b of the whole grid, into row_digests[b].  The planes are read as
+// 64-bit integers, like the AoS<->SoA kernels: no arithmetic instruction sees a NaN payload or a denormal.  Every index is formed in
+// 64 bits: (row * nx + x) * 9 + k passes 2^32 long before the cell index does.  Lanes stride along x (coalesced per plane), the wave's
+// lanes join by the butterfly, the waves' sums meet in LDS; integer sums do not depend on the order, and there is no atomic.  Reads
+// the grid, writes row_digests, nothing else.
+__global__ void __launch_bounds__(kBlock) lbm64_row_digest_kernel(const unsigned long long* grid, size_t ps, uint32_t nx, unsigned long long global_row0,
+                                                                  unsigned long long* row_digests)
+{
+  __shared__ unsigned long long red[kBlock / 64];
+  const unsigned long long* row = grid + static_cast<size_t>(blockIdx.x) * nx;
+  const unsigned long long cell0 = (global_row0 + blockIdx.x) * static_cast<unsigned long long>(nx);   // the row's first cell in the whole grid
+  unsigned long long h = 0;
+  for (uint32_t x = threadIdx.x; x < nx; x += kBlock) {              // nx < 2^31: x + kBlock does not wrap
+    unsigned long long f[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] = row[k * ps + x];
+    const unsigned long long idx0 = (cell0 + x) * 9ull;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      unsigned long long z = f[k] ^ ((idx0 + static_cast<unsigned long long>(k)) * 0x9E3779B97F4A7C15ull);
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      h += z ^ (z >> 31);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off, 64);   // every lane of the wave is back here: the loop has ended
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = h;
+  lds_barrier();
+  if (threadIdx.x == 0) {
+    unsigned long long t = red[0];
+#pragma unroll
+    for (int w = 1; w < kBlock / 64; ++w) t += red[w];
+    row_digests[blockIdx.x] = t;
+  }
 }
 
 }  // namespace

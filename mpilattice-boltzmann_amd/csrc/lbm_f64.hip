@@ -7,7 +7,8 @@
 // epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  lbm_step_kernel_f64<CELLS, NT> makes one
 // step per launch; with LBM64_FLAG_TILE_STEPS a small grid is advanced by lbm_tile_kernel_f64<T, H, FULL> (kernels/tile64.h), up to H
 // steps per launch; with LBM64_FLAG_MULTI_STEPS a large one by lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h), up to K.  Whole
-// periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph, no state digest).  What a context gets of all that
+// periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph; the state digest is lbm_digest64_grid, at the end of
+// this unit: include/lbm_d2q9_f64_digest.h).  What a context gets of all that
 // is decided in lbm_plan.cpp (Plan64 and PlanMulti64, lbm_internal.h); this unit allocates and launches by the plans.  What it does
 // with its grid as lbm_rows64.hip does with a rank's row block (allocation, chunked read-outs, the velocity sum) is in lbm_f64_slab.h.
 //
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "lbm_d2q9_f64.h"
+#include "lbm_d2q9_f64_digest.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 #include "kernels/step64.h"
@@ -306,6 +308,25 @@ int lbm64_describe(const lbm64_ctx* c, char* kernel_name, size_t len, long long*
   if (blocks) *blocks = plan.tile_kernel ? plan.n_tiles : plan.blocks;
   if (cells_per_block) *cells_per_block = plan.tile_kernel ? static_cast<long long>(plan.tile_T) * plan.tile_T : static_cast<long long>(kBlock) * plan.iters * plan.lane_cells;
   if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->slab.ncells * sizeof(double));
+  return 0;
+}
+
+// include/lbm_d2q9_f64_digest.h: one digest per row of the current grid.  Reads the grid on the slab's stream and leaves the context as
+// it was: cur, the partials, the counter and the events of the last run are not touched.
+int lbm_digest64_grid(lbm64_ctx* c, int y_begin, int y_end, unsigned long long* row_digests, unsigned long long* digest)
+{
+  if (!c) { lbm_internal::set_error("lbm_digest64_grid: null context"); return 1; }
+  if (!row_digests && !digest) { lbm_internal::set_error("lbm_digest64_grid: both output pointers are null"); return 1; }
+  if (y_begin < 0 || y_end > c->p.ny || y_begin > y_end) { lbm_internal::set_error("lbm_digest64_grid: rows outside the grid (0 <= y_begin <= y_end <= ny)"); return 1; }
+  const int rows = y_end - y_begin;
+  if (rows == 0) { if (digest) *digest = 0; return 0; }
+  std::vector<unsigned long long> own;
+  if (!row_digests) { own.resize(static_cast<size_t>(rows)); row_digests = own.data(); }
+  HIP_TRY(hipSetDevice(c->slab.device));
+  unsigned long long* dev = nullptr;
+  const int bad = slab64_enqueue_row_digests(c->slab, c->cur, c->p.nx, y_begin, rows, y_begin, &dev);
+  if (slab64_collect_row_digests(c->slab, dev, rows, row_digests) || bad) return 1;
+  if (digest) *digest = slab64_digest_sum(row_digests, rows);
   return 0;
 }
 

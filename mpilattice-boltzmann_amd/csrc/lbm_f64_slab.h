@@ -153,6 +153,39 @@ int slab64_get_observables(const Slab64& s, int g, size_t chunk, double* obs)
   return 0;
 }
 
+// The row digests (include/lbm_d2q9_f64_digest.h) of `rows` owned rows of grid `g` from the slab's row `local_row` on, which is row
+// `global_row` of the whole grid.  In two halves, so that a caller with several slabs enqueues on all of them before it waits for one:
+// slab64_enqueue_row_digests launches lbm64_row_digest_kernel on the slab's stream into a device array it allocates (*dev);
+// slab64_collect_row_digests copies that array to `out`, waits for the stream and frees it (call it after a failed enqueue too:
+// *dev may be set).  rows >= 1.  Ghost rows are never reached: local_row counts from s.owned(g).  Touches nothing else of the slab.
+int slab64_enqueue_row_digests(const Slab64& s, int g, int nx, int local_row, int rows, long long global_row, unsigned long long** dev)
+{
+  HIP_TRY(hipMalloc(dev, sizeof(unsigned long long) * static_cast<size_t>(rows)));
+  hipLaunchKernelGGL(lbm64_row_digest_kernel, dim3(static_cast<unsigned>(rows)), dim3(kBlock), 0, s.stream,
+                     reinterpret_cast<const unsigned long long*>(s.owned(g) + static_cast<size_t>(local_row) * static_cast<size_t>(nx)), s.ps,
+                     static_cast<uint32_t>(nx), static_cast<unsigned long long>(global_row), *dev);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int slab64_collect_row_digests(const Slab64& s, unsigned long long* dev, int rows, unsigned long long* out)
+{
+  if (!dev) return 0;
+  hipError_t e = hipMemcpyAsync(out, dev, sizeof(unsigned long long) * static_cast<size_t>(rows), hipMemcpyDeviceToHost, s.stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
+  (void)hipFree(dev);
+  HIP_TRY(e);
+  return 0;
+}
+
+// What both digest entry points return from the row digests of their range: the wrap-around sum.
+unsigned long long slab64_digest_sum(const unsigned long long* row_digests, int rows)
+{
+  unsigned long long sum = 0;
+  for (int i = 0; i < rows; ++i) sum += row_digests[i];
+  return sum;
+}
+
 // av_velocity's sum over the owned free cells of grid `g`: each block's sum added to *total, in block order (no subtotal of the slab:
 // a caller that passes one accumulator from slab to slab adds every block of every slab to it serially).
 int slab64_add_velocity_sum(const Slab64& s, int g, double* total)

@@ -16,6 +16,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_d2q9_f64.h"
+#include "lbm_d2q9_f64_digest.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 
@@ -381,6 +382,36 @@ int lbm64_write_av_vels(const char* path, const double* av_vels, int n)
   if (!fp) { set_error("could not open file output file"); return 1; }         // :1131
   for (int i = 0; i < n; ++i) std::fprintf(fp, "%d:\t%.12E\n", i, av_vels[i]); // :1136
   std::fclose(fp);
+  return 0;
+}
+
+// ---- include/lbm_d2q9_f64_digest.h, the host form: the definition as a plain loop over a state in host memory -------------------------
+int lbm_digest64_abi_version(void) { return LBM_DIGEST64_ABI_VERSION; }
+
+int lbm_digest64_host(const double* cells_aos, int nx, int rows, long long y0, unsigned long long* row_digests, unsigned long long* digest)
+{
+  if (!row_digests && !digest) { set_error("lbm_digest64_host: both output pointers are null"); return 1; }
+  if (nx < 1) { set_error("lbm_digest64_host: nx must be positive"); return 1; }
+  if (rows < 0) { set_error("lbm_digest64_host: negative row count"); return 1; }
+  if (y0 < 0) { set_error("lbm_digest64_host: negative first row y0"); return 1; }
+  if (!cells_aos && rows > 0) { set_error("lbm_digest64_host: null state"); return 1; }
+  unsigned long long sum = 0;
+  for (int r = 0; r < rows; ++r) {
+    const double* row = cells_aos + static_cast<size_t>(r) * static_cast<size_t>(nx) * 9;
+    const unsigned long long idx0 = (static_cast<unsigned long long>(y0) + static_cast<unsigned long long>(r)) * static_cast<unsigned long long>(nx) * 9ull;
+    unsigned long long h = 0;
+    for (size_t i = 0; i < static_cast<size_t>(nx) * 9; ++i) {           // i = x * 9 + k
+      unsigned long long z;
+      std::memcpy(&z, row + i, sizeof z);                                  // the object representation: no arithmetic sees the value
+      z ^= (idx0 + i) * 0x9E3779B97F4A7C15ull;
+      z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+      z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+      h += z ^ (z >> 31);
+    }
+    if (row_digests) row_digests[r] = h;
+    sum += h;
+  }
+  if (digest) *digest = sum;
   return 0;
 }
 

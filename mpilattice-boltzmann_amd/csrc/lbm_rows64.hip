@@ -59,6 +59,7 @@
 #include <vector>
 
 #include "lbm_d2q9_f64_rows.h"
+#include "lbm_d2q9_f64_digest.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
 #include "kernels/rows64.h"
@@ -553,6 +554,52 @@ int lbm_rows64_describe(const lbm_rows64* c, char* kernel_name, size_t len, int*
   if (blocks) *blocks = most->plan.blocks;
   if (cells_per_block) *cells_per_block = static_cast<long long>(kBlock) * most->plan.iters * most->plan.lane_cells;
   if (state_bytes) *state_bytes = bytes;
+  return 0;
+}
+
+// include/lbm_d2q9_f64_digest.h: one digest per row of the current grids.  Every rank that owns rows of [y_begin, y_end) digests its
+// share on its device and stream (all ranks are idle: the last call synchronised them), every rank enqueued before any is waited for;
+// the share of rank k lands at row_digests + (its first row of the range - y_begin).  A rank's first owned row is row plan.y0 of the
+// whole grid and lies slab.first doubles into its storage (one ghost row, or K): slab.owned() skips them.  Leaves the run as it was:
+// cur, the partials, the counters and the events of the last run are not touched.
+int lbm_digest64_rows(lbm_rows64* c, int y_begin, int y_end, unsigned long long* row_digests, unsigned long long* digest)
+{
+  if (!c) { lbm_internal::set_error("lbm_digest64_rows: null run"); return 1; }
+  if (!row_digests && !digest) { lbm_internal::set_error("lbm_digest64_rows: both output pointers are null"); return 1; }
+  if (y_begin < 0 || y_end > c->p.ny || y_begin > y_end) { lbm_internal::set_error("lbm_digest64_rows: rows outside the grid (0 <= y_begin <= y_end <= ny)"); return 1; }
+  const int rows = y_end - y_begin;
+  if (rows == 0) { if (digest) *digest = 0; return 0; }
+  std::vector<unsigned long long> own;
+  if (!row_digests) { own.resize(static_cast<size_t>(rows)); row_digests = own.data(); }
+  c->current_device = -1;
+  const size_t nranks = c->ranks.size();
+  std::vector<unsigned long long*> dev(nranks, nullptr);
+  // the rows of the range that rank r owns: [lo, hi) of the whole grid
+  auto share = [&](size_t r, int* lo, int* hi) {
+    const lbm_internal::PlanRows64& plan = c->ranks[r].plan;
+    *lo = std::max(y_begin, plan.y0);
+    *hi = std::min(y_end, plan.y0 + plan.ny_local);
+    return *lo < *hi;
+  };
+  int bad = 0, lo = 0, hi = 0;
+  for (size_t r = 0; r < nranks && !bad; ++r) {
+    if (!share(r, &lo, &hi)) continue;
+    const Rank64& k = c->ranks[r];
+    bad = use_device(c, k.slab.device) || slab64_enqueue_row_digests(k.slab, c->cur, c->p.nx, lo - k.plan.y0, hi - lo, lo, &dev[r]);
+  }
+  std::string first_error;
+  if (bad) first_error = lbm_last_error();
+  for (size_t r = 0; r < nranks; ++r) {          // every rank that got a device array, after a failure too: the array is freed here
+    if (!dev[r] || !share(r, &lo, &hi)) continue;
+    const Rank64& k = c->ranks[r];
+    const int no_device = use_device(c, k.slab.device);
+    if ((slab64_collect_row_digests(k.slab, dev[r], hi - lo, row_digests + (lo - y_begin)) || no_device) && !bad) {
+      bad = 1;
+      first_error = lbm_last_error();
+    }
+  }
+  if (bad) { lbm_internal::set_error(first_error); return 1; }
+  if (digest) *digest = slab64_digest_sum(row_digests, rows);
   return 0;
 }
 

@@ -16,6 +16,9 @@ with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_mult
 (include/lbm_d2q9_f64_rows.h): Grid64's methods, Grid64's populations bit for bit for every rank count.  With
 `flags=f64.FLAG_ROWS_MULTI_STEPS`, ranks that 32 x 16 tiles cover advance several steps per launch and exchange
 (lbm_rows_multi_kernel_f64): the same populations.
+
+`g.digest()` of either class gives one 64-bit digest per row of the current state and their sum (include/lbm_d2q9_f64_digest.h), taken
+on the device; `f64.digest_host(cells, nx)` the same of an array, `f64.differing_rows(a, b)` the rows in which two objects differ.
 """
 from __future__ import annotations
 
@@ -187,6 +190,12 @@ class Grid64:
         check(self._lib.lbm64_last_run_kernel_ms(self._ctx, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def digest(self, y_begin: Optional[int] = None, y_end: Optional[int] = None) -> tuple[np.ndarray, int]:
+        """(row digests uint64 (y_end - y_begin,), their wrap-around sum) of global rows [y_begin, y_end) of the current state (default:
+        every row), taken on the device (include/lbm_d2q9_f64_digest.h): 8 bytes per row come back.  The state and the next run's
+        results are as without the call."""
+        return _device_digest(load_digest_library().lbm_digest64_grid, self._ctx, self.params.ny, y_begin, y_end)
+
     def describe(self) -> dict:
         name = C.create_string_buffer(256)
         blocks, per_block, nbytes = C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
@@ -316,6 +325,10 @@ class Rows64:
         check(self._lib.lbm_rows64_last_run_ms(self._run, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def digest(self, y_begin: Optional[int] = None, y_end: Optional[int] = None) -> tuple[np.ndarray, int]:
+        """Grid64.digest's pair for the whole grid's rows [y_begin, y_end), each rank digesting the rows it owns on its device."""
+        return _device_digest(load_digest_library().lbm_digest64_rows, self._run, self.params.ny, y_begin, y_end)
+
     def describe(self) -> dict:
         name = C.create_string_buffer(256)
         nranks, blocks, per_block, nbytes = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
@@ -323,5 +336,69 @@ class Rows64:
         return {"kernel": name.value.decode(), "nranks": nranks.value, "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
 
 
-__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_ROWS_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
+# ---- state digests (include/lbm_d2q9_f64_digest.h): a signature table of their own, beside EXPORTS and ROWS_EXPORTS, which stay as they are ----
+DIGEST_ABI_VERSION = 1
+_ull = C.c_ulonglong
+_DIGEST_SIGNATURES = {
+    "lbm_digest64_abi_version": (C.c_int, []),
+    "lbm_digest64_host": (C.c_int, [_P(C.c_double), C.c_int, C.c_int, C.c_longlong, _P(_ull), _P(_ull)]),
+    "lbm_digest64_grid": (C.c_int, [_ctx, C.c_int, C.c_int, _P(_ull), _P(_ull)]),
+    "lbm_digest64_rows": (C.c_int, [_ctx, C.c_int, C.c_int, _P(_ull), _P(_ull)]),
+}
+DIGEST_EXPORTS = tuple(_DIGEST_SIGNATURES)
+
+_digest_typed = None
+
+
+def load_digest_library() -> C.CDLL:
+    """liblbm_d2q9.so with the lbm64_*, the lbm_rows64_* and the lbm_digest64_* prototypes set.  Raises if the library or one of the
+    symbols is absent."""
+    global _digest_typed
+    if _digest_typed is None:
+        lib = load_rows_library()
+        for name, (res, args) in _DIGEST_SIGNATURES.items():
+            fn = getattr(lib, name)           # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
+        if lib.lbm_digest64_abi_version() != DIGEST_ABI_VERSION:
+            raise RuntimeError(f"liblbm_d2q9.so digest ABI {lib.lbm_digest64_abi_version()} != binding {DIGEST_ABI_VERSION}: rebuild")
+        _digest_typed = lib
+    return _digest_typed
+
+
+def _as_ull_ptr(a: np.ndarray):
+    assert a.dtype == np.uint64 and a.flags.c_contiguous
+    return a.ctypes.data_as(_P(_ull))
+
+
+def digest_host(cells: np.ndarray, nx: int, y0: int = 0) -> tuple[np.ndarray, int]:
+    """(row digests uint64 (rows,), their wrap-around sum) of AoS cells in host memory that are global rows [y0, y0 + rows) of a grid
+    `nx` cells wide; rows = cells.size / (9 * nx).  No GPU.  The bits of `cells` are digested as they are (NaN payloads, signed zeros)."""
+    cells = np.ascontiguousarray(cells, dtype=np.float64)
+    nx = int(nx)
+    if nx >= 1 and cells.size % (9 * nx) != 0:
+        raise ValueError("cells must hold whole rows of nx * 9 doubles")
+    rows = cells.size // (9 * nx) if nx >= 1 else 0
+    out = np.zeros(max(rows, 1), dtype=np.uint64)
+    total = _ull(0)
+    check(load_digest_library().lbm_digest64_host(_capi.as_double_ptr(cells), nx, rows, int(y0), _as_ull_ptr(out), C.byref(total)))
+    return out[:rows], total.value
+
+
+def _device_digest(entry, handle, ny: int, y_begin, y_end) -> tuple[np.ndarray, int]:
+    y_begin = 0 if y_begin is None else int(y_begin)
+    y_end = int(ny) if y_end is None else int(y_end)
+    out = np.zeros(max(y_end - y_begin, 1), dtype=np.uint64)
+    total = _ull(0)
+    check(entry(handle, y_begin, y_end, _as_ull_ptr(out), C.byref(total)))
+    return out[:y_end - y_begin], total.value
+
+
+def differing_rows(a, b) -> list[int]:
+    """The global rows whose digests differ between two objects of either class (Grid64, Rows64) on grids of the same shape."""
+    if (a.params.nx, a.params.ny) != (b.params.nx, b.params.ny):
+        raise ValueError("differing_rows: the two grids differ in shape")
+    return [int(y) for y in np.nonzero(a.digest()[0] != b.digest()[0])[0]]
+
+
+__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_ROWS_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
            "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]
