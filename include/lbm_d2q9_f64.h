@@ -32,8 +32,8 @@
  * OUT OF SCOPE of this mode (use lbm_d2q9.h; for row blocks in double precision inside one process, lbm_d2q9_f64_rows.h): row or tile
  * partitions and every halo transport (peer-to-peer, RCCL, split-phase calls)
  * — a context is a whole periodic grid on one GPU (several steps per launch are opt-in: LBM64_FLAG_TILE_STEPS for small grids,
- * LBM64_FLAG_MULTI_STEPS for large ones that 32 x 16 tiles cover; without them, and on every grid they do not take, every step is one
- * launch of lbm_step_kernel_f64); the
+ * LBM64_FLAG_MULTI_STEPS for large ones that 32 x 16 tiles cover, LBM64_FLAG_MULTI_ANY_SIZE for large ones of any even width; without
+ * them, and on every grid they do not take, every step is one launch of lbm_step_kernel_f64); the
  * fused arithmetic (LBM_FLAG_FUSED_ARITH); hipGraph replay (LBM_FLAG_GRAPH).  The state digest of doubles, lbm_state_checksum's
  * counterpart, is lbm_digest64_grid of lbm_d2q9_f64_digest.h: one digest per row, under names of its own.
  */
@@ -64,6 +64,19 @@ extern "C" {
  * this flag.  A run of n steps is floor(n / K) launches of K steps and at most one shorter launch, the last.  Populations are the
  * same bits either way; av_vels differs in the order of its additions only (above).  lbm_create of lbm_d2q9.h ignores this bit. */
 #define LBM64_FLAG_MULTI_STEPS 1024u
+
+/* lbm64_create flag, wherever LBM64_FLAG_MULTI_STEPS is taken (alone, with a store form, with the two flags above): it means
+ * LBM64_FLAG_MULTI_STEPS, and takes the large grids that 32 x 16 tiles do NOT cover exactly as well.  A grid the tiles cover runs
+ * precisely as under LBM64_FLAG_MULTI_STEPS (the same kernel, name and av_vels bits).  Any other grid with nx even and >= 32, ny >= 16
+ * and at least LBM_TUNE_MULTI64_MIN cells, which the tiled kernel does not take, advances K steps per launch with the EDGE-TILE form of
+ * lbm_multi_kernel_f64: ceil(nx / 32) x ceil(ny / 16) tiles, tile (tx, ty) starting at x0 = min(32 tx, nx - 32), y0 = min(16 ty,
+ * ny - 16) — a tile that would hang over the edge is shifted back inside the grid, over its neighbour — and OWNING (storing, and
+ * counting in the sums) only its cells at tile-local x >= 32 tx - x0 and y >= 16 ty - y0: every cell of the grid has exactly one
+ * owner.  The frame, the sub-steps, the cell update and the recomputed ring are the kernel's as they are.  The av_vels tree is the
+ * one stated above for lbm_multi_kernel_f64, over the ceil(nx / 32) * ceil(ny / 16) tiles.  Odd nx, nx < 32 and ny < 16 run
+ * lbm_step_kernel_f64 exactly as without the flag.  Populations are the same bits either way.  Row partitions (lbm_d2q9_f64_rows.h)
+ * refuse this bit; lbm_create of lbm_d2q9.h ignores it. */
+#define LBM64_FLAG_MULTI_ANY_SIZE 4096u
 
 /* t_param (d2q9-bgk.c:79-90) with its three floats as doubles. */
 typedef struct lbm64_params {
@@ -102,7 +115,8 @@ int lbm64_write_av_vels(const char* path, const double* av_vels, int n);
 /* A whole periodic nx x ny grid (ny >= 3) on GPU `device`, in the initial state of d2q9-bgk.c:880-902.  obstacles = ny*nx ints.
  * flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default once the two grids
  * exceed the Infinity Cache), each with or without LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS (with both, the tiled kernel where
- * it takes the grid, otherwise lbm_multi_kernel_f64 where that does); any other flag is refused. */
+ * it takes the grid, otherwise lbm_multi_kernel_f64 where that does) and LBM64_FLAG_MULTI_ANY_SIZE (LBM64_FLAG_MULTI_STEPS, and its
+ * edge-tile form where the tiles do not cover the grid); any other flag is refused. */
 int lbm64_create(lbm64_ctx** ctx, const lbm64_params* params, int free_cells, const int* obstacles, int device, unsigned flags);
 int lbm64_destroy(lbm64_ctx* ctx);
 
@@ -130,7 +144,8 @@ int lbm64_last_run_kernel_ms(lbm64_ctx* ctx, double* ms, int* launches);
  * a block advances (256 lanes x cells per lane x units per lane) and the bytes of the two grids.  A context that
  * LBM64_FLAG_TILE_STEPS advances with the tiled kernel: "lbm_tile_kernel_f64<T, H>", the tiles, T * T.  One that LBM64_FLAG_MULTI_STEPS
  * advances with the multi-step kernel: "lbm_multi_kernel_f64<K>" ("lbm_multi_kernel_f64<K,nt>" with non-temporal stores), the tiles,
- * 32 * 16. */
+ * 32 * 16.  One that LBM64_FLAG_MULTI_ANY_SIZE advances with the edge-tile form: "lbm_multi_kernel_f64<K,edge>" ("<K,nt,edge>"),
+ * ceil(nx / 32) * ceil(ny / 16), 512 (the cells a block computes in its last sub-step; it owns fewer where it is shifted). */
 int lbm64_describe(const lbm64_ctx* ctx, char* kernel_name, size_t len, long long* blocks, long long* cells_per_block, long long* state_bytes);
 
 #ifdef __cplusplus

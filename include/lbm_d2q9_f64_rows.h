@@ -49,7 +49,8 @@
  *
  * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; uneven
  * ranks under LBM_ROWS64_FLAG_MULTI_STEPS (they run the one-step kernel); overlap of a rank's interior rows or tiles with the exchange.
- * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused.
+ * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused, and so is its LBM64_FLAG_MULTI_ANY_SIZE: several steps per
+ * exchange on ranks that 32 x 16 tiles do not cover exactly (the edge-tile form of lbm_d2q9_f64.h for row blocks) are a follow-up.
  */
 #ifndef LBM_D2Q9_F64_ROWS_H
 #define LBM_D2Q9_F64_ROWS_H

@@ -17,7 +17,8 @@
  * which is what the reference's shipped results and README were produced with; the same five lines and two files.  One GPU only
  * (LBM_GPUS > 1 is refused); of LBM_FLAGS it takes 1 and 2 (LBM_FLAG_NT_STORES / LBM_FLAG_NO_NT_STORES), 512 (LBM64_FLAG_TILE_STEPS:
  * a small grid advances several steps per launch, the same populations and files) and 1024 (LBM64_FLAG_MULTI_STEPS: the same for a
- * large grid that 32 x 16 tiles cover, with lbm_multi_kernel_f64), in any sum, and has no other default.  LBM_DESCRIBE=1 adds one
+ * large grid that 32 x 16 tiles cover, with lbm_multi_kernel_f64) and 4096 (LBM64_FLAG_MULTI_ANY_SIZE: 1024, and large grids of any even
+ * width from 32 and any height from 16 with the kernel's edge-tile form), in any sum, and has no other default.  LBM_DESCRIBE=1 adds one
  * line on stderr: the kernel that advanced the grid (lbm64_describe) and the step launches of the run.
  * LBM_PRECISION=double LBM64_RANKS=N (N >= 1) runs the same deck as N row blocks (include/lbm_d2q9_f64_rows.h): the rows are
  * partitioned by the reference's rule, rank r lives on device LBM_DEVICES[r] (a comma list; default r % device count; ranks may share

@@ -1,4 +1,4 @@
-// multi64.h — lbm_multi_kernel_f64<K, NT, FULL>: up to K steps per launch of the double-precision mode, for the large whole grids whose
+// multi64.h — lbm_multi_kernel_f64<K, NT, FULL, EDGE>: up to K steps per launch of the double-precision mode, for the large whole grids whose
 // one-step launches are bound by HBM (144 B per cell-step).  Part of the translation unit lbm_f64.hip (gfx950 only, -ffp-contract=off).
 //
 // lbm_multi_kernel's scheme (kernels/multi.h) with every object a double.  A block of kMulti64Lanes lanes owns a TX x TY tile
@@ -10,7 +10,7 @@
 //   sub-step s > 1  works on the tile grown by e = k-s cells each way, one cell per lane and item: a lane reads the nine neighbours of ALL
 //                   its items (at most two: a region has up to 2 x lanes cells) from the frame into registers and computes; then a
 //                   barrier, the write-back, a barrier — otherwise one pass's results would feed another's neighbours;
-//   the last one    covers the owned tile, one cell per lane, and stores to the destination grid: x-neighbouring lanes exchange halves
+//   the last one    covers the tile, one cell per lane, and stores to the destination grid: x-neighbouring lanes exchange halves
 //                   (one DPP move per population pair) so that every store is 16 bytes, non-temporal where NT.
 // k = 1 (a tail): sub-step 1 is the last and stores its pairs directly.
 // Ring cells are recomputed by the neighbouring blocks with the same arithmetic, so no block waits for another.  The cell update is
@@ -39,7 +39,7 @@ struct Multi64Args {
   const uint32_t* mask;
   size_t ps;
   int nx, ny;
-  int tiles_x;                 // nx / TX
+  int tiles_x;                 // nx / TX (EDGE: rounded up)
   int ksteps;                  // 1..K steps in this launch (FULL: K)
   double omega, accel_w1, accel_w2;
   int accel_row;               // ny-2
@@ -56,7 +56,12 @@ struct Multi64Args {
 constexpr int kMulti64WavesPerSimd = 2 * (kMulti64Lanes / 64) / 4;
 
 // FULL: the launch makes exactly K steps, so every region size is a compile-time constant.
-template <int K, bool NT, bool FULL>
+// EDGE (LBM64_FLAG_MULTI_ANY_SIZE): ceil(nx / TX) x ceil(ny / TY) tiles on a grid they do not cover exactly (nx even and >= TX, ny >= TY).
+// Tile (tx, ty) starts at x0 = min(TX tx, nx - TX), y0 = min(TY ty, ny - TY): a tile of the last column or row is shifted back inside
+// the grid, over its neighbour, and owns only its cells at tile-local x >= TX tx - x0, y >= TY ty - y0, so every cell of the grid has
+// exactly one owner.  x0 and the x bound are even (nx is): pairs stay aligned and are owned whole.  A tile's cells it does not own
+// are computed like ring cells, for their neighbours; only owned cells are stored and counted.  All else is the kernel as it is.
+template <int K, bool NT, bool FULL, bool EDGE = false>
 __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi_kernel_f64(const Multi64Args a)
 {
   static_assert(multi64_k_ok(K), "unsupported steps per launch");
@@ -92,6 +97,10 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int k_total = FULL ? K : a.ksteps;
   const size_t ps = a.ps;
+  // the tile's first cell (EDGE: shifted back inside the grid).  Formed where it is used, x before y, not here: the existing instantiations
+  // then compile to the instructions they had before EDGE was a parameter (profiles/r20/device_asm_identical.txt).
+  auto tile_x0 = [&]() __attribute__((always_inline)) { return EDGE ? min(tx * TX, a.nx - TX) : tx * TX; };
+  auto tile_y0 = [&]() __attribute__((always_inline)) { return EDGE ? min(ty * TY, a.ny - TY) : ty * TY; };
 
   double acc[kMulti64Accs];
 #pragma unroll
@@ -105,13 +114,15 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi
     const bool last = !FULL && e == 0;
     if (tid < wp * hy) {
       const int ry = FULL ? tid / wp : small_div(tid, wp), rx = 2 * (tid - ry * wp);
-      int x = tx * TX - gx + rx; if (x < 0) x += a.nx; else if (x >= a.nx) x -= a.nx;      // -gx .. nx + gx - 2, and nx >= TX > gx
-      int y = ty * TY - e + ry;  if (y < 0) y += a.ny; else if (y >= a.ny) y -= a.ny;      // -e .. ny + e - 1, and ny >= TY > e
+      const int x0 = tile_x0(), own_x = EDGE ? tx * TX - x0 : 0;
+      int x = x0 - gx + rx; if (x < 0) x += a.nx; else if (x >= a.nx) x -= a.nx;           // -gx .. nx + gx - 2, and nx >= TX > gx
+      const int y0 = tile_y0(), own_y = EDGE ? ty * TY - y0 : 0;
+      int y = y0 - e + ry;  if (y < 0) y += a.ny; else if (y >= a.ny) y -= a.ny;           // -e .. ny + e - 1, and ny >= TY > e
       const uint32_t cell = static_cast<uint32_t>(y) * static_cast<uint32_t>(a.nx) + static_cast<uint32_t>(x);
       const uint32_t mbits = (a.mask[cell >> 5] >> (cell & 31u)) & 3u;                       // cell is even: both bits in one word
       const bool on_row = y == a.accel_row;
       const bool accel = on_row && (!last || a.accel_last);
-      const bool owned = rx >= gx && rx < gx + TX && ry >= e && ry < e + TY;                // both cells of a pair, or neither
+      const bool owned = rx >= gx + own_x && rx < gx + TX && ry >= e + own_y && ry < e + TY;   // both cells of a pair, or neither
       d2 p[9];
       pull_pair_f64(a.src, ps, static_cast<uint32_t>(a.nx), rows_of(static_cast<uint32_t>(a.nx), static_cast<uint32_t>(a.ny), static_cast<uint32_t>(y)), static_cast<uint32_t>(x), p);
       if (last) {
@@ -121,13 +132,16 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi
           double t[9], q[9];
 #pragma unroll
           for (int k = 0; k < 9; ++k) t[k] = p[k][j];
-          acc[0] += finish_cell_f64(t, (mbits >> j) & 1u, a.omega, accel, a.accel_w1, a.accel_w2, q);   // e = 0: every cell is owned
+          const double term = finish_cell_f64(t, (mbits >> j) & 1u, a.omega, accel, a.accel_w1, a.accel_w2, q);
+          if (!EDGE || owned) acc[0] += term;                                                // e = 0: every cell is owned, except in a shifted tile
 #pragma unroll
           for (int k = 0; k < 9; ++k) out[k][j] = q[k];
         }
         double* d = a.dst + cell;
+        if (!EDGE || owned) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) store2<NT>(d + k * ps, out[k]);
+          for (int k = 0; k < 9; ++k) store2<NT>(d + k * ps, out[k]);
+        }
       } else {
         const int c = (EY - e + ry) * FX + (EX - gx + rx);
         const uint32_t common = (owned ? 2u : 0u) | (on_row ? 4u : 0u);
@@ -188,7 +202,9 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi
       // 0, 2, 4, 6, 8, the odd lane 1, 3, 5, 7: each sends the other the half it does not store (bits, by a DPP move).
       const int ry = tid / TX, rx = tid - ry * TX;
       const bool odd = (tid & 1) != 0;
-      double* d = a.dst + (static_cast<size_t>(ty * TY + ry) * a.nx + static_cast<size_t>(tx * TX + (rx & ~1)));
+      const int x0 = tile_x0(), y0 = tile_y0(), own_x = EDGE ? tx * TX - x0 : 0, own_y = EDGE ? ty * TY - y0 : 0;
+      const bool stores = !EDGE || (rx >= own_x && ry >= own_y);      // owned (own_x is even: both lanes of a pair, or neither); every lane makes the exchange
+      double* d = a.dst + (static_cast<size_t>(y0 + ry) * a.nx + static_cast<size_t>(x0 + (rx & ~1)));
 #pragma unroll
       for (int j = 0; j < 5; ++j) {
         constexpr int kLastOdd = 7;
@@ -197,7 +213,7 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_multi
         const double send = odd ? out[0][ke] : out[0][ko];
         const double recv = dpp_full<0xB1>(send);                      // quad_perm [1,0,3,2]: lane l ^ 1
         const d2 v = odd ? d2{recv, mine} : d2{mine, recv};
-        if (j < 4 || !odd) store2<NT>(d + static_cast<size_t>(odd ? ko : ke) * ps, v);
+        if ((j < 4 || !odd) && stores) store2<NT>(d + static_cast<size_t>(odd ? ko : ke) * ps, v);
       }
     }
   };

@@ -6,10 +6,11 @@
 // pull-stream, moments + equilibrium, BGK relaxation / bounce-back, the sum|u| terms into per-block partials, accelerate_flow as an
 // epilogue on row ny-2 for the NEXT step, av_vels[t] folded by block 0 of the next launch.  lbm_step_kernel_f64<CELLS, NT> makes one
 // step per launch; with LBM64_FLAG_TILE_STEPS a small grid is advanced by lbm_tile_kernel_f64<T, H, FULL> (kernels/tile64.h), up to H
-// steps per launch; with LBM64_FLAG_MULTI_STEPS a large one by lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h), up to K.  Whole
+// steps per launch; with LBM64_FLAG_MULTI_STEPS a large one by lbm_multi_kernel_f64<K, NT, FULL> (kernels/multi64.h), up to K, and with
+// LBM64_FLAG_MULTI_ANY_SIZE by its edge-tile form where the tiles do not cover the grid.  Whole
 // periodic grids on one GPU only (no partitions, no fused arithmetic, no hipGraph; the state digest is lbm_digest64_grid, at the end of
 // this unit: include/lbm_d2q9_f64_digest.h).  What a context gets of all that
-// is decided in lbm_plan.cpp (Plan64 and PlanMulti64, lbm_internal.h); this unit allocates and launches by the plans.  What it does
+// is decided in lbm_plan.cpp (Plan64 and PlanMultiAny64, lbm_internal.h); this unit allocates and launches by the plans.  What it does
 // with its grid as lbm_rows64.hip does with a rank's row block (allocation, chunked read-outs, the velocity sum) is in lbm_f64_slab.h.
 //
 // Layout in HBM: struct-of-arrays, 9 planes of ny*nx doubles at a padded, skewed plane stride (the float path's rule in elements: lbm_plan.cpp plane_stride_floats), two grids
@@ -43,7 +44,7 @@ struct lbm64_ctx {
   int free_cells = 0;
   double free_cells_inv = 0.0;
   lbm_internal::Plan64 plan{};       // kernels, launch shapes and sizes (lbm_plan.cpp plan64_whole): written once
-  lbm_internal::PlanMulti64 multi{}; // lbm_multi_kernel_f64's part of them (plan64_multi): written once
+  lbm_internal::PlanMultiAny64 multi{};   // lbm_multi_kernel_f64's part of them, the edge-tile form included (plan64_multi_any): written once
   Slab64 slab;                       // the whole grid on its device (lbm_f64_slab.h)
   int cur = 0;
   double accel_w1 = 0.0, accel_w2 = 0.0;
@@ -74,6 +75,15 @@ using Multi64Kernel = void (*)(Multi64Args);
 constexpr Multi64Kernel kMulti64Kernels[kMulti64Rows] = {LBM_MULTI64_ROWS(2), LBM_MULTI64_ROWS(3), LBM_MULTI64_ROWS(4)};
 #undef LBM_MULTI64_ROWS
 static_assert(kMulti64MinK == 2 && kMulti64MaxK == 4 && multi64_row(2, false, true) == 1 && multi64_row(3, true, false) == 6 && multi64_row(4, true, true) == 11, "the order of kMulti64Kernels");
+// and every instantiation of its edge-tile form (LBM64_FLAG_MULTI_ANY_SIZE), in the same order
+#define LBM_MULTI64_EDGE_ROWS(K) &lbm_multi_kernel_f64<K, false, false, true>, &lbm_multi_kernel_f64<K, false, true, true>, &lbm_multi_kernel_f64<K, true, false, true>, &lbm_multi_kernel_f64<K, true, true, true>
+constexpr Multi64Kernel kMulti64EdgeKernels[kMulti64Rows] = {LBM_MULTI64_EDGE_ROWS(2), LBM_MULTI64_EDGE_ROWS(3), LBM_MULTI64_EDGE_ROWS(4)};
+#undef LBM_MULTI64_EDGE_ROWS
+// the instantiation a context launches for a launch of K steps (full) or fewer
+Multi64Kernel multi64_kernel(const lbm_internal::PlanMultiAny64& m, bool full)
+{
+  return (m.edge ? kMulti64EdgeKernels : kMulti64Kernels)[multi64_row(m.K, m.nt_stores != 0, full)];
+}
 
 // The run loop of both frame kernels (lbm_tile_kernel_f64, lbm_multi_kernel_f64): next_steps(left) steps per launch of kernel_of(steps)
 // over n_tiles blocks; block 0 of a launch folds the vectors of the launch before it.  Moves on *parity and c->cur; leaves the number
@@ -134,7 +144,7 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   if (p->ny < 3) { lbm_internal::set_error("lbm64_create: ny must be >= 3 (accelerate_flow works on row ny-2, d2q9-bgk.c:449)"); return 1; }
   if (free_cells <= 0) { lbm_internal::set_error("lbm64_create: free_cells must be positive"); return 1; }
   if ((flags & ~lbm_internal::kFlags64) != 0u) {
-    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only, each with or without LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS (whole grids, exact arithmetic)");
+    lbm_internal::set_error("lbm64_create: the double-precision mode takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only, each with or without LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS and LBM64_FLAG_MULTI_ANY_SIZE (whole grids, exact arithmetic)");
     return 1;
   }
   if (static_cast<long long>(p->nx) * p->ny > (1LL << 31) - 4096) { lbm_internal::set_error("lbm64_create: grid too large for 32-bit cell indices"); return 1; }
@@ -149,8 +159,8 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   c->accel_w2 = p->density * p->accel * 0.0277777777777777777777778;        // d2q9-bgk.c:446
   lbm_internal::plan64_whole(c->knobs, p, flags, &c->plan);
   const lbm_internal::Plan64& plan = c->plan;
-  lbm_internal::plan64_multi(c->knobs, p, plan, &c->multi);
-  const lbm_internal::PlanMulti64& multi = c->multi;
+  lbm_internal::plan64_multi_any(c->knobs, p, plan, &c->multi);
+  const lbm_internal::PlanMultiAny64& multi = c->multi;
   Slab64& s = c->slab;
   s.device = device;
   s.ncells = static_cast<size_t>(p->nx) * p->ny;
@@ -167,7 +177,7 @@ int lbm64_create(lbm64_ctx** out, const lbm64_params* p, int free_cells, const i
   }
   if (multi.multi_kernel && multi.lds_bytes > 65536) {
     for (int full = 0; full < 2; ++full)
-      HIP_TRY_OR(hipFuncSetAttribute(reinterpret_cast<const void*>(kMulti64Kernels[multi64_row(multi.K, multi.nt_stores != 0, full != 0)]),
+      HIP_TRY_OR(hipFuncSetAttribute(reinterpret_cast<const void*>(multi64_kernel(multi, full != 0)),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, multi.lds_bytes), return fail());
   }
   HIP_TRY_OR(hipStreamSynchronize(s.stream), return fail());
@@ -189,7 +199,7 @@ int lbm64_run(lbm64_ctx* c, int n_steps, double* av_vels)
   hipLaunchKernelGGL(lbm64_accelerate_kernel, dim3((nx + 255) / 256), dim3(256), 0, s, slab.grid[c->cur], slab.ps, slab.mask, nx, ny - 2, c->accel_w1, c->accel_w2);
   HIP_TRY(hipGetLastError());
   const lbm_internal::Plan64& plan = c->plan;
-  const lbm_internal::PlanMulti64& multi = c->multi;
+  const lbm_internal::PlanMultiAny64& multi = c->multi;
   int parity = 0, launches = 0;
   int last_n = 0, last_vecs = 0;        // the last launch's partials: vectors of last_n sums, one per step
   if (plan.tile_kernel) {
@@ -200,10 +210,10 @@ int lbm64_run(lbm64_ctx* c, int n_steps, double* av_vels)
                                &parity, &launches, &last_vecs)) return 1;
     last_n = plan.n_tiles;
   } else if (multi.multi_kernel) {
-    // up to K steps per launch (lbm_plan.cpp plan64_multi_next_steps)
+    // up to K steps per launch (lbm_plan.cpp plan64_multi_any_next_steps)
     if (run_frames<Multi64Args>(c, n_steps, multi.tiles_x, multi.n_tiles, multi.block, multi.lds_bytes,
-                                [&](int left) { return lbm_internal::plan64_multi_next_steps(multi, left); },
-                                [&](int k) { return kMulti64Kernels[multi64_row(multi.K, multi.nt_stores != 0, k == multi.K)]; },
+                                [&](int left) { return lbm_internal::plan64_multi_any_next_steps(multi, left); },
+                                [&](int k) { return multi64_kernel(multi, k == multi.K); },
                                 &parity, &launches, &last_vecs)) return 1;
     last_n = multi.n_tiles;
   } else {
@@ -296,9 +306,9 @@ int lbm64_describe(const lbm64_ctx* c, char* kernel_name, size_t len, long long*
 {
   if (!c) { lbm_internal::set_error("lbm64_describe: null context"); return 1; }
   const lbm_internal::Plan64& plan = c->plan;
-  const lbm_internal::PlanMulti64& multi = c->multi;
+  const lbm_internal::PlanMultiAny64& multi = c->multi;
   if (multi.multi_kernel) {
-    if (kernel_name && len > 0) lbm_internal::plan64_multi_kernel_name(multi, kernel_name, len);
+    if (kernel_name && len > 0) lbm_internal::plan64_multi_any_kernel_name(multi, kernel_name, len);
     if (blocks) *blocks = multi.n_tiles;
     if (cells_per_block) *cells_per_block = static_cast<long long>(multi.TX) * multi.TY;
     if (state_bytes) *state_bytes = static_cast<long long>(2 * 9 * c->slab.ncells * sizeof(double));

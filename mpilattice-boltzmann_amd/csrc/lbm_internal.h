@@ -110,8 +110,29 @@ void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan,
 void plan64_multi_kernel_name(const PlanMulti64& plan, char* kernel_name, size_t len);
 // Steps of the next launch with `left` steps remaining: K, or what is left as the one shorter launch that ends the run.
 int plan64_multi_next_steps(const PlanMulti64& plan, int left);
-// The flags lbm64_create takes: a store form, LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS.
-constexpr unsigned kFlags64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS;
+// The flags lbm64_create takes: a store form, LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS, LBM64_FLAG_MULTI_ANY_SIZE.
+constexpr unsigned kFlags64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | LBM64_FLAG_TILE_STEPS | LBM64_FLAG_MULTI_STEPS | LBM64_FLAG_MULTI_ANY_SIZE;
+
+// The multi-step launches of a context, whichever flag asks for them: what PlanMulti64 says where the tiles cover the grid exactly
+// (LBM64_FLAG_MULTI_STEPS, or LBM64_FLAG_MULTI_ANY_SIZE, which means it), and under LBM64_FLAG_MULTI_ANY_SIZE the edge-tile form of
+// lbm_multi_kernel_f64 (kernels/multi64.h EDGE) on a grid they do not cover: nx even and >= TX, ny >= TY, at least LBM_TUNE_MULTI64_MIN
+// cells, not claimed by Plan64.tile_kernel.  lbm_f64.hip allocates and launches by this plan.  Plain data in this order
+// (tests/test_plan64_any.py mirrors it); beside Plan64 and PlanMulti64, whose layouts and values do not change.
+struct PlanMultiAny64 {
+  int multi_kernel, edge;            // the context advances up to K steps per launch with lbm_multi_kernel_f64; in its edge-tile form
+  int K, TX, TY;                     // as PlanMulti64
+  int tiles_x, tiles_y, n_tiles;     // ceil(nx / TX), ceil(ny / TY), their product (= work blocks of a launch); 0 where no multi-step kernel can tile the grid
+  int last_x0, last_y0;              // where the last tile column and row start: nx - TX, ny - TY (the others at TX * tx, TY * ty)
+  int block, lds_bytes;              // as PlanMulti64
+  int nt_stores;                     // Plan64.nt_stores
+  int partials_cap;                  // K * n_tiles + 1
+};
+static_assert(sizeof(PlanMultiAny64) == 14 * sizeof(int), "no padding: the order above is the layout");
+// Fills *out for the context whose Plan64 is `plan` (the caller has checked the arguments as for plan64_whole).
+void plan64_multi_any(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMultiAny64* out);
+void plan64_multi_any_kernel_name(const PlanMultiAny64& plan, char* kernel_name, size_t len);
+// Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
+int plan64_multi_any_next_steps(const PlanMultiAny64& plan, int left);
 
 // One rank of a row-partitioned double-precision run (include/lbm_d2q9_f64_rows.h; lbm_rows64.hip allocates and launches by it): the
 // rows lbm_decompose gives the rank, the one-step launch over them by plan64_whole's rules, and the sizes of its two grids of
@@ -244,6 +265,12 @@ extern "C" int lbm_plan64_multi_sizeof(void);
 extern "C" int lbm_plan64_multi(const lbm64_params* p, unsigned flags, lbm_internal::PlanMulti64* out);
 extern "C" int lbm_plan64_multi_kernel_name(const lbm_internal::PlanMulti64* plan, char* kernel_name, size_t len);
 extern "C" int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* plan, int n_steps, int* steps, int* full, int cap);
+// And for the multi-step launches under either flag, LBM64_FLAG_MULTI_ANY_SIZE's edge-tile form among them: the PlanMultiAny64 a context
+// of these arguments would get, its kernel's name ("" where multi_kernel is 0), and the launches of a run, all as above.
+extern "C" int lbm_plan64_multi_any_sizeof(void);
+extern "C" int lbm_plan64_multi_any(const lbm64_params* p, unsigned flags, lbm_internal::PlanMultiAny64* out);
+extern "C" int lbm_plan64_multi_any_kernel_name(const lbm_internal::PlanMultiAny64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_multi_any_run_launches(const lbm_internal::PlanMultiAny64* plan, int n_steps, int* steps, int* full, int cap);
 // And for a row-partitioned run: the PlanRows64 rank `rank` of `nranks` would get (0, or 1 where lbm_rows64_create refuses the
 // arguments, the message in lbm_last_error()), and its kernel's name.
 extern "C" int lbm_plan64_rows_sizeof(void);

@@ -519,11 +519,11 @@ int plan64_next_steps(const Plan64& c, int left)
 // 67.5 / 46.4 / 41.3   1024x1024 23.46 | 18.40 / 13.70 / 11.99 (the tiled kernel there: 20.67).  K is the fastest at 8192 x 8192; the
 // minimum is the smallest measured size that beats the one-step kernel by more than both max - min spreads together (11.46 us against
 // 0.05 us), which is the smallest size measured.
+constexpr int kMulti64DefaultK = 4, kMulti64DefaultMin = 1 << 20;         // cells of a whole grid (a row partition has a default of its own: plan64_rows_multi)
 void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMulti64* out)
 {
   PlanMulti64 m{};
-  constexpr int kDefaultK = 4, kDefaultMin = 1 << 20;                     // cells of a whole grid (a row partition has a default of its own: plan64_rows_multi)
-  m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kDefaultK;     // a malformed or unbuilt value: the default
+  m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kMulti64DefaultK;     // a malformed or unbuilt value: the default
   m.TX = kMulti64TX; m.TY = kMulti64TY;
   m.block = kMulti64Lanes;
   m.lds_bytes = multi64_lds_bytes(m.K);
@@ -531,8 +531,8 @@ void plan64_multi(const Knobs& knobs, const lbm64_params* p, const Plan64& plan,
   const bool tiles = p->nx % m.TX == 0 && p->ny % m.TY == 0;
   m.tiles_x = tiles ? p->nx / m.TX : 0;
   m.n_tiles = tiles ? m.tiles_x * (p->ny / m.TY) : 0;
-  m.multi_kernel = (plan.flags & LBM64_FLAG_MULTI_STEPS) != 0u && !plan.tile_kernel && tiles &&
-                   static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knob_or(knobs.multi64_min, kDefaultMin));
+  m.multi_kernel = (plan.flags & (LBM64_FLAG_MULTI_STEPS | LBM64_FLAG_MULTI_ANY_SIZE)) != 0u && !plan.tile_kernel && tiles &&   // the latter means the former
+                   static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knob_or(knobs.multi64_min, kMulti64DefaultMin));
   m.partials_cap = m.K * m.n_tiles + 1;
   *out = m;
 }
@@ -547,6 +547,50 @@ void plan64_multi_kernel_name(const PlanMulti64& m, char* kernel_name, size_t le
 int plan64_multi_next_steps(const PlanMulti64& m, int left)
 {
   return std::min(m.K, left);
+}
+
+// The multi-step launches of a context: plan64_multi's answer where the tiles cover the grid, and with LBM64_FLAG_MULTI_ANY_SIZE the
+// edge-tile form on a grid they do not cover — nx even (aligned x-pairs) and >= TX, ny >= TY (a shifted tile lies inside the grid, and
+// the wrap of sub-step 1 needs one correction per axis), at least LBM_TUNE_MULTI64_MIN cells (plan64_multi's knob and default), not
+// claimed by the tiled kernel.  ceil(nx / TX) x ceil(ny / TY) tiles; the last column and row start at nx - TX and ny - TY.
+// Measured (profiles/r20/f64_multi_any.txt), us per step for the one-step kernel | the edge form at K = 4:  8190x8190 1858.5 | 699.5
+// 4098x4100 458.6 | 182.6   2050x2046 106.8 | 46.6   1022x1026 24.93 | 12.92.  The edge form beats the one-step kernel by more than both
+// max - min spreads together at every size (at the smallest: 12.01 us against 0.42 us), so it has no minimum of its own.  8192x8192
+// under this flag: 642.4, under LBM64_FLAG_MULTI_STEPS 641.4 (the same kernel); a tile-step of 8190x8190 costs 9 % more than one of it.
+void plan64_multi_any(const Knobs& knobs, const lbm64_params* p, const Plan64& plan, PlanMultiAny64* out)
+{
+  PlanMulti64 m{};
+  plan64_multi(knobs, p, plan, &m);
+  PlanMultiAny64 a{};
+  a.K = m.K; a.TX = m.TX; a.TY = m.TY;
+  a.block = m.block; a.lds_bytes = m.lds_bytes;
+  a.nt_stores = m.nt_stores;
+  const bool exact = m.n_tiles > 0;
+  const bool shape = exact || (p->nx % kPairCells == 0 && p->nx >= a.TX && p->ny >= a.TY);
+  a.tiles_x = shape ? (p->nx + a.TX - 1) / a.TX : 0;
+  a.tiles_y = shape ? (p->ny + a.TY - 1) / a.TY : 0;
+  a.n_tiles = a.tiles_x * a.tiles_y;
+  a.last_x0 = shape ? p->nx - a.TX : 0;
+  a.last_y0 = shape ? p->ny - a.TY : 0;
+  a.edge = (plan.flags & LBM64_FLAG_MULTI_ANY_SIZE) != 0u && !plan.tile_kernel && shape && !exact &&
+           static_cast<long long>(p->nx) * p->ny >= static_cast<long long>(knob_or(knobs.multi64_min, kMulti64DefaultMin));
+  a.multi_kernel = m.multi_kernel || a.edge;
+  a.partials_cap = a.K * a.n_tiles + 1;
+  *out = a;
+}
+
+void plan64_multi_any_kernel_name(const PlanMultiAny64& a, char* kernel_name, size_t len)
+{
+  if (!a.multi_kernel) { kernel_name[0] = '\0'; return; }
+  const char* form = a.edge ? (a.nt_stores ? "lbm_multi_kernel_f64<%d,nt,edge>" : "lbm_multi_kernel_f64<%d,edge>")
+                            : (a.nt_stores ? "lbm_multi_kernel_f64<%d,nt>" : "lbm_multi_kernel_f64<%d>");
+  std::snprintf(kernel_name, len, form, a.K);
+}
+
+// plan64_multi_next_steps' rule: floor(n / K) launches of K steps and at most one shorter launch, the last.
+int plan64_multi_any_next_steps(const PlanMultiAny64& a, int left)
+{
+  return std::min(a.K, left);
 }
 
 // One rank of a row-partitioned double-precision run (lbm_rows64_create).  Rows by the reference's rule; the launch over the rank's
@@ -1025,6 +1069,32 @@ int lbm_plan64_multi_run_launches(const lbm_internal::PlanMulti64* plan, int n_s
     left -= k;
   }
   return n;
+}
+int lbm_plan64_multi_any_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanMultiAny64)); }
+int lbm_plan64_multi_any(const lbm64_params* p, unsigned flags, lbm_internal::PlanMultiAny64* out)
+{
+  lbm_internal::Plan64 plan;
+  if (!out) { set_error("lbm_plan64_multi_any: null argument"); return 1; }
+  if (lbm_plan64_whole(p, flags, &plan)) return 1;
+  lbm_internal::plan64_multi_any(knobs_from_env(), p, plan, out);
+  return 0;
+}
+int lbm_plan64_multi_any_kernel_name(const lbm_internal::PlanMultiAny64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_multi_any_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_multi_any_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_multi_any_run_launches(const lbm_internal::PlanMultiAny64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || !multi64_k_ok(plan->K) || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_multi_any_run_launches: bad argument"); return -1; }
+  int count = 0;
+  for (int left = n_steps; left > 0; ++count) {
+    const int k = lbm_internal::plan64_multi_any_next_steps(*plan, left);
+    if (count < cap) { steps[count] = k; full[count] = k == plan->K; }
+    left -= k;
+  }
+  return count;
 }
 int lbm_plan64_kernel_name(const lbm_internal::Plan64* plan, char* kernel_name, size_t len)
 {

@@ -10,7 +10,8 @@
 
 The reference's arithmetic with every float object a double (the contract is in the header): whole periodic grids on one GPU, one
 step per launch of lbm_step_kernel_f64 or, with `flags=f64.FLAG_TILE_STEPS` on a small grid, several per launch of lbm_tile_kernel_f64,
-with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_multi_kernel_f64 (the same populations, bit for bit).  There is no CPU fallback: a missing library or symbol raises.
+with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_multi_kernel_f64 (the same populations, bit for bit);
+`flags=f64.FLAG_MULTI_ANY_SIZE` means the same and also takes the large grids that 32 x 16 tiles do not cover exactly.  There is no CPU fallback: a missing library or symbol raises.
 
 `f64.Rows64(p, obst, nranks, devices=None)` is the same grid as `nranks` row blocks over one or several GPUs of this process
 (include/lbm_d2q9_f64_rows.h): Grid64's methods, Grid64's populations bit for bit for every rank count.  With
@@ -36,6 +37,7 @@ ABI_VERSION = 1
 FLAG_NT_STORES, FLAG_NO_NT_STORES = _capi.FLAG_NT_STORES, _capi.FLAG_NO_NT_STORES
 FLAG_TILE_STEPS = 512        # LBM64_FLAG_TILE_STEPS: small grids advance several steps per launch (lbm_tile_kernel_f64); the same populations
 FLAG_MULTI_STEPS = 1024      # LBM64_FLAG_MULTI_STEPS: large grids that 32 x 16 tiles cover do (lbm_multi_kernel_f64); the same populations
+FLAG_MULTI_ANY_SIZE = 4096   # LBM64_FLAG_MULTI_ANY_SIZE: FLAG_MULTI_STEPS, and large grids of any even width >= 32 and ny >= 16 by the kernel's edge-tile form ("lbm_multi_kernel_f64<K,edge>"); the same populations
 FLAG_ROWS_MULTI_STEPS = 2048  # LBM_ROWS64_FLAG_MULTI_STEPS: Rows64 only; ranks that 32 x 16 tiles cover advance K steps per launch and exchange (lbm_rows_multi_kernel_f64); the same populations
 
 
@@ -400,5 +402,5 @@ def differing_rows(a, b) -> list[int]:
     return [int(y) for y in np.nonzero(a.digest()[0] != b.digest()[0])[0]]
 
 
-__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_ROWS_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
+__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_MULTI_ANY_SIZE", "FLAG_ROWS_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
            "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]

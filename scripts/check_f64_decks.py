@@ -8,7 +8,7 @@ largest relative distance of av_vels from the shipped file beside it.
 LBM_TUNE_TILE64_MAX and LBM_TUNE_TILE64_GEOM of the caller's environment reach the CLI; every other LBM_* variable is dropped.  Each
 deck's report ends with the kernel that ran and its launches (LBM_DESCRIBE=1).
 
---flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS, 1024 = LBM64_FLAG_MULTI_STEPS, 1536 = both: several steps per launch where the grid is eligible).
+--flags: LBM_FLAGS of the CLI, the lbm64_create flags (512 = LBM64_FLAG_TILE_STEPS, 1024 = LBM64_FLAG_MULTI_STEPS, 1536 = both: several steps per launch where the grid is eligible; 4096 = LBM64_FLAG_MULTI_ANY_SIZE: 1024 on the shipped decks, which 32 x 16 tiles cover).
 
 --ranks N: LBM64_RANKS of the CLI: the deck as N row blocks (include/lbm_d2q9_f64_rows.h), rank r on device r % (device count); then
 --flags takes 0, 1 or 2 only.
@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--decks", default=",".join(DECKS))
     ap.add_argument("--out")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per deck")
-    ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS, 1024: LBM64_FLAG_MULTI_STEPS, 1536: both)")
+    ap.add_argument("--flags", type=int, default=0, help="LBM_FLAGS: lbm64_create flags (512: LBM64_FLAG_TILE_STEPS, 1024: LBM64_FLAG_MULTI_STEPS, 1536: both, 4096: LBM64_FLAG_MULTI_ANY_SIZE)")
     ap.add_argument("--ranks", type=int, default=0, help="LBM64_RANKS: the deck as this many row blocks (0: one context)")
     a = ap.parse_args()
     lbm.build()

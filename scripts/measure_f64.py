@@ -37,6 +37,15 @@ compared for equal bits (host-bound, about 13 GB of host memory); its line goes 
     timeout -k 10 120 python scripts/measure_f64.py --multi --baseline-lib $B --work 1024x1024 --out $F &&
     timeout -k 10 300 python scripts/measure_f64.py --multi-bits 3 --out $F
 
+--multi-any: LBM64_FLAG_MULTI_ANY_SIZE (the edge-tile form of lbm_multi_kernel_f64 on grids that 32 x 16 tiles do not cover) beside
+the best of the same BASELINE build for the grid: its one-step kernel, or on a grid the tiles cover its LBM64_FLAG_MULTI_STEPS run,
+which flag 4096 must equal in time.  One size per process:
+
+    F=profiles/r20/f64_multi_any.txt; rm -f $F; B=mpilattice-boltzmann_amd/lib/variants/liblbm_d2q9_parent.so
+    for w in 8190x8190 8192x8192 4098x4100 2050x2046 1022x1026; do
+      timeout -k 10 240 python scripts/measure_f64.py --multi-any --baseline-lib $B --work $w --out $F || break
+    done
+
 --ranks N[,N] [--devices LIST] [--steps S]: row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count beside
 the one-context one-step and LBM64_FLAG_MULTI_STEPS runs of the same grid (--work NXxNY, default 8192x8192), alternating: device and
 wall time per step.  Each rank count runs twice, without and with LBM_ROWS64_FLAG_MULTI_STEPS (K steps per launch and exchange; the
@@ -246,6 +255,55 @@ def measure_multi(name, baseline_lib, reps, lines, steps_override=None):
     print("\n".join(lines[n0:]), flush=True)
 
 
+MULTI_ANY_STEPS = ((1 << 25, 60), (1 << 23, 120), (1 << 21, 240), (0, 1200))      # steps per run by cells: multiples of every K
+
+
+def measure_multi_any(name, baseline_lib, reps, lines, steps_override=None):
+    """LBM64_FLAG_MULTI_ANY_SIZE at the library's K beside the parent commit's best for the same grid, in the baseline build: the
+    one-step kernel on a grid that 32 x 16 tiles do not cover, LBM64_FLAG_MULTI_STEPS on one they do (the same kernel: the two must
+    agree within their spreads).  Device time per step, the contexts alternating run by run."""
+    p, obst = deck(name)
+    steps = steps_override or next(s for cells, s in MULTI_ANY_STEPS if p.nx * p.ny >= cells)
+    n0 = len(lines)
+    os.environ["LBM_TUNE_MULTI64_MIN"] = "0"              # read when a context is made: every size is measured
+    exact = p.nx % 32 == 0 and p.ny % 16 == 0
+    base_key = "parent build, flag 1024" if exact else "parent build, one step"
+    runs = {base_key: BaselineGrid64(baseline_lib, p, obst, flags=f64.FLAG_MULTI_STEPS if exact else 0)}
+    runs["flag 4096"] = f64.Grid64(p, obst, flags=f64.FLAG_MULTI_ANY_SIZE)
+    if exact:
+        runs["flag 1024"] = f64.Grid64(p, obst, flags=f64.FLAG_MULTI_STEPS)
+    kernels = {k: q.describe()["kernel"] for k, q in runs.items()}
+    want = "lbm_multi_kernel_f64<" if exact else "lbm_step_kernel_f64<"
+    if not kernels[base_key].startswith(want) or not kernels["flag 4096"].startswith("lbm_multi_kernel_f64<") or kernels["flag 4096"].endswith(",edge>") == exact:
+        raise SystemExit(f"{name}: the contexts run {kernels}")
+    first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
+    for k, av in first.items():                            # the same run: av_vels agree to the order of their additions
+        if not np.allclose(av, first[base_key], rtol=1e-12, atol=0.0):
+            raise SystemExit(f"{name}, {k}: av_vels differ from the baseline's by {np.max(np.abs(av - first[base_key]) / first[base_key]):.3e}")
+    us = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, q in runs.items():                          # alternate: all see the same drift of the card
+            q.run(steps)
+            us[k].append(1e3 * q.last_run_kernel_ms()[0] / steps)
+    blocks = runs["flag 4096"].describe()["blocks"]
+    for q in runs.values():
+        q.close()
+    med = {k: statistics.median(v) for k, v in us.items()}
+    spread = {k: max(v) - min(v) for k, v in us.items()}
+    lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; {blocks} tiles; device time of a run's step launches, us per step")
+    for k in runs:
+        lines.append(f"  {k:26s} {kernels[k]:32s} us/step median {med[k]:9.3f}  min {min(us[k]):9.3f}  max {max(us[k]):9.3f}   {144 * p.nx * p.ny / med[k] / 1e6:6.3f} TB/s at 144 B/cell-step"
+                     f"   {1e3 * med[k] / blocks:7.3f} ns per tile-step")
+    gain, spreads = med[base_key] - med["flag 4096"], spread[base_key] + spread["flag 4096"]
+    if exact:
+        lines.append(f"  flag 4096 against {base_key}: {med[base_key] / med['flag 4096']:.4f} x; median difference {gain:.3f} us against the two max - min spreads together "
+                     f"{spreads:.3f} us -> {'the same time' if abs(gain) <= spreads else 'DIFFERENT'}")
+    else:
+        lines.append(f"  flag 4096 against {base_key}: {med[base_key] / med['flag 4096']:.3f} x; median gain {gain:.3f} us against the two max - min spreads together "
+                     f"{spreads:.3f} us -> {'a win' if gain > spreads else 'no win'}")
+    print("\n".join(lines[n0:]), flush=True)
+
+
 def multi_bits(ks, lines):
     """8192 x 7296 (the nine planes pass 4 GiB): 2K + 1 steps from tests/test_f64.py's separable state with the flag and without;
     populations compared by row blocks for equal bits."""
@@ -345,6 +403,7 @@ def main():
     ap.add_argument("--tile", action="store_true", help="LBM64_FLAG_TILE_STEPS in every geometry against --baseline-lib's one-step path; --work: a deck")
     ap.add_argument("--multi", action="store_true", help="LBM64_FLAG_MULTI_STEPS with every built K against --baseline-lib's one-step path; --work: a size")
     ap.add_argument("--multi-bits", metavar="K[,K]", help="the 8192 x 7296 bit comparison of lbm_multi_kernel_f64<K> with the one-step kernel (--out appends)")
+    ap.add_argument("--multi-any", action="store_true", help="LBM64_FLAG_MULTI_ANY_SIZE against --baseline-lib's best for the grid; --work: NXxNY (--out appends)")
     ap.add_argument("--baseline-lib", help="liblbm_d2q9.so of the parent commit")
     ap.add_argument("--ranks", metavar="N[,N]", help="row-partitioned runs (f64.Rows64) with these rank counts beside the one-context runs; --work: NXxNY (default 8192x8192)")
     ap.add_argument("--devices", metavar="LIST", help="with --ranks: HIP ordinals, rank r on LIST[r %% len(LIST)] (default: the library's, r %% device count)")
@@ -367,6 +426,19 @@ def main():
         lines = []
         multi_bits([int(v) for v in a.multi_bits.split(",")], lines)
         if a.out:
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
+    if a.multi_any:
+        if not a.baseline_lib or not os.path.exists(a.baseline_lib) or not a.work:
+            ap.error("--multi-any needs --work NXxNY and --baseline-lib, an existing build of the library")
+        lines = [] if a.out and os.path.exists(a.out) else [
+            "# scripts/measure_f64.py --multi-any: LBM64_FLAG_MULTI_ANY_SIZE (the edge-tile form of lbm_multi_kernel_f64 where 32 x 16 tiles do not cover the grid) beside "
+            "the parent commit's best for the same grid, in the parent commit's build",
+            "# device time per step (lbm64_last_run_kernel_ms: events around the step launches of a run, over its steps); LBM_TUNE_MULTI64_MIN=0, the library's K"]
+        measure_multi_any(a.work, a.baseline_lib, 3 if a.quick else 5, lines, steps_override=12 if a.quick else None)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "a") as fh:
                 fh.write("\n".join(lines) + "\n")
         return 0
