@@ -476,5 +476,71 @@ __device__ __forceinline__ double finish_pair(const f2 (&t)[9], uint32_t mbits, 
   return (TERMS & ~kTermsFused) == kTermsCompensated ? hi + static_cast<double>(lo) : hi;
 }
 
+// fmaxf(msq, 2^-126) for msq = mx^2 + my^2 (or its fused form): never negative and never -0, and non-negative floats order as
+// their bit patterns do, so the clamp is v_max_u32 on the bits.  fmaxf costs a second, canonicalising v_max_f32 here: hipcc does
+// not see that an element of a packed sum is already canonical.  (A NaN msq stays NaN where fmaxf gave 2^-126; the term, whose
+// first product is msq * y, is NaN in both cases.)
+__device__ __forceinline__ float clamp_msq(float msq)
+{
+  const uint32_t b = __builtin_bit_cast(uint32_t, msq);
+  return __builtin_bit_cast(float, b > 0x00800000u ? b : 0x00800000u);
+}
+
+// The form lbm_multi_kernel's tall geometry relaxes with (owned_substeps: no accelerate_flow here, accelerate_pair follows):
+// finish_pair's populations and, for a pair that has a term, finish_pair's double: (double)p.x + (double)p.y + (double)(lo.x + lo.y)
+// with a dropped cell contributing +0.  TERM: kPairTermNone, a ring pair, which has no term; kPairTermOwned, the owned pair;
+// kPairTermGuarded, the same behind a wave-uniform test for any lane that counts a cell (sub-step 1's rolled body, which serves
+// owned and ring pairs in turn).  What differs from finish_pair is the code around the compensated term, which every owned pair
+// runs in every sub-step:
+//   - a wave in which no lane drops a cell (`clean`, wave-uniform, the caller's: no obstacle and nothing uncounted in the wave,
+//     about half the waves of a 0.5 % deck) takes the plain sums and no bounce-back test;
+//   - elsewhere the selects act on the floats BEFORE the widening (hipcc moves them behind it, where each is two v_cndmask on
+//     the halves of a double; the empty asm keeps them in place), and no divergent branch surrounds lanes with skip = 3:
+//     their selects yield +0, as that branch did;
+//   - the clamp of msq is an unsigned integer maximum (clamp_msq), with no canonicalising v_max in front of it;
+//   - the low parts are summed as they are, not added onto a zero lo_sum first.  0.0f + x differs from x for x = -0 only, and
+//     lo.x + lo.y is never -0: e = fma(s, rinv, -p), where it is zero, is +0 (an exact zero sum of two products rounds to +0,
+//     and s * rinv and -p are zeros of opposite sign where both are zero), so neither lo = fma(c, rinv, e) is -0.
+// The other term forms go through finish_pair unchanged.
+constexpr int kPairTermNone = 0, kPairTermOwned = 1, kPairTermGuarded = 2;
+template <int TERMS_ARITH, int TERM>
+__device__ __forceinline__ double finish_pair_owned(const f2 (&t)[9], uint32_t mbits, float omega, uint32_t skip, bool clean, f2 (&out)[9])
+{
+  if constexpr ((TERMS_ARITH & ~kTermsFused) != kTermsCompensated) {
+    return finish_pair<TERMS_ARITH>(t, mbits, omega, false, false, 0.0f, 0.0f, TERM != kPairTermNone ? skip : 3u, out);
+  } else {
+    f2 o[9], msq, rinv;
+    relax_core<f2, (TERMS_ARITH & kTermsFused) != 0>(t, omega, o, msq, rinv);
+    static constexpr int opp[9] = {0, 3, 4, 1, 2, 7, 8, 5, 6};
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[k] = o[k];
+    if (!clean && __builtin_amdgcn_ballot_w64(mbits != 0u) != 0ull) {   // bounce-back select (d2q9-bgk.c:687-695), as finish_pair_lo
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const bool blocked = (mbits >> j) & 1u;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k][j] = blocked ? t[opp[k]][j] : o[k][j];
+      }
+    }
+    if constexpr (TERM == kPairTermNone) {
+      return 0.0;
+    } else {
+      if constexpr (TERM == kPairTermGuarded) {
+        if (__builtin_amdgcn_ballot_w64(skip != 3u) == 0ull) return 0.0;
+      }
+      const f2 y = f2{__builtin_amdgcn_rsqf(clamp_msq(msq.x)), __builtin_amdgcn_rsqf(clamp_msq(msq.y))};
+      const f2 s = msq * y;                                  // ~sqrt(msq)
+      const f2 r = fma2(-s, s, msq);                         // msq - s*s
+      const f2 c = (r * y) * 0.5f;                           // sqrt(msq) ~ s + c
+      const f2 p = s * rinv;
+      const f2 e = fma2(s, rinv, -p);                        // s * rinv = p + e exactly
+      const f2 lo = fma2(c, rinv, e);
+      if (clean) return static_cast<double>(p.x) + static_cast<double>(p.y) + static_cast<double>(lo.x + lo.y);
+      float px = (skip & 1u) ? 0.0f : p.x, py = (skip & 2u) ? 0.0f : p.y, lx = (skip & 1u) ? 0.0f : lo.x, ly = (skip & 2u) ? 0.0f : lo.y;
+      asm("" : "+v"(px), "+v"(py), "+v"(lx), "+v"(ly));
+      return static_cast<double>(px) + static_cast<double>(py) + static_cast<double>(lx + ly);
+    }
+  }
+}
 
 }  // namespace

@@ -509,13 +509,63 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
       const int i = fy < EY ? fy * wp + rp : fy >= EY + TY ? band + (fy - EY - TY) * wp + rp : 2 * band + (fy - EY) * (2 * ep) + (rp < ep ? rp : rp - TP);
       return ring0 + i;
     };
-    // relaxation, bounce-back and accelerate_flow of one pair; returns its sum|u| term (0 where skip = 3)
-    auto relax = [&](const f2 (&p)[9], const uint32_t mbits, const bool accel, const uint32_t skip, f2 (&out)[9]) __attribute__((always_inline)) {
-      const double term = finish_pair<TERMS>(p, mbits, a.omega, false, false, a.accel_w1, a.accel_w2, skip, out);
+    // relaxation, bounce-back and accelerate_flow of one pair; returns its sum|u| term (0 where skip = 3).  term_c: kPairTermNone for
+    // a ring pair, kPairTermOwned for the owned pair, kPairTermGuarded where one rolled body serves both (finish_pair_owned);
+    // clean (wave-uniform): no lane of the wave drops a cell from its term, hence none holds an obstacle either
+    auto relax = [&](auto term_c, const f2 (&p)[9], const uint32_t mbits, const bool accel, const uint32_t skip, const bool clean, f2 (&out)[9]) __attribute__((always_inline)) {
+      const double term = finish_pair_owned<TERMS, decltype(term_c)::value>(p, mbits, a.omega, skip, clean, out);
       if (tile_accel) accelerate_pair(out, mbits, accel, a.accel_w1, a.accel_w2);
       return term;
     };
+    constexpr std::integral_constant<int, kPairTermNone> ring_term{};
+    constexpr std::integral_constant<int, kPairTermOwned> owned_term{};
+    constexpr std::integral_constant<int, kPairTermGuarded> either_term{};
     const int py = tid / TP, ofx = EX + 2 * (tid - py * TP), ofy = EY + py;
+    // The owned pair's frame accesses.  Its position is fixed for the launch and every plane, row and sub-step shift is a constant,
+    // so each dword can be one ds_read_b32 / ds_write_b32 with a 16-bit immediate offset on a lane base that never changes.  Written
+    // as plain loads and stores (read_pair, store_pair) hipcc pairs the two dwords of a split plane into ds_read2_b32 / ds_write2_b32,
+    // whose 8-bit offsets do not span a plane, and builds a new base per plane and pass (12 v_add_u32 per in-frame sub-step).  A
+    // relaxed wavefront-scope atomic access is the same LDS instruction and is left unpaired.  Three bases, byte offsets into the
+    // frame, each set below everything a read or write of any sub-step reaches so that all immediates are >= 0: the interleaved
+    // planes (2, 4), the split planes, and the last split plane, whose offsets pass 64 KB.  Sub-steps 2 .. K only: with the bases
+    // alive through sub-step 1's pull as well the kernel needs more than its 80 VGPRs, so sub-step 1 stores through store_pair.
+    constexpr int kLowI = (K - 1) * W, kLowS = (K - 1) * W + 1;       // dwords a sub-step reaches below the pair's own position
+    constexpr int kImmDwords = 16384, kHiDwords = (kPlanes - 1) * kCells;
+    static_assert((kPlanes - 2) * kCells + kLowS + W + WH + 1 < kImmDwords && kPlanes * kCells - kHiDwords < kImmDwords, "two split bases reach every plane");
+    uint32_t own_bi = 0, own_bs = 0, own_bs_hi = 0;                    // set after sub-step 1
+    auto own_split = [&](const int o) __attribute__((always_inline)) -> float* {          // dword o (a constant) above the split base
+      return o < kImmDwords ? reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + own_bs) + o
+                            : reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + own_bs_hi) + (o - kHiDwords);
+    };
+    auto own_inter = [&](const int o) __attribute__((always_inline)) -> unsigned long long* {
+      return reinterpret_cast<unsigned long long*>(reinterpret_cast<float*>(reinterpret_cast<char*>(lds) + own_bi) + o);
+    };
+    auto ld1 = [&](const int o) __attribute__((always_inline)) { return __hip_atomic_load(own_split(o), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); };
+    auto ld2 = [&](const int o) __attribute__((always_inline)) { return __builtin_bit_cast(f2, __hip_atomic_load(own_inter(o), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT)); };
+    // read_pair(rd, ofx, ofy, p)
+    auto read_pair_own = [&](const int rd, f2 (&p)[9]) __attribute__((always_inline)) {
+      const int ci = kLowI - rd, cs = kLowS - rd;
+      p[2] = ld2((2 - kPl) * kCells + ci - W);
+      p[4] = ld2((4 - kPl) * kCells + ci + W);
+      p[1] = f2{ld1((1 - kPl) * kCells + cs - 1), ld1((1 - kPl) * kCells + cs + WH)};
+      p[5] = f2{ld1((5 - kPl) * kCells + cs - W - 1), ld1((5 - kPl) * kCells + cs - W + WH)};
+      p[8] = f2{ld1((8 - kPl) * kCells + cs + W - 1), ld1((8 - kPl) * kCells + cs + W + WH)};
+      p[3] = f2{ld1((3 - kPl) * kCells + cs), ld1((3 - kPl) * kCells + cs + WH + 1)};
+      p[6] = f2{ld1((6 - kPl) * kCells + cs - W), ld1((6 - kPl) * kCells + cs - W + WH + 1)};
+      p[7] = f2{ld1((7 - kPl) * kCells + cs + W), ld1((7 - kPl) * kCells + cs + W + WH + 1)};
+    };
+    // store_pair<W>(lds + (k - kPl) * kCells, k, ofy * W - wr, ofx, v[k]) for k = 1 .. 8
+    auto store_pair_own = [&](const int wr, const f2 (&v)[9]) __attribute__((always_inline)) {
+  #pragma unroll
+      for (int k = 1; k < 9; ++k) {
+        if (k == 2 || k == 4) {
+          __hip_atomic_store(own_inter((k - kPl) * kCells + kLowI - wr), __builtin_bit_cast(unsigned long long, v[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        } else {
+          __hip_atomic_store(own_split((k - kPl) * kCells + kLowS - wr), v[k].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+          __hip_atomic_store(own_split((k - kPl) * kCells + kLowS - wr + WH), v[k].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+      }
+    };
     f2 own0 = f2{0.0f, 0.0f};                                          // population 0 of the owned pair
     uint32_t ofl = 0;                                                  // its flag bits; 0: not computed
     if (!COUNT && inner) {                                             // block-uniform
@@ -549,7 +599,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         uint32_t mbits;
         pull_inner(ofx, ofy, p, mbits);
         const bool accel_row_here = on_accel_row(sy0 + py);
-        acc[0] = relax(p, mbits, accel_row_here, mbits, out);
+        acc[0] = relax(owned_term, p, mbits, accel_row_here, mbits, __builtin_amdgcn_ballot_w64(mbits != 0u) == 0ull, out);
   #pragma unroll
         for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, ofy * W, ofx, out[k]);
         own0 = out[0];
@@ -562,7 +612,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         uint32_t mbits;
         pull_inner(fx, fy, p, mbits);
         const bool accel_row_here = on_accel_row(sy0 + fy - EY);
-        relax(p, mbits, accel_row_here, 3u, out);
+        relax(ring_term, p, mbits, accel_row_here, 3u, false, out);
   #pragma unroll
         for (int k = kPl; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, fy * W, fx, out[k]);
         if constexpr (G::compact0) ring0[tid] = out[0];
@@ -584,7 +634,7 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
         classify(count_c, fx, fy, own, kept, counted);
         const bool accel_row_here = on_accel_row(sr);
         f2 out[9];
-        const double term = relax(p, mbits, accel_row_here, counted ? mbits : 3u, out);
+        const double term = relax(either_term, p, mbits, accel_row_here, counted ? mbits : 3u, false, out);
   #pragma unroll
         for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, fy * W, fx, out[k]);
         fl = pair_flag_bits(mbits, kept, accel_row_here, COUNT && counted);
@@ -604,17 +654,23 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
     LBM_MSTAMP(1);
     __syncthreads();
     LBM_MSTAMP(2);
+    // the three bases, from here on in their registers: left to itself hipcc derives them again from the lane index in every sub-step
+    own_bi = 4u * static_cast<uint32_t>(ofy * W + ofx - kLowI); own_bs = 4u * static_cast<uint32_t>(ofy * W + (ofx >> 1) - kLowS);
+    own_bs_hi = own_bs + 4u * kHiDwords;
+    asm volatile("" : "+v"(own_bi), "+v"(own_bs), "+v"(own_bs_hi));
+    // the owned pair's flags do not change either: is this a wave in which every lane counts both its cells ?
+    const bool own_clean = __builtin_amdgcn_ballot_w64(((ofl & (COUNT ? kPairCounted : kPairKept)) != 0u ? ofl & kPairObstacles : 3u) != 0u) == 0ull;
     // ---- sub-steps 2..K in place, the frame creeping down one row per sub-step as in k_substeps
     auto in_lds_substep = [&](auto jc) __attribute__((always_inline)) {
       constexpr int j = decltype(jc)::value;
       constexpr bool last = j == K;
       constexpr int rd = (j - 2) * W, wr = (j - 1) * W;                // storage shift of the frame read / written
       f2 p[9], outs[9];
-      read_pair(rd, ofx, ofy, p);
+      read_pair_own(rd, p);
       p[0] = own0;
       const uint32_t mbits = ofl & kPairObstacles;
       const bool counted = (ofl & (COUNT ? kPairCounted : kPairKept)) != 0u;
-      acc[j - 1] = relax(p, mbits, (!last || a.accel_last) && (ofl & kPairAccelRow), counted ? mbits : 3u, outs);
+      acc[j - 1] = relax(owned_term, p, mbits, (!last || a.accel_last) && (ofl & kPairAccelRow), counted ? mbits : 3u, own_clean, outs);
       own0 = outs[0];
       if constexpr (!last) {
         // the ring pair's populations are READ before the barrier and relaxed after it, once the owned results are stored: a lane
@@ -632,13 +688,10 @@ __global__ void __launch_bounds__((MultiGeom<K, GEOM>::LANES), (MultiGeom<K, GEO
           else q[0] = *reinterpret_cast<const f2*>(lds + rfy * W + rfx - rd);
         }
         __syncthreads();                       // every lane has read its neighbours
-        if (ofl & kPairComputed) {
-  #pragma unroll
-          for (int k = 1; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, ofy * W - wr, ofx, outs[k]);
-        }
+        if (ofl & kPairComputed) store_pair_own(wr, outs);
         if (ring) {
           f2 routs[9];
-          relax(q, rfl & kPairObstacles, (rfl & kPairAccelRow) != 0u, 3u, routs);
+          relax(ring_term, q, rfl & kPairObstacles, (rfl & kPairAccelRow) != 0u, 3u, false, routs);
           if (rfl & kPairComputed) {
   #pragma unroll
             for (int k = kPl; k < 9; ++k) store_pair<W>(lds + (k - kPl) * kCells, k, rfy * W - wr, rfx, routs[k]);

@@ -13,10 +13,16 @@
 //      then for each of them n floats (lo_sum, started from 0);
 //      then n x 2 floats each: msq, rinv of relax_core (exact arithmetic), msq, rinv of the fused arithmetic,
 //      the raw v_sqrt_f32 and the raw v_rsq_f32 of the exact msq.
+// With --owned as the first argument each OUT gets a second file OUT.owned: the term of finish_pair_owned (the form lbm_multi_kernel's tall
+//      geometry relaxes with), n doubles for each of <kTermsCompensated, kPairTermOwned>, <kTermsCompensated | kTermsFused, kPairTermOwned>,
+//      <kTermsCompensated, kPairTermGuarded>, <kTermsCompensated | kTermsFused, kPairTermGuarded>, with `clean` what owned_substeps passes:
+//      no lane of the pair's wave (64 consecutive pairs) drops a cell.  OUT itself is the same with and without the option.
 // Exit status 0 only if every file was read, computed and written and no HIP call failed.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+#include <string>
 #include <type_traits>
 #include <vector>
 #include "../../mpilattice-boltzmann_amd/csrc/kernels/common.h"
@@ -70,9 +76,26 @@ __global__ void __launch_bounds__(kBlock) terms_probe_kernel(const float* in, co
   }
 }
 
+constexpr int kOwnedForms = 4;
+
+__global__ void __launch_bounds__(kBlock) terms_probe_owned_kernel(const float* in, const unsigned char* mbits_in, const unsigned char* skip_in, size_t n, float omega, double* term)
+{
+  const size_t c = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x;
+  if (c >= n) return;
+  f2 t[9], out[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) t[k] = f2{in[(c * 9 + k) * 2], in[(c * 9 + k) * 2 + 1]};
+  const uint32_t mbits = mbits_in[c] & 3u, skip = skip_in[c] & 3u;
+  const bool clean = __builtin_amdgcn_ballot_w64(skip != 0u) == 0ull;
+  term[0 * n + c] = finish_pair_owned<kTermsCompensated, kPairTermOwned>(t, mbits, omega, skip, clean, out);
+  term[1 * n + c] = finish_pair_owned<kTermsCompensated | kTermsFused, kPairTermOwned>(t, mbits, omega, skip, clean, out);
+  term[2 * n + c] = finish_pair_owned<kTermsCompensated, kPairTermGuarded>(t, mbits, omega, skip, clean, out);
+  term[3 * n + c] = finish_pair_owned<kTermsCompensated | kTermsFused, kPairTermGuarded>(t, mbits, omega, skip, clean, out);
+}
+
 struct Header { uint64_t n; float omega, pad; };
 
-static int probe_file(const char* in_path, const char* out_path)
+static int probe_file(const char* in_path, const char* out_path, bool owned)
 {
   std::FILE* f = std::fopen(in_path, "rb");
   if (!f) { std::fprintf(stderr, "terms_probe: cannot open %s\n", in_path); return 1; }
@@ -115,6 +138,18 @@ static int probe_file(const char* in_path, const char* out_path)
   HIP_OK(hipMemcpy(term.data(), d_term, term.size() * sizeof(double), hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(lo.data(), d_lo, lo.size() * sizeof(float), hipMemcpyDeviceToHost));
   HIP_OK(hipMemcpy(planes.data(), d_planes, planes.size() * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<double> owned_term;
+  if (owned) {
+    double* d_owned = nullptr;
+    HIP_OK(hipMalloc(&d_owned, kOwnedForms * n * sizeof(double)));
+    HIP_OK(hipMemset(d_owned, 0xff, kOwnedForms * n * sizeof(double)));
+    terms_probe_owned_kernel<<<blocks, kBlock>>>(d_in, d_codes, d_codes + n, n, h.omega, d_owned);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipDeviceSynchronize());
+    owned_term.resize(kOwnedForms * n);
+    HIP_OK(hipMemcpy(owned_term.data(), d_owned, owned_term.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_OK(hipFree(d_owned));
+  }
   HIP_OK(hipFree(d_in));
   HIP_OK(hipFree(d_codes));
   HIP_OK(hipFree(d_flags));
@@ -127,18 +162,27 @@ static int probe_file(const char* in_path, const char* out_path)
                      std::fwrite(lo.data(), sizeof(float), lo.size(), g) == lo.size() &&
                      std::fwrite(planes.data(), sizeof(float), planes.size(), g) == planes.size();
   if (std::fclose(g) != 0 || !wrote) { std::fprintf(stderr, "terms_probe: %s: short write\n", out_path); return 1; }
+  if (owned) {
+    const std::string owned_path = std::string(out_path) + ".owned";
+    std::FILE* o = std::fopen(owned_path.c_str(), "wb");
+    if (!o) { std::fprintf(stderr, "terms_probe: cannot write %s\n", owned_path.c_str()); return 1; }
+    const bool wrote_owned = std::fwrite(owned_term.data(), sizeof(double), owned_term.size(), o) == owned_term.size();
+    if (std::fclose(o) != 0 || !wrote_owned) { std::fprintf(stderr, "terms_probe: %s: short write\n", owned_path.c_str()); return 1; }
+  }
   std::printf("terms_probe: %s: %zu pairs, float denormals %s\n", in_path, n, flags[0] ? "kept" : "flushed");
   return 0;
 }
 
 int main(int argc, char** argv)
 {
-  if (argc < 3 || argc % 2 != 1) {
-    std::fprintf(stderr, "usage: %s IN OUT [IN OUT ...]\n", argv[0]);
+  const bool owned = argc > 1 && std::strcmp(argv[1], "--owned") == 0;
+  const int first = owned ? 2 : 1;
+  if (argc - first < 2 || (argc - first) % 2 != 0) {
+    std::fprintf(stderr, "usage: %s [--owned] IN OUT [IN OUT ...]\n", argv[0]);
     return 1;
   }
-  for (int i = 1; i + 1 < argc; i += 2) {
-    const int rc = probe_file(argv[i], argv[i + 1]);
+  for (int i = first; i + 1 < argc; i += 2) {
+    const int rc = probe_file(argv[i], argv[i + 1], owned);
     if (rc != 0) return rc;
   }
   return 0;
