@@ -75,7 +75,8 @@ extern "C" {
  * owner.  The frame, the sub-steps, the cell update and the recomputed ring are the kernel's as they are.  The av_vels tree is the
  * one stated above for lbm_multi_kernel_f64, over the ceil(nx / 32) * ceil(ny / 16) tiles.  Odd nx, nx < 32 and ny < 16 run
  * lbm_step_kernel_f64 exactly as without the flag.  Populations are the same bits either way.  Row partitions (lbm_d2q9_f64_rows.h)
- * refuse this bit; lbm_create of lbm_d2q9.h ignores it. */
+ * refuse this bit (their own, for ranks the tiles do not cover, is LBM_ROWS64_FLAG_MULTI_ANY_SIZE there); lbm_create of lbm_d2q9.h
+ * ignores it. */
 #define LBM64_FLAG_MULTI_ANY_SIZE 4096u
 
 /* t_param (d2q9-bgk.c:79-90) with its three floats as doubles. */

@@ -47,10 +47,22 @@
  * nranks - 1 host additions in rank order: the same bits in every run.  On any other run the flag changes nothing: the one-step kernel,
  * one ghost row, the same name from lbm_rows64_describe and the same av_vels bits as without it.
  *
- * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; uneven
- * ranks under LBM_ROWS64_FLAG_MULTI_STEPS (they run the one-step kernel); overlap of a rank's interior rows or tiles with the exchange.
- * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused, and so is its LBM64_FLAG_MULTI_ANY_SIZE: several steps per
- * exchange on ranks that 32 x 16 tiles do not cover exactly (the edge-tile form of lbm_d2q9_f64.h for row blocks) are a follow-up.
+ * ... ON RANKS OF ANY SIZE (LBM_ROWS64_FLAG_MULTI_ANY_SIZE, opt-in; alone, with a store form, or with LBM_ROWS64_FLAG_MULTI_STEPS, which
+ * it means).  A run that 32 x 16 tiles cover on every rank runs precisely as under LBM_ROWS64_FLAG_MULTI_STEPS: the same kernel, name
+ * and bits.  Any other run whose nx is even and >= 32, whose EVERY rank owns >= 16 rows (lbm_decompose; the ranks may be uneven) and
+ * whose smallest rank owns at least LBM_TUNE_MULTI64_MIN cells advances up to K steps per launch and exchange too, with the EDGE-TILE
+ * form of lbm_rows_multi_kernel_f64 (the edge-tile form of lbm_d2q9_f64.h on a rank's rows): rank r launches ceil(nx / 32) *
+ * ceil(nyl / 16) tiles, nyl its own rows; a tile of its last column or row is shifted back inside the rank's owned rows, over its
+ * neighbour, and owns — stores and counts — only the cells the neighbour does not.  K ghost rows, the exchange, the ORDER and the cut
+ * of a run into launches are those above; the decision is one for all ranks.  The populations are the same bits.  av_vels[t]: per
+ * rank the tree of lbm_multi_kernel_f64 over the rank's ceil(nx / 32) * ceil(nyl / 16) tiles (a shifted tile adds zeros for the cells
+ * it does not own), then the nranks - 1 host additions in rank order.  On any other run (odd nx, nx < 32, a rank of fewer than 16 rows,
+ * a smallest rank below the minimum) the flag changes nothing, as above.
+ *
+ * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; odd nx
+ * under either flag (such runs take the one-step kernel); overlap of a rank's interior rows or tiles with the exchange.
+ * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused, and so is its LBM64_FLAG_MULTI_ANY_SIZE: the row
+ * partition's own bit for ranks that 32 x 16 tiles do not cover exactly is LBM_ROWS64_FLAG_MULTI_ANY_SIZE.
  */
 #ifndef LBM_D2Q9_F64_ROWS_H
 #define LBM_D2Q9_F64_ROWS_H
@@ -66,6 +78,7 @@ extern "C" {
 #define LBM_ROWS64_ABI_VERSION 1
 #define LBM_ROWS64_MAX_RANKS 64     /* MPI_PROCS, d2q9-bgk.c:67 */
 #define LBM_ROWS64_FLAG_MULTI_STEPS 2048u   /* K steps per launch and exchange on K ghost rows where every rank is eligible; else no effect */
+#define LBM_ROWS64_FLAG_MULTI_ANY_SIZE 8192u   /* LBM_ROWS64_FLAG_MULTI_STEPS, and the same by the kernel's edge-tile form where nx is even and >= 32 and every rank owns >= 16 rows */
 
 typedef struct lbm_rows64 lbm_rows64;   /* opaque: the device state of every rank of one run */
 
@@ -74,12 +87,12 @@ int lbm_rows64_abi_version(void);
 /* A whole periodic nx x ny grid (ny >= 3) in the initial state of d2q9-bgk.c:880-902, its rows dealt to `nranks` ranks.
  * obstacles_all = ny*nx ints, the whole grid's map.  devices = nranks HIP ordinals, or NULL: rank r on device r % (device count).
  * Ranks may share a device.  flags: 0, LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES (non-temporal stores of the output grid: by default
- * once a RANK's two grids exceed the Infinity Cache), each with or without LBM_ROWS64_FLAG_MULTI_STEPS (several steps per exchange,
- * above; accepted, like the store forms, before the first HIP call).
+ * once a RANK's two grids exceed the Infinity Cache), each with or without LBM_ROWS64_FLAG_MULTI_STEPS and
+ * LBM_ROWS64_FLAG_MULTI_ANY_SIZE (several steps per exchange, above; accepted, like the store forms, before the first HIP call).
  * Refused, with a message and before the first HIP call: nranks outside 1..LBM_ROWS64_MAX_RANKS; a decomposition that leaves a rank
  * without a row, or the last rank fewer than 3 (d2q9-bgk.c:848-849; ny = 5 on 3 ranks is 2, 1, 2); the shapes lbm64_create refuses;
- * free_cells < 1; any other flag — LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS among them, with or without
- * LBM_ROWS64_FLAG_MULTI_STEPS: they are the whole grid's.  Refused after it: two ranks on distinct devices that hipDeviceCanAccessPeer
+ * free_cells < 1; any other flag — LBM64_FLAG_TILE_STEPS, LBM64_FLAG_MULTI_STEPS and LBM64_FLAG_MULTI_ANY_SIZE among them, with or without
+ * the two flags above: they are the whole grid's.  Refused after it: two ranks on distinct devices that hipDeviceCanAccessPeer
  * denies. */
 int lbm_rows64_create(lbm_rows64** run, const lbm64_params* params, int free_cells, const int* obstacles_all, int nranks,
                       const int* devices, unsigned flags);
@@ -110,7 +123,8 @@ int lbm_rows64_last_run_ms(lbm_rows64* run, double* ms, int* launches);
  * "lbm_rows_kernel_f64<2,nt>"), the rank count, and of the rank with the most work blocks: those blocks (one more block folds the
  * previous step's sums) and the cells a block advances; the bytes of all ranks' grids, ghost rows included.  Under
  * LBM_ROWS64_FLAG_MULTI_STEPS on an eligible run: "lbm_rows_multi_kernel_f64<K>" or "<K,nt>", the tiles of the rank with the most,
- * 512 cells, and 2 * 9 * 8 * nx * (ny + 2 * K * nranks) bytes. */
+ * 512 cells, and 2 * 9 * 8 * nx * (ny + 2 * K * nranks) bytes.  Under LBM_ROWS64_FLAG_MULTI_ANY_SIZE on a run that takes the edge-tile
+ * form: "lbm_rows_multi_kernel_f64<K,edge>" or "<K,nt,edge>" and the same three figures. */
 int lbm_rows64_describe(const lbm_rows64* run, char* kernel_name, size_t len, int* nranks, long long* blocks, long long* cells_per_block,
                         long long* state_bytes);
 

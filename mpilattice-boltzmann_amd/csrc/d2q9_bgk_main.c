@@ -24,8 +24,9 @@
  * partitioned by the reference's rule, rank r lives on device LBM_DEVICES[r] (a comma list; default r % device count; ranks may share
  * a device), one host thread drives all of them and the edge rows travel as peer-to-peer stores ordered by stream events.  The same
  * five lines and two files; final_state.dat is the same bytes for every N.  Of LBM_FLAGS it takes 0, 1 and 2, each with or without
- * 2048 (LBM_ROWS64_FLAG_MULTI_STEPS: several steps per launch and exchange where every rank is eligible, the same files).  LBM64_RANKS
- * without LBM_PRECISION=double is refused.
+ * 2048 (LBM_ROWS64_FLAG_MULTI_STEPS: several steps per launch and exchange where every rank is eligible, the same files) and
+ * 8192 (LBM_ROWS64_FLAG_MULTI_ANY_SIZE: 2048, and runs of any even width from 32 whose every rank owns 16 rows or more, with the
+ * kernel's edge-tile form).  LBM64_RANKS without LBM_PRECISION=double is refused.
  * LBM_PRECISION=double LBM_DIGEST=1, with or without LBM64_RANKS, adds one line on stderr after the run, "state digest: <16 hex digits>":
  * the digest of the final populations (include/lbm_d2q9_f64_digest.h), the same for every way of advancing the same deck.  LBM_DIGEST=1
  * without LBM_PRECISION=double is refused.
@@ -139,8 +140,8 @@ static int main_double(char* argv[])
     const char* list = getenv("LBM_DEVICES");
     int* device = NULL;
     int r;
-    if (flags < 0 || (flags & ~(int)LBM_ROWS64_FLAG_MULTI_STEPS) > 2)
-      die("LBM_FLAGS: with LBM64_RANKS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES), each with or without 2048 (LBM_ROWS64_FLAG_MULTI_STEPS)", __LINE__, __FILE__);
+    if (flags < 0 || (flags & ~(int)(LBM_ROWS64_FLAG_MULTI_STEPS | LBM_ROWS64_FLAG_MULTI_ANY_SIZE)) > 2)
+      die("LBM_FLAGS: with LBM64_RANKS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES), each with or without 2048 (LBM_ROWS64_FLAG_MULTI_STEPS) and 8192 (LBM_ROWS64_FLAG_MULTI_ANY_SIZE)", __LINE__, __FILE__);
     if (list && *list) {
       device = (int*)xmalloc(sizeof(int) * (size_t)nranks);
       for (r = 0; r < nranks; ++r) {

@@ -1,5 +1,5 @@
-// rows_multi64.h — row-partitioned runs of the double-precision mode, several steps per exchange (LBM_ROWS64_FLAG_MULTI_STEPS):
-// lbm_rows_multi_kernel_f64<K, NT, FULL>, the partition form of lbm_multi_kernel_f64 (kernels/multi64.h: up to K steps of one rank per
+// rows_multi64.h — row-partitioned runs of the double-precision mode, several steps per exchange (LBM_ROWS64_FLAG_MULTI_STEPS,
+// LBM_ROWS64_FLAG_MULTI_ANY_SIZE): lbm_rows_multi_kernel_f64<K, NT, FULL, EDGE>, the partition form of lbm_multi_kernel_f64 (kernels/multi64.h: up to K steps of one rank per
 // launch), and lbm64_push_ghost_rows_kernel, which stores a rank's K first and K last owned rows into its neighbours' ghost rows.
 // Part of the translation unit lbm_rows64.hip (gfx950 only, -ffp-contract=off); include/lbm_d2q9_f64_rows.h states the contract.
 //
@@ -24,7 +24,21 @@
 //                   periodic): bit c of the storage cell c.  nx is even, so a pair's two bits sit in one word.
 //   sum|u| terms    count for owned cells, as before: ghost rows are ring cells of the edge tiles.
 // Bounds: a pull reads storage cells only, shifted by one double into the planes' guards at most; stores go to owned cells.
+//
+// EDGE (LBM_ROWS64_FLAG_MULTI_ANY_SIZE): multi64.h's edge-tile form on a rank's rows.  ceil(nx / TX) x ceil(nyl / TY) tiles on a rank
+// they do not cover exactly (nx even and >= TX, nyl >= TY; ranks of one run may differ in nyl).  Tile (tx, ty) starts at column
+// x0 = min(TX tx, nx - TX) and OWNED row y0 = min(TY ty, nyl - TY): a tile of the last column or row is shifted back inside the rank's
+// owned rows, over its neighbour, and owns only its cells at tile-local x >= TX tx - x0, y >= TY ty - y0, so every owned cell of the
+// rank has exactly one owner.  Only owned cells are stored and counted; the others are computed like ring cells.  What the bounds
+// above become:
+//   rows            y0 <= nyl - TY, so the region grown by e spans storage rows ghost + y0 - e >= 1 to ghost + y0 + TY + e - 1 <=
+//                   ghost + nyl + e - 1, as before; the pull reads one row further, inside the storage.
+//   obstacle bits   x0 and gx are even (nx and TX are), so a pair's first cell is even and its two bits still sit in one word.
+//   x wrap          nx >= TX = 32 > gx, and x0 - gx + rx lies in -gx .. nx + gx - 2: one correction suffices, as before.
+//   row ny-2        by the whole grid's row of the storage row, which does not depend on the tile: unchanged.
 #pragma once
+#include <type_traits>
+
 #include "multi64.h"
 
 namespace {
@@ -37,7 +51,7 @@ struct RowsMulti64Args {
   int nx, ny;                  // of the WHOLE grid (ny: for the row-ny-2 flag alone)
   int ghost;                   // ghost rows on each side of the owned rows: the K of a full launch
   int row0;                    // the whole grid's row of storage row 0, y0 - ghost: -ghost .. ny - 1 - ghost
-  int tiles_x;                 // nx / TX
+  int tiles_x;                 // nx / TX (EDGE: rounded up)
   int ksteps;                  // 1..K steps in this launch (FULL: K)
   double omega, accel_w1, accel_w2;
   int accel_row;               // ny-2, a row of the WHOLE grid
@@ -48,6 +62,12 @@ struct RowsMulti64Args {
   double* sums;                // this rank's per-step totals of this run
   int* counter;
 };
+// What the EDGE form takes: a type of its own, so that the kernel arguments of the other form (and with them the offsets of the
+// hidden ones behind them) stay what they were.
+struct RowsMulti64EdgeArgs : RowsMulti64Args {
+  int last_y0;                 // the owned row at which the rank's last tile row starts: nyl - TY
+};
+template <bool EDGE> using RowsMulti64ArgsOf = std::conditional_t<EDGE, RowsMulti64EdgeArgs, RowsMulti64Args>;
 
 // Rows that storage row sy pulls from: no wrap, its neighbours are rows of the storage (1 <= sy <= rows - 2).
 __device__ __forceinline__ Rows64 rows_of_storage(uint32_t nx, uint32_t sy)
@@ -60,8 +80,9 @@ __device__ __forceinline__ Rows64 rows_of_storage(uint32_t nx, uint32_t sy)
 }
 
 // FULL: the launch makes exactly K steps, so every region size is a compile-time constant.
-template <int K, bool NT, bool FULL>
-__global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_multi_kernel_f64(const RowsMulti64Args a)
+// EDGE: the edge-tile form described above.
+template <int K, bool NT, bool FULL, bool EDGE = false>
+__global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_multi_kernel_f64(const RowsMulti64ArgsOf<EDGE> a)
 {
   static_assert(multi64_k_ok(K), "unsupported steps per launch");
   constexpr int TX = kMulti64TX, TY = kMulti64TY, FX = multi64_frame_x(K), FY = multi64_frame_y(K), FC = FX * FY;
@@ -96,6 +117,11 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int k_total = FULL ? K : a.ksteps;
   const size_t ps = a.ps;
+  // the tile's first column and owned row (EDGE: shifted back inside the rank).  Formed where they are used, x before y, not here, as in
+  // multi64.h: the existing instantiations then compile to the instructions they had before EDGE was a parameter
+  // (profiles/r22/device_asm_identical.txt).
+  auto tile_x0 = [&]() __attribute__((always_inline)) { return EDGE ? min(tx * TX, a.nx - TX) : tx * TX; };
+  auto tile_y0 = [&]() __attribute__((always_inline)) { if constexpr (EDGE) return min(ty * TY, a.last_y0); else return ty * TY; };
 
   double acc[kMulti64Accs];
 #pragma unroll
@@ -109,14 +135,16 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
     const bool last = !FULL && e == 0;
     if (tid < wp * hy) {
       const int ry = FULL ? tid / wp : small_div(tid, wp), rx = 2 * (tid - ry * wp);
-      int x = tx * TX - gx + rx; if (x < 0) x += a.nx; else if (x >= a.nx) x -= a.nx;      // -gx .. nx + gx - 2, and nx >= TX > gx
-      const int sy = a.ghost + ty * TY - e + ry;                                            // storage row: ghost - e .. ghost + nyl + e - 1, and ghost > e
+      const int x0 = tile_x0(), own_x = EDGE ? tx * TX - x0 : 0;
+      int x = x0 - gx + rx; if (x < 0) x += a.nx; else if (x >= a.nx) x -= a.nx;      // -gx .. nx + gx - 2, and nx >= TX > gx
+      const int y0 = tile_y0(), own_y = EDGE ? ty * TY - y0 : 0;
+      const int sy = a.ghost + y0 - e + ry;                                            // storage row: ghost - e .. ghost + nyl + e - 1, and ghost > e
       int gy = a.row0 + sy; if (gy < 0) gy += a.ny; else if (gy >= a.ny) gy -= a.ny;       // the whole grid's row: -e .. ny + e - 1 before, and ny >= TY > e
       const uint32_t cell = static_cast<uint32_t>(sy) * static_cast<uint32_t>(a.nx) + static_cast<uint32_t>(x);
       const uint32_t mbits = (a.mask[cell >> 5] >> (cell & 31u)) & 3u;                       // cell is even: both bits in one word
       const bool on_row = gy == a.accel_row;                                                 // the owned row ny-2 and every ghost or ring copy of it
       const bool accel = on_row && (!last || a.accel_last);
-      const bool owned = rx >= gx && rx < gx + TX && ry >= e && ry < e + TY;                // both cells of a pair, or neither
+      const bool owned = rx >= gx + own_x && rx < gx + TX && ry >= e + own_y && ry < e + TY;   // both cells of a pair, or neither
       d2 p[9];
       pull_pair_f64(a.src, ps, static_cast<uint32_t>(a.nx), rows_of_storage(static_cast<uint32_t>(a.nx), static_cast<uint32_t>(sy)), static_cast<uint32_t>(x), p);
       if (last) {
@@ -126,13 +154,16 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
           double t[9], q[9];
 #pragma unroll
           for (int k = 0; k < 9; ++k) t[k] = p[k][j];
-          acc[0] += finish_cell_f64(t, (mbits >> j) & 1u, a.omega, accel, a.accel_w1, a.accel_w2, q);   // e = 0: every cell is owned
+          const double term = finish_cell_f64(t, (mbits >> j) & 1u, a.omega, accel, a.accel_w1, a.accel_w2, q);
+          if (!EDGE || owned) acc[0] += term;                                                // e = 0: every cell is owned, except in a shifted tile
 #pragma unroll
           for (int k = 0; k < 9; ++k) out[k][j] = q[k];
         }
         double* d = a.dst + cell;
+        if (!EDGE || owned) {
 #pragma unroll
-        for (int k = 0; k < 9; ++k) store2<NT>(d + k * ps, out[k]);
+          for (int k = 0; k < 9; ++k) store2<NT>(d + k * ps, out[k]);
+        }
       } else {
         const int c = (EY - e + ry) * FX + (EX - gx + rx);
         const uint32_t common = (owned ? 2u : 0u) | (on_row ? 4u : 0u);
@@ -193,7 +224,9 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
       // 0, 2, 4, 6, 8, the odd lane 1, 3, 5, 7: each sends the other the half it does not store (bits, by a DPP move).
       const int ry = tid / TX, rx = tid - ry * TX;
       const bool odd = (tid & 1) != 0;
-      double* d = a.dst + (static_cast<size_t>(a.ghost + ty * TY + ry) * a.nx + static_cast<size_t>(tx * TX + (rx & ~1)));   // owned row ty * TY + ry
+      const int x0 = tile_x0(), y0 = tile_y0(), own_x = EDGE ? tx * TX - x0 : 0, own_y = EDGE ? ty * TY - y0 : 0;
+      const bool stores = !EDGE || (rx >= own_x && ry >= own_y);      // owned (own_x is even: both lanes of a pair, or neither); every lane makes the exchange
+      double* d = a.dst + (static_cast<size_t>(a.ghost + y0 + ry) * a.nx + static_cast<size_t>(x0 + (rx & ~1)));   // owned row y0 + ry
 #pragma unroll
       for (int j = 0; j < 5; ++j) {
         constexpr int kLastOdd = 7;
@@ -202,7 +235,7 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
         const double send = odd ? out[0][ke] : out[0][ko];
         const double recv = dpp_full<0xB1>(send);                      // quad_perm [1,0,3,2]: lane l ^ 1
         const d2 v = odd ? d2{recv, mine} : d2{mine, recv};
-        if (j < 4 || !odd) store2<NT>(d + static_cast<size_t>(odd ? ko : ke) * ps, v);
+        if ((j < 4 || !odd) && stores) store2<NT>(d + static_cast<size_t>(odd ? ko : ke) * ps, v);
       }
     }
   };
@@ -225,8 +258,10 @@ __global__ void __launch_bounds__(kMulti64Lanes, kMulti64WavesPerSimd) lbm_rows_
 // The exchange of one rank after a launch: all nine planes of its first `ghost` owned rows (storage rows ghost .. 2 ghost - 1) into the
 // upper ghost rows of the rank below (its storage rows ghost + down_nyl ..), and of its last `ghost` owned rows (storage rows nyl ..
 // nyl + ghost - 1) into the lower ghost rows of the rank above (its storage rows 0 .. ghost - 1), in the neighbour's grid of the same
-// parity.  Sources are owned rows, targets ghost rows: disjoint even where the rank is its own neighbour (nyl >= 16 > 2 ghost).  A
-// neighbour's grid may be another device's memory (peer access): plain 16-byte vector stores (nx is even, every row starts at an even
+// parity.  Sources are owned rows, targets ghost rows: disjoint even where the rank is its own neighbour (nyl >= 16 > 2 ghost).  Ranks of
+// an uneven run (EDGE) differ in nyl and plane stride: the targets are formed from the NEIGHBOUR's down_nyl, down_ps and up_ps, and
+// every rank owns >= 16 rows, so the same holds.
+// A neighbour's grid may be another device's memory (peer access): plain 16-byte vector stores (nx is even, every row starts at an even
 // double).  Nothing waits on the device.
 struct RowsPushGhost64Args {
   const double* grid;          // this rank's grid just written, plane 0 storage row 0

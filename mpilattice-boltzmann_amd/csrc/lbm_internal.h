@@ -154,12 +154,14 @@ struct PlanRows64 {
 };
 static_assert(sizeof(PlanRows64) == 14 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
 constexpr int kMaxRows64Ranks = 64;  // MPI_PROCS, d2q9-bgk.c:67
-// The flags lbm_rows64_create takes: a store form, LBM_ROWS64_FLAG_MULTI_STEPS (lbm_d2q9_f64_rows.h; lbm_plan.cpp holds the two equal).
-constexpr unsigned kFlagRows64MultiSteps = 2048u;
-constexpr unsigned kFlagsRows64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | kFlagRows64MultiSteps;
+// The flags lbm_rows64_create takes: a store form, LBM_ROWS64_FLAG_MULTI_STEPS, LBM_ROWS64_FLAG_MULTI_ANY_SIZE (lbm_d2q9_f64_rows.h;
+// lbm_plan.cpp holds each pair equal).
+constexpr unsigned kFlagRows64MultiSteps = 2048u, kFlagRows64MultiAnySize = 8192u;
+constexpr unsigned kFlagsRows64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | kFlagRows64MultiSteps | kFlagRows64MultiAnySize;
 // Fills *out for rank `rank` of `nranks`; checks every argument itself.  0, or 1 and the message in lbm_last_error(): nranks outside
 // 1..64, a rank without a row, a last rank with fewer than 3 rows, the shapes lbm64_create refuses, any flag outside kFlagsRows64.
-// LBM_ROWS64_FLAG_MULTI_STEPS changes nothing in *out but .flags: what it adds is PlanRowsMulti64's.
+// LBM_ROWS64_FLAG_MULTI_STEPS and LBM_ROWS64_FLAG_MULTI_ANY_SIZE change nothing in *out but .flags: what they add is PlanRowsMulti64's
+// and PlanRowsMultiAny64's.
 int plan64_rows(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanRows64* out);
 void plan64_rows_kernel_name(const PlanRows64& plan, char* kernel_name, size_t len);
 
@@ -184,6 +186,31 @@ void plan64_rows_multi(const Knobs& knobs, const lbm64_params* p, const PlanRows
 void plan64_rows_multi_kernel_name(const PlanRowsMulti64& plan, char* kernel_name, size_t len);
 // Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
 int plan64_rows_multi_next_steps(const PlanRowsMulti64& plan, int left);
+
+// The multi-step launches of one rank of a row-partitioned run, whichever flag asks for them: what PlanRowsMulti64 says where the tiles
+// cover every rank exactly (LBM_ROWS64_FLAG_MULTI_STEPS, or LBM_ROWS64_FLAG_MULTI_ANY_SIZE, which means it), and under
+// LBM_ROWS64_FLAG_MULTI_ANY_SIZE the edge-tile form of lbm_rows_multi_kernel_f64 (kernels/rows_multi64.h EDGE) on a run they do not
+// cover: nx even and >= TX, EVERY rank of at least TY rows, the smallest rank of at least LBM_TUNE_MULTI64_MIN cells.  One decision for
+// all ranks: ranks of an uneven run differ in tiles_y, n_tiles, last_y0, mask_words, partials_cap, ps and grid_doubles and agree on the
+// rest.  lbm_rows64.hip allocates and launches by this plan.  Plain data in this order (tests/test_plan64_rows_any.py mirrors it);
+// beside PlanRows64 and PlanRowsMulti64, whose layouts and values do not change.
+struct PlanRowsMultiAny64 {
+  int multi_kernel, edge;            // every rank advances up to K steps per launch with lbm_rows_multi_kernel_f64; in its edge-tile form
+  int K, ghost;                      // as PlanRowsMulti64
+  int tiles_x, tiles_y, n_tiles;     // ceil(nx / TX), ceil(ny_local / TY) of THIS rank, their product (= work blocks of a launch); 0 where no multi-step kernel can tile the run
+  int last_x0, last_y0;              // where the last tile column and this rank's last tile row start: nx - TX, and the OWNED row ny_local - TY
+  int block, lds_bytes;              // as PlanRowsMulti64
+  int nt_stores;                     // as PlanRowsMulti64
+  int mask_words;                    // as PlanRowsMulti64
+  int partials_cap;                  // K * n_tiles + 1
+  long long ps, grid_doubles;        // as PlanRowsMulti64
+};
+static_assert(sizeof(PlanRowsMultiAny64) == 14 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
+// Fills *out for the rank whose PlanRows64 is `rows` (plan64_rows has checked the arguments).
+void plan64_rows_multi_any(const Knobs& knobs, const lbm64_params* p, const PlanRows64& rows, PlanRowsMultiAny64* out);
+void plan64_rows_multi_any_kernel_name(const PlanRowsMultiAny64& plan, char* kernel_name, size_t len);
+// Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
+int plan64_rows_multi_any_next_steps(const PlanRowsMultiAny64& plan, int left);
 
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
@@ -282,3 +309,9 @@ extern "C" int lbm_plan64_rows_multi_sizeof(void);
 extern "C" int lbm_plan64_rows_multi(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMulti64* out);
 extern "C" int lbm_plan64_rows_multi_kernel_name(const lbm_internal::PlanRowsMulti64* plan, char* kernel_name, size_t len);
 extern "C" int lbm_plan64_rows_multi_run_launches(const lbm_internal::PlanRowsMulti64* plan, int n_steps, int* steps, int* full, int cap);
+// And for a rank's multi-step launches under either flag, LBM_ROWS64_FLAG_MULTI_ANY_SIZE's edge-tile form among them: the
+// PlanRowsMultiAny64 that rank would get, its kernel's name ("" where multi_kernel is 0), and the launches of a run on one rank.
+extern "C" int lbm_plan64_rows_multi_any_sizeof(void);
+extern "C" int lbm_plan64_rows_multi_any(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMultiAny64* out);
+extern "C" int lbm_plan64_rows_multi_any_kernel_name(const lbm_internal::PlanRowsMultiAny64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_rows_multi_any_run_launches(const lbm_internal::PlanRowsMultiAny64* plan, int n_steps, int* steps, int* full, int cap);

@@ -659,10 +659,11 @@ void plan64_rows_kernel_name(const PlanRows64& c, char* kernel_name, size_t len)
 // pushes (its first and last K owned ones) and the ghost rows it receives are disjoint even where it is its own neighbour.
 static_assert(LBM_ROWS64_FLAG_MULTI_STEPS == kFlagRows64MultiSteps, "lbm_internal.h restates the header's flag");
 static_assert(kMulti64TY > 2 * kMulti64MaxK, "a rank's pushed rows and ghost rows are disjoint");
+constexpr int kRowsMulti64DefaultMin = 1 << 17;                           // cells of the smallest rank
 void plan64_rows_multi(const Knobs& knobs, const lbm64_params* p, const PlanRows64& rows, PlanRowsMulti64* out)
 {
   PlanRowsMulti64 m{};
-  constexpr int kDefaultK = 4, kDefaultMin = 1 << 17;                     // cells of the smallest rank
+  constexpr int kDefaultK = 4, kDefaultMin = kRowsMulti64DefaultMin;
   m.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kDefaultK;     // a malformed or unbuilt value: the default
   m.ghost = m.K;
   m.block = kMulti64Lanes;
@@ -677,7 +678,7 @@ void plan64_rows_multi(const Knobs& knobs, const lbm64_params* p, const PlanRows
   }
   m.tiles_x = tiles ? p->nx / kMulti64TX : 0;
   m.n_tiles = tiles ? m.tiles_x * (rows.ny_local / kMulti64TY) : 0;
-  m.multi_kernel = (rows.flags & kFlagRows64MultiSteps) != 0u && tiles &&
+  m.multi_kernel = (rows.flags & (kFlagRows64MultiSteps | kFlagRows64MultiAnySize)) != 0u && tiles &&   // the latter means the former
                    static_cast<long long>(p->nx) * smallest >= static_cast<long long>(knob_or(knobs.multi64_min, kDefaultMin));
   const size_t storage = static_cast<size_t>(p->nx) * (rows.ny_local + 2 * m.ghost);
   m.ps = static_cast<long long>(plane_stride_floats(storage, knobs.skew));   // always even
@@ -700,6 +701,65 @@ void plan64_rows_multi_kernel_name(const PlanRowsMulti64& m, char* kernel_name, 
 int plan64_rows_multi_next_steps(const PlanRowsMulti64& m, int left)
 {
   return std::min(m.K, left);
+}
+
+// The multi-step launches of a rank: plan64_rows_multi's answer where the tiles cover every rank, and with
+// LBM_ROWS64_FLAG_MULTI_ANY_SIZE the edge-tile form on a run they do not cover — nx even (aligned x-pairs) and >= TX, EVERY rank of at
+// least TY rows (a shifted tile lies inside the rank's owned rows; the pushed and the ghost rows stay disjoint: TY > 2 K), the smallest
+// rank of at least LBM_TUNE_MULTI64_MIN cells (plan64_rows_multi's knob and default).  ceil(nx / TX) x ceil(ny_local / TY) tiles on
+// this rank; its last tile column and row start at nx - TX and at the owned row ny_local - TY.  Storage, window bitfield, store rule
+// and K are plan64_rows_multi's.
+// Measured (profiles/r22/f64_rows_any.txt, all ranks on one MI355X), device us per step of the parent commit's run of the same shape
+// (the one-step kernel there) | the edge form at K = 4, on 1 / 2 / 8 ranks:
+//   8190x8190  2008.0 | 693.2   1716.9 | 720.2   1929.0 | 738.6      4098x4100  546.9 | 182.8   506.2 | 184.3   526.6 | 189.5
+//   2050x2046  113.05 | 48.28   130.67 | 50.91   159.16 | 51.25      1022x1026  28.91 | 14.07   38.85 | 15.74   59.90 | 20.20
+// The edge form wins by more than both max - min spreads together at every size and rank count; at the smallest rank measured,
+// 1022x1026 on 8 ranks (130 816 cells a rank), by 39.70 us against spreads of 30.01 us (52.94 against 31.01 beside this tree's own
+// unflagged run).  By plan64_rows_multi's rule the minimum is the smallest measured rank size that wins, which is the smallest size
+// measured: the edge form gets no minimum of its own and shares the rows' default of 2^17 cells (which that one run, measured with
+// the minimum lowered to 0, is 256 cells short of).  8192x8192, the control: under LBM_ROWS64_FLAG_MULTI_STEPS 642.2 / 678.8 / 685.1
+// against the parent's 643.1 / 675.5 / 684.1 (the same kernel and instructions: within both spreads), under this flag 644.8 / 676.2 / 682.4.
+static_assert(LBM_ROWS64_FLAG_MULTI_ANY_SIZE == kFlagRows64MultiAnySize, "lbm_internal.h restates the header's flag");
+static_assert((kFlagRows64MultiAnySize & (LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES | kFlagRows64MultiSteps | kFlags64)) == 0u, "a bit of its own");
+void plan64_rows_multi_any(const Knobs& knobs, const lbm64_params* p, const PlanRows64& rows, PlanRowsMultiAny64* out)
+{
+  PlanRowsMulti64 m{};
+  plan64_rows_multi(knobs, p, rows, &m);
+  PlanRowsMultiAny64 a{};
+  a.K = m.K; a.ghost = m.ghost;
+  a.block = m.block; a.lds_bytes = m.lds_bytes;
+  a.nt_stores = m.nt_stores;
+  a.mask_words = m.mask_words;
+  a.ps = m.ps; a.grid_doubles = m.grid_doubles;
+  int nyl[kMaxRows64Ranks], dis[kMaxRows64Ranks];
+  (void)lbm_decompose(p->ny, rows.nranks, nyl, dis);                       // plan64_rows made `rows` of it
+  const int smallest = *std::min_element(nyl, nyl + rows.nranks);
+  const bool exact = m.n_tiles > 0;
+  const bool shape = exact || (p->nx % kPairCells == 0 && p->nx >= kMulti64TX && smallest >= kMulti64TY);
+  a.tiles_x = shape ? (p->nx + kMulti64TX - 1) / kMulti64TX : 0;
+  a.tiles_y = shape ? (rows.ny_local + kMulti64TY - 1) / kMulti64TY : 0;
+  a.n_tiles = a.tiles_x * a.tiles_y;
+  a.last_x0 = shape ? p->nx - kMulti64TX : 0;
+  a.last_y0 = shape ? rows.ny_local - kMulti64TY : 0;
+  a.edge = (rows.flags & kFlagRows64MultiAnySize) != 0u && shape && !exact &&
+           static_cast<long long>(p->nx) * smallest >= static_cast<long long>(knob_or(knobs.multi64_min, kRowsMulti64DefaultMin));
+  a.multi_kernel = m.multi_kernel || a.edge;
+  a.partials_cap = a.K * a.n_tiles + 1;
+  *out = a;
+}
+
+void plan64_rows_multi_any_kernel_name(const PlanRowsMultiAny64& a, char* kernel_name, size_t len)
+{
+  if (!a.multi_kernel) { kernel_name[0] = '\0'; return; }
+  const char* form = a.edge ? (a.nt_stores ? "lbm_rows_multi_kernel_f64<%d,nt,edge>" : "lbm_rows_multi_kernel_f64<%d,edge>")
+                            : (a.nt_stores ? "lbm_rows_multi_kernel_f64<%d,nt>" : "lbm_rows_multi_kernel_f64<%d>");
+  std::snprintf(kernel_name, len, form, a.K);
+}
+
+// plan64_multi_next_steps' rule: floor(n / K) launches of K steps and at most one shorter launch, the last.
+int plan64_rows_multi_any_next_steps(const PlanRowsMultiAny64& a, int left)
+{
+  return std::min(a.K, left);
 }
 
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
@@ -1147,6 +1207,34 @@ int lbm_plan64_rows_multi_run_launches(const lbm_internal::PlanRowsMulti64* plan
   int n = 0;
   for (int left = n_steps; left > 0; ++n) {
     const int k = lbm_internal::plan64_rows_multi_next_steps(*plan, left);
+    if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
+    left -= k;
+  }
+  return n;
+}
+
+int lbm_plan64_rows_multi_any_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanRowsMultiAny64)); }
+int lbm_plan64_rows_multi_any(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMultiAny64* out)
+{
+  lbm_internal::PlanRows64 rows;
+  if (!out) { set_error("lbm_plan64_rows_multi_any: null argument"); return 1; }
+  const Knobs knobs = knobs_from_env();
+  if (lbm_internal::plan64_rows(knobs, p, nranks, rank, flags, &rows)) return 1;
+  lbm_internal::plan64_rows_multi_any(knobs, p, rows, out);
+  return 0;
+}
+int lbm_plan64_rows_multi_any_kernel_name(const lbm_internal::PlanRowsMultiAny64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_rows_multi_any_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_rows_multi_any_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_rows_multi_any_run_launches(const lbm_internal::PlanRowsMultiAny64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || !multi64_k_ok(plan->K) || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_rows_multi_any_run_launches: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_internal::plan64_rows_multi_any_next_steps(*plan, left);
     if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
     left -= k;
   }

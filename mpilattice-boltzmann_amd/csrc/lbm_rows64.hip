@@ -28,7 +28,8 @@
 // av_vels[t]: each rank's sums[t] (folded as lbm64_run folds them) copied to the host and added there in rank order, times
 // 1.0 / free_cells: one more serial level of the summation tree, nranks - 1 additions, the same bits in every run.
 //
-// SEVERAL STEPS PER EXCHANGE (LBM_ROWS64_FLAG_MULTI_STEPS where PlanRowsMulti64.multi_kernel, the same on every rank).  Rank r then keeps
+// SEVERAL STEPS PER EXCHANGE (LBM_ROWS64_FLAG_MULTI_STEPS or LBM_ROWS64_FLAG_MULTI_ANY_SIZE where PlanRowsMultiAny64.multi_kernel, the
+// same on every rank; .edge, the same on every rank too: the kernel's edge-tile form, on ranks that may differ in rows, tiles and strides).  Rank r then keeps
 // two grids of ny_local + 2 K storage rows (kernels/rows_multi64.h has the layout) and, beside the slab's bitfield of its owned rows,
 // a WINDOW bitfield over all its storage rows.  A launch of a rank is lbm_rows_multi_kernel_f64, k <= K steps from grid A into grid B,
 // then lbm64_push_ghost_rows_kernel, which stores all nine planes of B's first and last K owned rows into the neighbours' ghost rows of
@@ -43,7 +44,8 @@
 // A launch of k steps consumes k of the K ghost rows on each side; the K rows pushed after it are whole again.  Degenerate rings: with
 // one rank the rank is its own neighbour, with two both neighbours are the other rank; the rows a push reads (owned) and writes (ghost)
 // are disjoint in both, because ny_local >= 16 > 2 K.  av_vels[t]: per rank lbm_multi_kernel_f64's tree over the rank's tiles (the
-// last launch's vectors folded by lbm64_fold_kernel(..., n_tiles, k, ...)), then the same nranks - 1 host additions.
+// last launch's vectors folded by lbm64_fold_kernel(..., n_tiles, k, ...)), then the same nranks - 1 host additions.  n_tiles is each
+// rank's OWN count everywhere (the launch, n_prev of the next launch's fold block, the last fold): uneven ranks differ in it.
 // The one-step path's code and launches are what they were.
 //
 // gfx950 only: 64-wide wavefronts (block_sum).
@@ -70,7 +72,7 @@ namespace {
 
 struct Rank64 {
   lbm_internal::PlanRows64 plan{};   // written once (lbm_plan.cpp plan64_rows)
-  lbm_internal::PlanRowsMulti64 multi{};   // lbm_rows_multi_kernel_f64's part of it (plan64_rows_multi): written once; multi_kernel is the same on every rank
+  lbm_internal::PlanRowsMultiAny64 multi{};   // lbm_rows_multi_kernel_f64's part of it (plan64_rows_multi_any): written once; multi_kernel, edge and K are the same on every rank
   uint32_t* window_mask = nullptr;   // multi_kernel: the obstacle bitfield over ALL storage rows of the rank, bit c of the storage cell c
   Slab64 slab;                       // the rank's row block on its device (lbm_f64_slab.h): grid[g] is plane 0 STORAGE row 0, the owned cells start one row on (multi_kernel: K rows)
   hipEvent_t pushed[2] = {nullptr, nullptr}; // this rank's push of step t has finished: pushed[t & 1]
@@ -103,9 +105,12 @@ constexpr Rows64Kernel kRows64Kernels[2][2] = {
 };
 
 using RowsMulti64Kernel = void (*)(RowsMulti64Args);
-// every instantiation of the rank's multi-step kernel, by multi64_row(K, NT, FULL) (lbm_geometry.h, as kMulti64Kernels of lbm_f64.hip)
-#define LBM_ROWS_MULTI64_ROWS(K) &lbm_rows_multi_kernel_f64<K, false, false>, &lbm_rows_multi_kernel_f64<K, false, true>, &lbm_rows_multi_kernel_f64<K, true, false>, &lbm_rows_multi_kernel_f64<K, true, true>
-constexpr RowsMulti64Kernel kRowsMulti64Kernels[kMulti64Rows] = {LBM_ROWS_MULTI64_ROWS(2), LBM_ROWS_MULTI64_ROWS(3), LBM_ROWS_MULTI64_ROWS(4)};
+using RowsMulti64EdgeKernel = void (*)(RowsMulti64EdgeArgs);
+// every instantiation of the rank's multi-step kernel, by multi64_row(K, NT, FULL) (lbm_geometry.h, as kMulti64Kernels of lbm_f64.hip);
+// and of its edge-tile form, which takes one argument more
+#define LBM_ROWS_MULTI64_ROWS(K, EDGE) &lbm_rows_multi_kernel_f64<K, false, false, EDGE>, &lbm_rows_multi_kernel_f64<K, false, true, EDGE>, &lbm_rows_multi_kernel_f64<K, true, false, EDGE>, &lbm_rows_multi_kernel_f64<K, true, true, EDGE>
+constexpr RowsMulti64Kernel kRowsMulti64Kernels[kMulti64Rows] = {LBM_ROWS_MULTI64_ROWS(2, false), LBM_ROWS_MULTI64_ROWS(3, false), LBM_ROWS_MULTI64_ROWS(4, false)};
+constexpr RowsMulti64EdgeKernel kRowsMulti64EdgeKernels[kMulti64Rows] = {LBM_ROWS_MULTI64_ROWS(2, true), LBM_ROWS_MULTI64_ROWS(3, true), LBM_ROWS_MULTI64_ROWS(4, true)};
 #undef LBM_ROWS_MULTI64_ROWS
 static_assert(kMulti64MinK == 2 && kMulti64MaxK == 4 && multi64_row(2, false, true) == 1 && multi64_row(4, true, true) == 11, "the order of kRowsMulti64Kernels");
 static_assert(multi64_lds_bytes(kMulti64MaxK) <= 65536, "no launch asks for more dynamic LDS than a kernel gets without hipFuncSetAttribute");
@@ -199,13 +204,13 @@ int run_multi(lbm_rows64* c, int n_steps, double* av_vels)
   }
   int parity = 0, launches = 0, last_vecs = 0;
   for (int left = n_steps; left > 0; ++launches) {
-    const int steps = lbm_internal::plan64_rows_multi_next_steps(c->ranks[0].multi, left);     // K is the same on every rank
+    const int steps = lbm_internal::plan64_rows_multi_any_next_steps(c->ranks[0].multi, left);     // K is the same on every rank
     left -= steps;
     const int before = (launches + 1) & 1, now = launches & 1;     // the pushed events of launch - 1 and of this launch
     for (int r = 0; r < nranks; ++r) {
       Rank64& k = c->ranks[r];
       const Slab64& s = k.slab;
-      const lbm_internal::PlanRowsMulti64& m = k.multi;
+      const lbm_internal::PlanRowsMultiAny64& m = k.multi;
       const int down = (r + nranks - 1) % nranks, up = (r + 1) % nranks;
       if (use_device(c, s.device)) return 1;
       if (down != r) HIP_TRY(hipStreamWaitEvent(s.stream, c->ranks[down].pushed[before], 0));
@@ -227,10 +232,19 @@ int run_multi(lbm_rows64* c, int n_steps, double* av_vels)
       a.accel_last = left > 0;
       a.partials_out = s.partials[parity];
       a.prev_partials = s.partials[parity ^ 1];
-      a.n_prev = m.n_tiles; a.n_prev_vecs = last_vecs;
+      a.n_prev = m.n_tiles; a.n_prev_vecs = last_vecs;                 // this rank's own tiles: the previous launch wrote that many per step
       a.sums = s.sums;
       a.counter = s.counter;
-      kRowsMulti64Kernels[multi64_row(m.K, m.nt_stores != 0, steps == m.K)]<<<dim3(m.n_tiles + 1), dim3(m.block), static_cast<size_t>(m.lds_bytes), s.stream>>>(a);   // + the fold block
+      const int row = multi64_row(m.K, m.nt_stores != 0, steps == m.K);
+      const dim3 blocks(m.n_tiles + 1), lanes(m.block);                     // + the fold block
+      if (m.edge) {
+        RowsMulti64EdgeArgs e{};
+        static_cast<RowsMulti64Args&>(e) = a;
+        e.last_y0 = m.last_y0;
+        kRowsMulti64EdgeKernels[row]<<<blocks, lanes, static_cast<size_t>(m.lds_bytes), s.stream>>>(e);
+      } else {
+        kRowsMulti64Kernels[row]<<<blocks, lanes, static_cast<size_t>(m.lds_bytes), s.stream>>>(a);
+      }
       HIP_TRY(hipGetLastError());
       if (enqueue_push_ghost(c, r, c->cur ^ 1)) return 1;
       HIP_TRY(hipEventRecord(k.pushed[now], s.stream));
@@ -307,7 +321,7 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
   for (int r = 0; r < nranks; ++r) {
     Rank64& k = c->ranks[r];
     if (lbm_internal::plan64_rows(knobs, p, nranks, r, flags, &k.plan)) return fail();
-    lbm_internal::plan64_rows_multi(knobs, p, k.plan, &k.multi);
+    lbm_internal::plan64_rows_multi_any(knobs, p, k.plan, &k.multi);
     const bool multi = k.multi.multi_kernel != 0;
     k.slab.ncells = static_cast<size_t>(p->nx) * k.plan.ny_local;
     k.slab.first = static_cast<size_t>(p->nx) * (multi ? k.multi.ghost : 1);      // the first owned row: storage row 1, or K
@@ -350,7 +364,7 @@ int lbm_rows64_create(lbm_rows64** out, const lbm64_params* p, int free_cells, c
     Rank64& k = c->ranks[r];
     const lbm_internal::PlanRows64& plan = k.plan;
     HIP_TRY_OR(hipSetDevice(k.slab.device), return fail());
-    const lbm_internal::PlanRowsMulti64& multi = k.multi;
+    const lbm_internal::PlanRowsMultiAny64& multi = k.multi;
     if (slab64_create(k.slab, static_cast<size_t>(multi.multi_kernel ? multi.grid_doubles : plan.grid_doubles), static_cast<size_t>(plan.mask_words),
                       static_cast<size_t>(std::max(plan.partials_cap, multi.multi_kernel ? multi.partials_cap : 0)), obstacles + first_cell(c, k), p->density, p->max_iters))
       return fail();
@@ -536,7 +550,7 @@ int lbm_rows64_describe(const lbm_rows64* c, char* kernel_name, size_t len, int*
       if (k.multi.n_tiles > most->multi.n_tiles) most = &k;
       bytes += static_cast<long long>(2 * 9 * sizeof(double)) * c->p.nx * (k.plan.ny_local + 2 * k.multi.ghost);
     }
-    if (kernel_name && len > 0) lbm_internal::plan64_rows_multi_kernel_name(most->multi, kernel_name, len);
+    if (kernel_name && len > 0) lbm_internal::plan64_rows_multi_any_kernel_name(most->multi, kernel_name, len);
     if (nranks) *nranks = c->nranks;
     if (blocks) *blocks = most->multi.n_tiles;
     if (cells_per_block) *cells_per_block = static_cast<long long>(kMulti64TX) * kMulti64TY;

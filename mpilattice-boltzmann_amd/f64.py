@@ -16,7 +16,8 @@ with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_mult
 `f64.Rows64(p, obst, nranks, devices=None)` is the same grid as `nranks` row blocks over one or several GPUs of this process
 (include/lbm_d2q9_f64_rows.h): Grid64's methods, Grid64's populations bit for bit for every rank count.  With
 `flags=f64.FLAG_ROWS_MULTI_STEPS`, ranks that 32 x 16 tiles cover advance several steps per launch and exchange
-(lbm_rows_multi_kernel_f64): the same populations.
+(lbm_rows_multi_kernel_f64): the same populations.  `flags=f64.FLAG_ROWS_MULTI_ANY_SIZE` means the same and also takes the runs
+of any even width >= 32 whose every rank owns >= 16 rows, uneven ranks among them, by the kernel's edge-tile form.
 
 `g.digest()` of either class gives one 64-bit digest per row of the current state and their sum (include/lbm_d2q9_f64_digest.h), taken
 on the device; `f64.digest_host(cells, nx)` the same of an array, `f64.differing_rows(a, b)` the rows in which two objects differ.
@@ -39,6 +40,7 @@ FLAG_TILE_STEPS = 512        # LBM64_FLAG_TILE_STEPS: small grids advance severa
 FLAG_MULTI_STEPS = 1024      # LBM64_FLAG_MULTI_STEPS: large grids that 32 x 16 tiles cover do (lbm_multi_kernel_f64); the same populations
 FLAG_MULTI_ANY_SIZE = 4096   # LBM64_FLAG_MULTI_ANY_SIZE: FLAG_MULTI_STEPS, and large grids of any even width >= 32 and ny >= 16 by the kernel's edge-tile form ("lbm_multi_kernel_f64<K,edge>"); the same populations
 FLAG_ROWS_MULTI_STEPS = 2048  # LBM_ROWS64_FLAG_MULTI_STEPS: Rows64 only; ranks that 32 x 16 tiles cover advance K steps per launch and exchange (lbm_rows_multi_kernel_f64); the same populations
+FLAG_ROWS_MULTI_ANY_SIZE = 8192  # LBM_ROWS64_FLAG_MULTI_ANY_SIZE: Rows64 only; FLAG_ROWS_MULTI_STEPS, and runs of any even width >= 32 whose every rank owns >= 16 rows by the kernel's edge-tile form ("lbm_rows_multi_kernel_f64<K,edge>"); the same populations
 
 
 class CParams64(C.Structure):
@@ -241,7 +243,9 @@ def load_rows_library() -> C.CDLL:
 class Rows64:
     """A whole periodic grid in double precision, its rows dealt to `nranks` ranks on one or several GPUs — one `lbm_rows64`.
     `devices`: one HIP ordinal per rank (ranks may share a device), or None: rank r on device r % (device count).  Grid64's methods;
-    the populations are Grid64's bits for every rank count."""
+    the populations are Grid64's bits for every rank count.  `flags`: 0, a store form, FLAG_ROWS_MULTI_STEPS (several steps per launch
+    and exchange where 32 x 16 tiles cover every rank), FLAG_ROWS_MULTI_ANY_SIZE (the same, and ranks of any size from 16 rows on grids of
+    any even width from 32: the kernel's edge-tile form), in any sum."""
 
     def __init__(self, params, obstacles: np.ndarray, nranks: int, devices=None, flags: int = 0):
         self._lib = load_rows_library()
@@ -402,5 +406,5 @@ def differing_rows(a, b) -> list[int]:
     return [int(y) for y in np.nonzero(a.digest()[0] != b.digest()[0])[0]]
 
 
-__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_MULTI_ANY_SIZE", "FLAG_ROWS_MULTI_STEPS", "CParams64", "Grid64", "Rows64",
+__all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_MULTI_ANY_SIZE", "FLAG_ROWS_MULTI_STEPS", "FLAG_ROWS_MULTI_ANY_SIZE", "CParams64", "Grid64", "Rows64",
            "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]

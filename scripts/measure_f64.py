@@ -48,10 +48,20 @@ which flag 4096 must equal in time.  One size per process:
 
 --ranks N[,N] [--devices LIST] [--steps S]: row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count beside
 the one-context one-step and LBM64_FLAG_MULTI_STEPS runs of the same grid (--work NXxNY, default 8192x8192), alternating: device and
-wall time per step.  Each rank count runs twice, without and with LBM_ROWS64_FLAG_MULTI_STEPS (K steps per launch and exchange; the
-minimum size is lowered to 0 so that every size whose ranks the tiles cover is measured), and a line under the table holds the flagged
-run against the unflagged one: the median gain beside the two max - min spreads together.  With all ranks on one device this measures
-the loop's overhead, not a speed-up; --out appends.
+wall time per step.  Each rank count runs three times: without a flag, with LBM_ROWS64_FLAG_MULTI_STEPS (K steps per launch and
+exchange) and with LBM_ROWS64_FLAG_MULTI_ANY_SIZE (the same, and the kernel's edge-tile form on ranks the tiles do not cover, uneven
+ranks among them); the minimum size is lowered to 0 so that every size is measured, and a flagged run that takes the one-step kernel
+all the same is left out.  With --baseline-lib (the parent commit's build) each rank count also runs in that build, without a flag
+and, where it takes the kernel there, with LBM_ROWS64_FLAG_MULTI_STEPS.  Lines under the table hold each flagged run against the
+unflagged ones: the median gain beside the two max - min spreads together.  With all ranks on one device this measures the loop's
+overhead, not a speed-up; --out appends.
+
+    F=profiles/r22/f64_rows_any.txt; rm -f $F; B=mpilattice-boltzmann_amd/lib/variants/liblbm_d2q9_parent.so
+    timeout -k 10 500 python scripts/measure_f64.py --ranks 1,2,8 --baseline-lib $B --work 8190x8190 --out $F &&
+    timeout -k 10 300 python scripts/measure_f64.py --ranks 1,2,8 --baseline-lib $B --work 4098x4100 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --baseline-lib $B --work 2050x2046 --steps 400 --out $F &&
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --baseline-lib $B --work 1022x1026 --steps 2000 --out $F &&
+    timeout -k 10 500 python scripts/measure_f64.py --ranks 1,2,8 --baseline-lib $B --work 8192x8192 --out $F
 
     F=profiles/r18/f64_rows_multi.txt; rm -f $F
     timeout -k 10 400 python scripts/measure_f64.py --ranks 1,2,8 --work 8192x8192 --out $F &&
@@ -338,11 +348,57 @@ def multi_bits(ks, lines):
             raise SystemExit("8192x7296: the populations differ")
 
 
-def measure_rows(name, ranks, devices, steps, reps, lines):
+class BaselineRows64:
+    """lbm_rows64_* of another build of the library (dlopen'ed privately, as BaselineGrid64): create, run, last_run_ms, describe, close."""
+
+    def __init__(self, path, p, obst, nranks, devices=None, flags=0):
+        self.lib = C.CDLL(os.path.abspath(path), mode=os.RTLD_LOCAL | os.RTLD_DEEPBIND)
+        for name, (res, args) in f64._ROWS_SIGNATURES.items():
+            fn = getattr(self.lib, name)
+            fn.restype, fn.argtypes = res, args
+        self.lib.lbm_last_error.restype = C.c_char_p
+        self.obst = np.ascontiguousarray(obst, dtype=np.int32)
+        self.cp = f64._cparams(p)
+        self.run_ = C.c_void_p()
+        dev = None if devices is None else (C.c_int * len(devices))(*devices)
+        self._check(self.lib.lbm_rows64_create(C.byref(self.run_), C.byref(self.cp), int(self.obst.size - np.count_nonzero(self.obst)),
+                                               self.obst.ctypes.data_as(C.POINTER(C.c_int)), nranks, dev, flags))
+
+    def _check(self, rc):
+        if rc:
+            raise SystemExit(f"baseline library: {self.lib.lbm_last_error().decode()}")
+
+    def run(self, n):
+        av = np.zeros(n, np.float64)
+        self._check(self.lib.lbm_rows64_run(self.run_, n, av.ctypes.data_as(C.POINTER(C.c_double))))
+        return av
+
+    def last_run_ms(self):
+        ms, n = C.c_double(0.0), C.c_int(0)
+        self._check(self.lib.lbm_rows64_last_run_ms(self.run_, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def describe(self):
+        name = C.create_string_buffer(256)
+        blocks = C.c_longlong(0)
+        self._check(self.lib.lbm_rows64_describe(self.run_, name, 256, None, C.byref(blocks), None, None))
+        return {"kernel": name.value.decode(), "blocks": blocks.value}
+
+    def close(self):
+        self.lib.lbm_rows64_destroy(self.run_)
+
+
+PARENT = " (parent build)"
+
+
+def measure_rows(name, ranks, devices, steps, reps, lines, baseline_lib=None):
     """Row-partitioned runs (f64.Rows64, include/lbm_d2q9_f64_rows.h) with each rank count of `ranks` beside the one-context one-step
     kernel and the one-context LBM64_FLAG_MULTI_STEPS run of the same grid: per step, the device time (events: for a partitioned run
     the largest span over the ranks) and the host's wall time around run(), which ends in a synchronise.  The contexts alternate run by
-    run.  With all ranks on one device their kernels serialise: the difference to the one-context figure is the loop's overhead."""
+    run.  With all ranks on one device their kernels serialise: the difference to the one-context figure is the loop's overhead.
+    Each rank count runs without a flag, with LBM_ROWS64_FLAG_MULTI_STEPS and with LBM_ROWS64_FLAG_MULTI_ANY_SIZE (a flagged run that
+    takes the one-step kernel all the same is left out); with `baseline_lib` also in that build, without a flag and, where it takes the
+    kernel there, with LBM_ROWS64_FLAG_MULTI_STEPS."""
     import time
     p, obst = deck(name)
     n0 = len(lines)
@@ -357,11 +413,16 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
         dev = None if devices is None else [devices[r % len(devices)] for r in range(n)]
         key = f"{n} rank{'s' if n > 1 else ''}"
         runs[key] = f64.Rows64(p, obst, n, devices=dev)
-        flagged = f64.Rows64(p, obst, n, devices=dev, flags=f64.FLAG_ROWS_MULTI_STEPS)
-        if flagged.describe()["kernel"].startswith("lbm_rows_multi_kernel_f64<"):
-            runs[key + ", multi-step"] = flagged
-        else:
-            flagged.close()                                # uneven ranks, or tiles that do not cover them: the flag changes nothing
+        made = [(key + ", multi-step", f64.Rows64(p, obst, n, devices=dev, flags=f64.FLAG_ROWS_MULTI_STEPS)),
+                (key + ", any-size", f64.Rows64(p, obst, n, devices=dev, flags=f64.FLAG_ROWS_MULTI_ANY_SIZE))]
+        if baseline_lib:
+            runs[key + PARENT] = BaselineRows64(baseline_lib, p, obst, n, devices=dev)
+            made.append((key + ", multi-step" + PARENT, BaselineRows64(baseline_lib, p, obst, n, devices=dev, flags=f64.FLAG_ROWS_MULTI_STEPS)))
+        for k, flagged in made:
+            if flagged.describe()["kernel"].startswith("lbm_rows_multi_kernel_f64<"):
+                runs[k] = flagged
+            else:
+                flagged.close()                            # the flag changes nothing on this run
     shapes = {k: q.describe() for k, q in runs.items()}
     first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every context from the rest state
     base = first["one context, one step"]
@@ -374,7 +435,7 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
             t0 = time.perf_counter()
             q.run(steps)
             wall_us[k].append(1e6 * (time.perf_counter() - t0) / steps)
-            ms = q.last_run_ms()[0] if isinstance(q, f64.Rows64) else q.last_run_kernel_ms()[0]
+            ms = q.last_run_ms()[0] if isinstance(q, (f64.Rows64, BaselineRows64)) else q.last_run_kernel_ms()[0]
             dev_us[k].append(1e3 * ms / steps)
     for q in runs.values():
         q.close()
@@ -382,16 +443,28 @@ def measure_rows(name, ranks, devices, steps, reps, lines):
     lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; ranks on {where}; us per step")
     for k in runs:
         d, w = dev_us[k], wall_us[k]
-        lines.append(f"  {k:24s} {shapes[k]['kernel']:32s} {shapes[k]['blocks']:6d} blocks   device median {statistics.median(d):9.3f}  min {min(d):9.3f}  max {max(d):9.3f}"
+        lines.append(f"  {k:38s} {shapes[k]['kernel']:38s} {shapes[k]['blocks']:6d} blocks   device median {statistics.median(d):9.3f}  min {min(d):9.3f}  max {max(d):9.3f}"
                      f"   wall median {statistics.median(w):9.3f}  min {min(w):9.3f}  max {max(w):9.3f}")
-    for k in [k for k in runs if k.endswith(", multi-step") and k != "one context, multi-step"]:
-        off = k[:-len(", multi-step")]
+    def against(k, off, same=False):
         med = {q: statistics.median(dev_us[q]) for q in (off, k)}
         gain = med[off] - med[k]
         spreads = (max(dev_us[off]) - min(dev_us[off])) + (max(dev_us[k]) - min(dev_us[k]))
-        cells = p.nx * (p.ny // int(off.split()[0]))
-        lines.append(f"  {k} against {off} ({cells} cells a rank): {med[off] / med[k]:.3f} x; median gain {gain:.3f} us against the two max - min spreads together "
-                     f"{spreads:.3f} us -> {'a win' if gain > spreads else 'no win'}")
+        cells = p.nx * min(lbm.decompose(p.ny, int(off.split()[0]))[0])
+        verdict = ("the same time" if abs(gain) <= spreads else "DIFFERENT") if same else ("a win" if gain > spreads else "no win")
+        lines.append(f"  {k} against {off} ({cells} cells in the smallest rank): {med[off] / med[k]:.3f} x; median gain {gain:.3f} us against the two max - min "
+                     f"spreads together {spreads:.3f} us -> {verdict}")
+
+    for n in ranks:
+        key = f"{n} rank{'s' if n > 1 else ''}"
+        for flagged in (key + ", multi-step", key + ", any-size"):
+            if flagged in runs:
+                against(flagged, key)
+                if key + PARENT in runs:
+                    against(flagged, key + PARENT)           # the parent's run of the same shape without a flag
+        if key + ", multi-step" + PARENT in runs:              # the same kernel in both builds
+            for flagged in (key + ", multi-step", key + ", any-size"):
+                if flagged in runs:
+                    against(flagged, key + ", multi-step" + PARENT, same=True)
     print("\n".join(lines[n0:]), flush=True)
 
 
@@ -413,10 +486,10 @@ def main():
     if a.ranks:
         lines = [] if a.out and os.path.exists(a.out) else [
             "# scripts/measure_f64.py --ranks: row-partitioned double-precision runs (lbm_rows_kernel_f64 + lbm64_push_rows_kernel per rank-step; \"multi-step\": "
-            "LBM_ROWS64_FLAG_MULTI_STEPS, lbm_rows_multi_kernel_f64 + lbm64_push_ghost_rows_kernel per rank-launch) beside the one-context runs",
+            "LBM_ROWS64_FLAG_MULTI_STEPS, \"any-size\": LBM_ROWS64_FLAG_MULTI_ANY_SIZE, lbm_rows_multi_kernel_f64 + lbm64_push_ghost_rows_kernel per rank-launch) beside the one-context runs",
             "# device: events around a run's step launches, over its steps (partitioned: the largest span over the ranks); wall: the host's clock around run()"]
         measure_rows(a.work or "8192x8192", [int(v) for v in a.ranks.split(",")], [int(v) for v in a.devices.split(",")] if a.devices else None,
-                     a.steps or (12 if a.quick else 200), 3 if a.quick else 5, lines)
+                     a.steps or (12 if a.quick else 200), 3 if a.quick else 5, lines, baseline_lib=a.baseline_lib)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "a") as fh:
