@@ -29,7 +29,8 @@
  * the boundary as AoS, 9 doubles per cell, row-major, x fastest; obstacles as the reference's int map.  lbm_read_obstacles and
  * lbm_last_error of lbm_d2q9.h serve this mode as they are.
  *
- * OUT OF SCOPE of this mode (use lbm_d2q9.h; for row blocks in double precision inside one process, lbm_d2q9_f64_rows.h): row or tile
+ * OUT OF SCOPE of this mode (use lbm_d2q9.h; for row blocks in double precision inside one process, lbm_d2q9_f64_rows.h; for column
+ * blocks, lbm_d2q9_f64_cols.h): row or tile
  * partitions and every halo transport (peer-to-peer, RCCL, split-phase calls)
  * — a context is a whole periodic grid on one GPU (several steps per launch are opt-in: LBM64_FLAG_TILE_STEPS for small grids,
  * LBM64_FLAG_MULTI_STEPS for large ones that 32 x 16 tiles cover, LBM64_FLAG_MULTI_ANY_SIZE for large ones of any even width; without

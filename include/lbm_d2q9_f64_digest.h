@@ -37,6 +37,9 @@
  * with a message and before the first HIP call: a null context or run; both output pointers null; y_begin < 0, y_end > ny or
  * y_begin > y_end; for the host form a null state with rows > 0, nx < 1, rows < 0 or y0 < 0.  y_begin == y_end succeeds with digest 0
  * and launches nothing.
+ *
+ * NOT HERE: the digest of a column-partitioned run, whose ranks each hold a PART of every row.  It is lbm_cols64_digest of
+ * lbm_d2q9_f64_cols.h: the ranks' parts of a row, added wrap-around, are this header's row digest by the definition above.
  */
 #ifndef LBM_D2Q9_F64_DIGEST_H
 #define LBM_D2Q9_F64_DIGEST_H

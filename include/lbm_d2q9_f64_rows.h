@@ -59,7 +59,8 @@
  * it does not own), then the nranks - 1 host additions in rank order.  On any other run (odd nx, nx < 32, a rank of fewer than 16 rows,
  * a smallest rank below the minimum) the flag changes nothing, as above.
  *
- * OUT OF SCOPE: tiles (a 2-D decomposition); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; odd nx
+ * OUT OF SCOPE: tiles of a 2-D decomposition with more than one block in each direction (column blocks, for grids much wider than
+ * tall, are lbm_d2q9_f64_cols.h, an object of its own); ranks in separate processes, over IPC or RCCL; more than one launch per exchange; odd nx
  * under either flag (such runs take the one-step kernel); overlap of a rank's interior rows or tiles with the exchange.
  * The whole grid's LBM64_FLAG_TILE_STEPS and LBM64_FLAG_MULTI_STEPS are refused, and so is its LBM64_FLAG_MULTI_ANY_SIZE: the row
  * partition's own bit for ranks that 32 x 16 tiles do not cover exactly is LBM_ROWS64_FLAG_MULTI_ANY_SIZE.

@@ -41,13 +41,14 @@ def build(force: bool = False, verbose: bool = False) -> dict[str, str]:
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     os.makedirs(os.path.dirname(CLI), exist_ok=True)
     headers = [os.path.join(ROOT, "include", "lbm_d2q9.h"), os.path.join(ROOT, "include", "lbm_d2q9_p2p.h"), os.path.join(ROOT, "include", "lbm_d2q9_f64.h"),
-               os.path.join(ROOT, "include", "lbm_d2q9_f64_rows.h"), os.path.join(ROOT, "include", "lbm_d2q9_f64_digest.h"), os.path.join(CSRC, "lbm_internal.h"), os.path.join(CSRC, "lbm_knobs.h"), os.path.join(CSRC, "lbm_geometry.h"),
+               os.path.join(ROOT, "include", "lbm_d2q9_f64_rows.h"), os.path.join(ROOT, "include", "lbm_d2q9_f64_digest.h"), os.path.join(ROOT, "include", "lbm_d2q9_f64_cols.h"), os.path.join(CSRC, "lbm_internal.h"), os.path.join(CSRC, "lbm_knobs.h"), os.path.join(CSRC, "lbm_geometry.h"),
                os.path.join(CSRC, "lbm_p2p_impl.h"), os.path.join(CSRC, "lbm_hip_try.h"), os.path.join(CSRC, "lbm_f64_slab.h"), os.path.abspath(__file__)]
-    headers += sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")))       # device code, included by lbm_kernels.hip, lbm_f64.hip and lbm_rows64.hip
+    headers += sorted(glob.glob(os.path.join(CSRC, "kernels", "*.h")))       # device code, included by lbm_kernels.hip, lbm_f64.hip, lbm_rows64.hip and lbm_cols64.hip
     # lbm_f64.hip: the double-precision mode (include/lbm_d2q9_f64.h), a translation unit of its own
     # lbm_rows64.hip: its row-partitioned runs (include/lbm_d2q9_f64_rows.h), one more, so that the other two's code objects stay as they are
+    # lbm_cols64.hip: its column-partitioned runs (include/lbm_d2q9_f64_cols.h), again one more, for the same reason
     # lbm_plan.cpp: which kernel, geometry and sizes a context gets; host-only like lbm_host.cpp
-    lib_src = [os.path.join(CSRC, "lbm_kernels.hip"), os.path.join(CSRC, "lbm_f64.hip"), os.path.join(CSRC, "lbm_rows64.hip"),
+    lib_src = [os.path.join(CSRC, "lbm_kernels.hip"), os.path.join(CSRC, "lbm_f64.hip"), os.path.join(CSRC, "lbm_rows64.hip"), os.path.join(CSRC, "lbm_cols64.hip"),
                os.path.join(CSRC, "lbm_host.cpp"), os.path.join(CSRC, "lbm_plan.cpp")]
     if force or _stale(LIB, lib_src + headers):
         cmd = [hipcc, "--offload-arch=gfx950", *COMMON, "-fPIC", "-shared", *lib_src, "-o", LIB]

@@ -27,6 +27,10 @@
  * 2048 (LBM_ROWS64_FLAG_MULTI_STEPS: several steps per launch and exchange where every rank is eligible, the same files) and
  * 8192 (LBM_ROWS64_FLAG_MULTI_ANY_SIZE: 2048, and runs of any even width from 32 whose every rank owns 16 rows or more, with the
  * kernel's edge-tile form).  LBM64_RANKS without LBM_PRECISION=double is refused.
+ * LBM_PRECISION=double LBM64_COLS=N (1 <= N <= 64) runs the same deck as N column blocks (include/lbm_d2q9_f64_cols.h), K steps per launch
+ * and exchange: LBM_DEVICES, LBM_DESCRIBE and LBM_DIGEST as for LBM64_RANKS; of LBM_FLAGS it takes 0, 1 and 2.  The same five lines and
+ * two files; final_state.dat is the same bytes.  Refused: LBM64_COLS without LBM_PRECISION=double, together with LBM64_RANKS, with
+ * LBM_GPUS > 1, N outside 1..64 — and by the library the decks a column partition does not take (odd nx, a block narrower than 32, ny < 16).
  * LBM_PRECISION=double LBM_DIGEST=1, with or without LBM64_RANKS, adds one line on stderr after the run, "state digest: <16 hex digits>":
  * the digest of the final populations (include/lbm_d2q9_f64_digest.h), the same for every way of advancing the same deck.  LBM_DIGEST=1
  * without LBM_PRECISION=double is refused.
@@ -51,6 +55,7 @@
 #include "lbm_d2q9.h"
 #include "lbm_d2q9_f64.h"
 #include "lbm_d2q9_f64_rows.h"
+#include "lbm_d2q9_f64_cols.h"
 #include "lbm_d2q9_f64_digest.h"
 #include "lbm_d2q9_p2p.h"
 
@@ -107,15 +112,36 @@ static void* rank_main(void* arg)
   return NULL;
 }
 
+/* The devices of LBM_DEVICES (a comma list) for `nranks` ranks, or NULL where it is unset: the library's default then. */
+static int* devices_from_env(int nranks)
+{
+  const char* list = getenv("LBM_DEVICES");
+  int* device = NULL;
+  int r;
+  if (!list || !*list) return NULL;
+  device = (int*)xmalloc(sizeof(int) * (size_t)nranks);
+  for (r = 0; r < nranks; ++r) {
+    device[r] = r;                       /* a list shorter than the rank count: the ranks behind it on their own ordinal */
+    if (list && *list) {
+      device[r] = atoi(list);
+      list = strchr(list, ',');
+      if (list) ++list;
+    }
+  }
+  return device;
+}
+
 /* LBM_PRECISION=double: main() below with lbm64_* in place of lbm_* and doubles in place of floats; with LBM64_RANKS=N, with
- * lbm_rows64_* (N row blocks) in place of lbm64_*. */
+ * lbm_rows64_* (N row blocks) in place of lbm64_*; with LBM64_COLS=N, with lbm_cols64_* (N column blocks). */
 static int main_double(char* argv[])
 {
   lbm64_params params;
   lbm64_ctx* ctx = NULL;
   lbm_rows64* rows = NULL;
   const char* ranks_text = getenv("LBM64_RANKS");
-  const int nranks = (ranks_text && *ranks_text) ? atoi(ranks_text) : 0;      /* 0: one context, lbm64_* */
+  const char* cols_text = getenv("LBM64_COLS");
+  const int ncols = (cols_text && *cols_text) ? atoi(cols_text) : 0;          /* > 0: column blocks, lbm_cols64_* */
+  const int nranks = ncols > 0 ? ncols : (ranks_text && *ranks_text) ? atoi(ranks_text) : 0;      /* 0: one context, lbm64_* */
   int* obstacles;
   int free_cells = 0;
   double* av_vels;
@@ -124,6 +150,11 @@ static int main_double(char* argv[])
   struct rusage ru;
   size_t nx;
 
+  if (cols_text && *cols_text) {
+    if (ranks_text && *ranks_text) die("LBM64_COLS: column blocks and row blocks (LBM64_RANKS) exclude each other: set one of them", __LINE__, __FILE__);
+    if (env_int("LBM_GPUS", 1) > 1) die("LBM64_COLS: the column blocks of one process take their devices from LBM_DEVICES (unset LBM_GPUS)", __LINE__, __FILE__);
+    if (ncols < 1 || ncols > LBM_COLS64_MAX_RANKS) die("LBM64_COLS: expected 1 to 64 column blocks", __LINE__, __FILE__);
+  }
   if (env_int("LBM_GPUS", 1) > 1) die("LBM_PRECISION=double: double precision runs on one GPU (unset LBM_GPUS)", __LINE__, __FILE__);
   if (ranks_text && *ranks_text && (nranks < 1 || nranks > LBM_ROWS64_MAX_RANKS)) die("LBM64_RANKS: expected 1 to 64 ranks (MPI_PROCS, d2q9-bgk.c:67)", __LINE__, __FILE__);
   if (lbm64_read_params(argv[1], &params)) die(lbm_last_error(), __LINE__, __FILE__);
@@ -134,7 +165,33 @@ static int main_double(char* argv[])
   av_vels = (double*)xmalloc(sizeof(double) * ((size_t)params.max_iters + 1));
   obs = (double*)xmalloc(sizeof(double) * nx * (size_t)params.ny * 4);
 
-  if (nranks > 0) {
+  if (ncols > 0) {
+    /* ---- N column blocks in one lbm_cols64, one host thread ------------------------------------------------------------------- */
+    lbm_cols64* cols = NULL;
+    const int flags = env_int("LBM_FLAGS", 0);
+    int* device = devices_from_env(ncols);
+    if (flags < 0 || flags > 2) die("LBM_FLAGS: with LBM64_COLS expected 0, 1 (LBM_FLAG_NT_STORES) or 2 (LBM_FLAG_NO_NT_STORES)", __LINE__, __FILE__);
+    if (lbm_cols64_create(&cols, &params, free_cells, obstacles, ncols, device, (unsigned)flags)) die(lbm_last_error(), __LINE__, __FILE__);
+    free(device);
+    tic = wall_seconds();                                                  /* :278-279 */
+    if (lbm_cols64_run(cols, params.max_iters, av_vels)) die(lbm_last_error(), __LINE__, __FILE__);
+    toc = wall_seconds();                                                  /* :397-398 */
+    if (lbm_cols64_get_observables(cols, obs)) die(lbm_last_error(), __LINE__, __FILE__);
+    if (env_int("LBM_DESCRIBE", 0)) {
+      char kernel[128];
+      double ms = 0.0;
+      int launches = 0;
+      if (lbm_cols64_describe(cols, kernel, sizeof kernel, NULL, NULL, NULL, NULL)) die(lbm_last_error(), __LINE__, __FILE__);
+      if (params.max_iters > 0 && lbm_cols64_last_run_ms(cols, &ms, &launches)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "kernel: %s on %d column ranks, %d launches\n", kernel, ncols, launches);
+    }
+    if (env_int("LBM_DIGEST", 0)) {
+      unsigned long long digest = 0;
+      if (lbm_cols64_digest(cols, 0, params.ny, NULL, &digest)) die(lbm_last_error(), __LINE__, __FILE__);
+      fprintf(stderr, "state digest: %016llx\n", digest);
+    }
+    lbm_cols64_destroy(cols);
+  } else if (nranks > 0) {
     /* ---- N row blocks of the reference's decomposition in one lbm_rows64, one host thread ------------------------------------ */
     const int flags = env_int("LBM_FLAGS", 0);
     const char* list = getenv("LBM_DEVICES");
@@ -206,7 +263,8 @@ static int main_double(char* argv[])
   printf("Elapsed user CPU time:\t\t%.6lf (s)\n", usrtim);
   printf("Elapsed system CPU time:\t%.6lf (s)\n", systim);
   mlups = (double)params.nx * params.ny * params.max_iters / (toc - tic) / 1e6;
-  if (nranks > 0) printf("MLUPS:\t\t\t\t%.1f (%d ranks, double precision)\n", mlups, nranks);
+  if (ncols > 0) printf("MLUPS:\t\t\t\t%.1f (%d column ranks, double precision)\n", mlups, ncols);
+  else if (nranks > 0) printf("MLUPS:\t\t\t\t%.1f (%d ranks, double precision)\n", mlups, nranks);
   else printf("MLUPS:\t\t\t\t%.1f (1 GPU, double precision)\n", mlups);
   printf("HBM roofline (144 B/cell-step @ 8.0 TB/s = 55556 MLUPS per GPU):\t%.1f %%\n", 100.0 * mlups / (8.0e12 / 144.0 / 1e6));
 
@@ -238,6 +296,7 @@ int main(int argc, char* argv[])
     if (precision && strcmp(precision, "double") == 0) return main_double(argv);
     if (precision && *precision && strcmp(precision, "float") != 0) die("LBM_PRECISION: expected float or double", __LINE__, __FILE__);
     if (getenv("LBM64_RANKS") && *getenv("LBM64_RANKS")) die("LBM64_RANKS: row blocks in double precision need LBM_PRECISION=double", __LINE__, __FILE__);
+    if (getenv("LBM64_COLS") && *getenv("LBM64_COLS")) die("LBM64_COLS: column blocks in double precision need LBM_PRECISION=double", __LINE__, __FILE__);
     if (env_int("LBM_DIGEST", 0)) die("LBM_DIGEST: the state digest is the double-precision mode's, it needs LBM_PRECISION=double", __LINE__, __FILE__);
   }
 

@@ -11,9 +11,14 @@
 
 #include "lbm_internal.h"
 
+// (A failed call stays the thread's last HIP error until it is read.  It is read here: otherwise the next hipGetLastError() after a
+// launch — of another object of this thread, perhaps much later — would report this failure as its own.)
 inline bool hip_failed(hipError_t e, const char* call)
 {
-  if (e != hipSuccess) lbm_internal::set_error(std::string(call) + ": " + hipGetErrorString(e));
+  if (e != hipSuccess) {
+    lbm_internal::set_error(std::string(call) + ": " + hipGetErrorString(e));
+    (void)hipGetLastError();
+  }
   return e != hipSuccess;
 }
 #define HIP_TRY_OR(expr, on_fail) do { if (hip_failed((expr), #expr)) { on_fail; } } while (0)

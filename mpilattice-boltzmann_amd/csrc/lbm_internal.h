@@ -1,4 +1,4 @@
-// lbm_internal.h — shared between the host-only (lbm_host.cpp, lbm_plan.cpp) and device (lbm_kernels.hip, lbm_f64.hip, lbm_rows64.hip)
+// lbm_internal.h — shared between the host-only (lbm_host.cpp, lbm_plan.cpp) and device (lbm_kernels.hip, lbm_f64.hip, lbm_rows64.hip, lbm_cols64.hip)
 // units of liblbm_d2q9.so.  Not part of the ABI.
 #pragma once
 #include <cstddef>
@@ -212,6 +212,36 @@ void plan64_rows_multi_any_kernel_name(const PlanRowsMultiAny64& plan, char* ker
 // Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
 int plan64_rows_multi_any_next_steps(const PlanRowsMultiAny64& plan, int left);
 
+// One rank of a column-partitioned double-precision run (include/lbm_d2q9_f64_cols.h; lbm_cols64.hip allocates and launches by this
+// plan alone): the columns lbm_decompose_columns gives the rank, its storage of ny rows of pitch nxl + 2 * ghost doubles, and its launch
+// of lbm_cols_multi_kernel_f64 (kernels/cols64.h).  Ranks of one run agree on K, ghost, block and lds_bytes and may differ in the rest.
+// Plain data in this order — tests/test_plan64_cols.py mirrors it field for field and refuses a library whose lbm_plan64_cols_sizeof()
+// differs.  Beside the other plans, whose layouts and values do not change.
+struct PlanCols64 {
+  unsigned flags;                    // as lbm_cols64_create took them
+  int nranks, rank;
+  int x0, nxl, pitch;                // first owned column of the grid, owned columns (lbm_decompose_columns), doubles of a storage row: nxl + 2 * ghost
+  int K, ghost;                      // steps of a full launch (LBM_TUNE_MULTI64_K); ghost columns on each side: 2 * ceil(K / 2)
+  int n_tiles, tiles_x;              // ceil(nxl / TX) * ceil(ny / TY) (= work blocks of a launch); ceil(nxl / TX)
+  int edge;                          // the tiles do not cover the block exactly: the kernel's edge-tile form
+  int nt_stores;                     // plan64_whole's rule on the RANK's two grids of ny * pitch cells, and the flags
+  int block, lds_bytes;              // lanes and dynamic LDS bytes of a block
+  int mask_words;                    // words of the window bitfield over the ny * pitch storage cells
+  int partials_cap;                  // doubles of each partials buffer: K * n_tiles + 1
+  long long ps, grid_doubles;        // plane stride of ny * pitch cells; one grid's allocation, in doubles
+};
+static_assert(sizeof(PlanCols64) == 16 * sizeof(int) + 2 * sizeof(long long), "no padding: the order above is the layout");
+constexpr int kMaxCols64Ranks = 64;
+// The flags lbm_cols64_create takes: a store form.
+constexpr unsigned kFlagsCols64 = LBM_FLAG_NT_STORES | LBM_FLAG_NO_NT_STORES;
+// Fills *out for rank `rank` of `nranks`; checks every argument itself.  0, or 1 and the message in lbm_last_error(): nranks outside
+// 1..64, odd nx, a rank of fewer than TX columns, ny < TY, any flag outside kFlagsCols64, a rank's storage too large for 32-bit cell
+// indices.
+int plan64_cols(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanCols64* out);
+void plan64_cols_kernel_name(const PlanCols64& plan, char* kernel_name, size_t len);
+// Steps of the next launch with `left` steps remaining: plan64_multi_next_steps' rule.
+int plan64_cols_next_steps(const PlanCols64& plan, int left);
+
 // ---- lbm_plan.cpp: what a run launches ------------------------------------------------------------------------------------------
 // The launches between two halo exchanges of a partitioned run (a group): next_multi_k's launches for as long as their steps add
 // up to at most the ghost rows, group_max at most.  Launch i of a group advances, besides the owned rows, ext(i) = the steps of the
@@ -315,3 +345,9 @@ extern "C" int lbm_plan64_rows_multi_any_sizeof(void);
 extern "C" int lbm_plan64_rows_multi_any(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanRowsMultiAny64* out);
 extern "C" int lbm_plan64_rows_multi_any_kernel_name(const lbm_internal::PlanRowsMultiAny64* plan, char* kernel_name, size_t len);
 extern "C" int lbm_plan64_rows_multi_any_run_launches(const lbm_internal::PlanRowsMultiAny64* plan, int n_steps, int* steps, int* full, int cap);
+// And for a column-partitioned run: the PlanCols64 rank `rank` of `nranks` would get (0, or 1 where lbm_cols64_create refuses the
+// arguments before its first HIP call, the message in lbm_last_error()), its kernel's name, and the launches of a run on one rank.
+extern "C" int lbm_plan64_cols_sizeof(void);
+extern "C" int lbm_plan64_cols(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanCols64* out);
+extern "C" int lbm_plan64_cols_kernel_name(const lbm_internal::PlanCols64* plan, char* kernel_name, size_t len);
+extern "C" int lbm_plan64_cols_run_launches(const lbm_internal::PlanCols64* plan, int n_steps, int* steps, int* full, int cap);

@@ -25,6 +25,7 @@
 
 #include "lbm_d2q9.h"
 #include "lbm_d2q9_f64_rows.h"
+#include "lbm_d2q9_f64_cols.h"
 #include "lbm_geometry.h"
 #include "lbm_internal.h"
 #include "lbm_knobs.h"
@@ -762,6 +763,72 @@ int plan64_rows_multi_any_next_steps(const PlanRowsMultiAny64& a, int left)
   return std::min(a.K, left);
 }
 
+// One rank of a column-partitioned double-precision run (lbm_cols64_create).  Columns by lbm_decompose_columns (whole x-pairs, the
+// spare pairs to the first ranks); K is plan64_multi's knob and default; G = 2 ceil(K / 2) ghost columns on each side, so that a launch
+// of k <= K steps finds the k columns it consumes and the pitch nxl + 2 G stays even.  A run is taken if and only if nx is even, every
+// rank has at least TX columns and ny >= TY (a shifted tile lies inside the block; the wrap in y needs one correction): there is no
+// one-step column kernel to fall back on and no size threshold, so everything else is refused, and the message names the row
+// partition, which takes every shape.  nxl >= TX = 32 > 2 G: the columns a rank pushes (its first and last G owned ones) and the ghost
+// columns it receives are disjoint even where it is its own neighbour.  The store rule is plan64_whole's on the RANK's two grids.
+static_assert(kMulti64TX > 2 * 2 * ((kMulti64MaxK + 1) / 2), "a rank's pushed columns and ghost columns are disjoint");
+static_assert(LBM_COLS64_MAX_RANKS == kMaxCols64Ranks, "lbm_internal.h restates the header's limit");
+int plan64_cols(const Knobs& knobs, const lbm64_params* p, int nranks, int rank, unsigned flags, PlanCols64* out)
+{
+  static const char* const kRows = " (the row partition, lbm_rows64_create, takes every shape)";
+  if (!p || !out) { set_error("lbm_cols64: null argument"); return 1; }
+  if ((flags & ~kFlagsCols64) != 0u) { set_error("lbm_cols64: a column partition takes LBM_FLAG_NT_STORES or LBM_FLAG_NO_NT_STORES only"); return 1; }
+  if (nranks < 1 || nranks > kMaxCols64Ranks) { set_error("lbm_cols64: nranks must be 1..64"); return 1; }
+  if (rank < 0 || rank >= nranks) { set_error("lbm_cols64: rank outside 0..nranks-1"); return 1; }
+  if (p->nx < 1 || p->nx % kPairCells != 0) { set_error(std::string("lbm_cols64: nx must be even: column blocks are made of whole x-pairs") + kRows); return 1; }
+  if (p->ny < kMulti64TY) { set_error("lbm_cols64: ny = " + std::to_string(p->ny) + " is fewer than " + std::to_string(kMulti64TY) + " rows, the height of a tile" + kRows); return 1; }
+  if (p->nx / kPairCells < nranks) { set_error("lbm_cols64: nx = " + std::to_string(p->nx) + " on " + std::to_string(nranks) + " ranks leaves a rank without an x-pair" + kRows); return 1; }
+  int nxl[kMaxCols64Ranks], dis[kMaxCols64Ranks];
+  if (lbm_decompose_columns(p->nx, nranks, nxl, dis)) return 1;
+  for (int r = 0; r < nranks; ++r)
+    if (nxl[r] < kMulti64TX) {
+      set_error("lbm_cols64: nx = " + std::to_string(p->nx) + " on " + std::to_string(nranks) + " ranks leaves rank " + std::to_string(r) + " " + std::to_string(nxl[r]) +
+                " columns, fewer than " + std::to_string(kMulti64TX) + ", the width of a tile" + kRows);
+      return 1;
+    }
+  PlanCols64 c{};
+  c.flags = flags;
+  c.nranks = nranks; c.rank = rank;
+  c.x0 = dis[rank]; c.nxl = nxl[rank];
+  c.K = multi64_k_ok(knobs.multi64_k) ? knobs.multi64_k : kMulti64DefaultK;     // a malformed or unbuilt value: the default
+  c.ghost = 2 * ((c.K + 1) / 2);
+  c.pitch = c.nxl + 2 * c.ghost;
+  for (int r = 0; r < nranks; ++r)
+    if (static_cast<long long>(nxl[r] + 2 * c.ghost) * p->ny > (1LL << 31) - 4096) { set_error("lbm_cols64: a rank's storage is too large for 32-bit cell indices"); return 1; }
+  c.tiles_x = (c.nxl + kMulti64TX - 1) / kMulti64TX;
+  c.n_tiles = c.tiles_x * ((p->ny + kMulti64TY - 1) / kMulti64TY);
+  c.edge = c.nxl % kMulti64TX != 0 || p->ny % kMulti64TY != 0;
+  const size_t storage = static_cast<size_t>(c.pitch) * p->ny;
+  c.nt_stores = 2 * 9 * storage * sizeof(double) > (192u << 20);                // plan64_whole's rule
+  if (flags & LBM_FLAG_NT_STORES) c.nt_stores = 1;
+  if (flags & LBM_FLAG_NO_NT_STORES) c.nt_stores = 0;
+  c.block = kMulti64Lanes;
+  c.lds_bytes = multi64_lds_bytes(c.K);
+  c.mask_words = static_cast<int>((storage + 31) / 32 + 4);
+  c.partials_cap = c.K * c.n_tiles + 1;
+  c.ps = static_cast<long long>(plane_stride_floats(storage, knobs.skew));      // always even (the pair form's aligned 16-byte accesses)
+  c.grid_doubles = 9 * c.ps + 128;
+  *out = c;
+  return 0;
+}
+
+void plan64_cols_kernel_name(const PlanCols64& c, char* kernel_name, size_t len)
+{
+  const char* form = c.edge ? (c.nt_stores ? "lbm_cols_multi_kernel_f64<%d,nt,edge>" : "lbm_cols_multi_kernel_f64<%d,edge>")
+                            : (c.nt_stores ? "lbm_cols_multi_kernel_f64<%d,nt>" : "lbm_cols_multi_kernel_f64<%d>");
+  std::snprintf(kernel_name, len, form, c.K);
+}
+
+// plan64_multi_next_steps' rule: floor(n / K) launches of K steps and at most one shorter launch, the last.
+int plan64_cols_next_steps(const PlanCols64& c, int left)
+{
+  return std::min(c.K, left);
+}
+
 // ---- what a run launches ------------------------------------------------------------------------------------------------------
 
 // Steps of the next launch of lbm_multi_kernel when `left` steps remain: multi_K, except that a count multi_K does not
@@ -1235,6 +1302,29 @@ int lbm_plan64_rows_multi_any_run_launches(const lbm_internal::PlanRowsMultiAny6
   int n = 0;
   for (int left = n_steps; left > 0; ++n) {
     const int k = lbm_internal::plan64_rows_multi_any_next_steps(*plan, left);
+    if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
+    left -= k;
+  }
+  return n;
+}
+
+int lbm_plan64_cols_sizeof(void) { return static_cast<int>(sizeof(lbm_internal::PlanCols64)); }
+int lbm_plan64_cols(const lbm64_params* p, int nranks, int rank, unsigned flags, lbm_internal::PlanCols64* out)
+{
+  return lbm_internal::plan64_cols(knobs_from_env(), p, nranks, rank, flags, out);
+}
+int lbm_plan64_cols_kernel_name(const lbm_internal::PlanCols64* plan, char* kernel_name, size_t len)
+{
+  if (!plan || !kernel_name || !len) { set_error("lbm_plan64_cols_kernel_name: null argument"); return 1; }
+  lbm_internal::plan64_cols_kernel_name(*plan, kernel_name, len);
+  return 0;
+}
+int lbm_plan64_cols_run_launches(const lbm_internal::PlanCols64* plan, int n_steps, int* steps, int* full, int cap)
+{
+  if (!plan || !multi64_k_ok(plan->K) || n_steps < 0 || cap < 0 || (cap > 0 && (!steps || !full))) { set_error("lbm_plan64_cols_run_launches: bad argument"); return -1; }
+  int n = 0;
+  for (int left = n_steps; left > 0; ++n) {
+    const int k = lbm_internal::plan64_cols_next_steps(*plan, left);
     if (n < cap) { steps[n] = k; full[n] = k == plan->K; }
     left -= k;
   }

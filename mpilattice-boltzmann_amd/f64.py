@@ -19,6 +19,10 @@ with `flags=f64.FLAG_MULTI_STEPS` on a large one, several per launch of lbm_mult
 (lbm_rows_multi_kernel_f64): the same populations.  `flags=f64.FLAG_ROWS_MULTI_ANY_SIZE` means the same and also takes the runs
 of any even width >= 32 whose every rank owns >= 16 rows, uneven ranks among them, by the kernel's edge-tile form.
 
+`f64.Cols64(p, obst, nranks, devices=None)` is the same grid as `nranks` COLUMN blocks (include/lbm_d2q9_f64_cols.h), for grids much
+wider than tall: Rows64's methods, the same populations, K steps per launch and exchange (lbm_cols_multi_kernel_f64).  It takes even
+nx, blocks of at least 32 columns and ny >= 16, and refuses everything else.
+
 `g.digest()` of either class gives one 64-bit digest per row of the current state and their sum (include/lbm_d2q9_f64_digest.h), taken
 on the device; `f64.digest_host(cells, nx)` the same of an array, `f64.differing_rows(a, b)` the rows in which two objects differ.
 """
@@ -406,5 +410,127 @@ def differing_rows(a, b) -> list[int]:
     return [int(y) for y in np.nonzero(a.digest()[0] != b.digest()[0])[0]]
 
 
+# ---- column-partitioned runs (include/lbm_d2q9_f64_cols.h): a signature table of their own, beside the others, which stay as they are ----
+COLS_ABI_VERSION = 1
+_COLS_SIGNATURES = {
+    "lbm_cols64_abi_version": (C.c_int, []),
+    "lbm_cols64_create": (C.c_int, [_P(_ctx), _P(CParams64), C.c_int, _P(C.c_int), C.c_int, _P(C.c_int), C.c_uint]),
+    "lbm_cols64_destroy": (C.c_int, [_ctx]),
+    "lbm_cols64_run": (C.c_int, [_ctx, C.c_int, _P(C.c_double)]),
+    "lbm_cols64_get_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_cols64_set_cells": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_cols64_get_observables": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_cols64_av_velocity_sum": (C.c_int, [_ctx, _P(C.c_double)]),
+    "lbm_cols64_last_run_ms": (C.c_int, [_ctx, _P(C.c_double), _P(C.c_int)]),
+    "lbm_cols64_describe": (C.c_int, [_ctx, C.c_char_p, C.c_size_t, _P(C.c_int), _P(C.c_longlong), _P(C.c_longlong), _P(C.c_longlong)]),
+    "lbm_cols64_digest": (C.c_int, [_ctx, C.c_int, C.c_int, _P(_ull), _P(_ull)]),
+}
+COLS_EXPORTS = tuple(_COLS_SIGNATURES)
+
+_cols_typed = None
+
+
+def load_cols_library() -> C.CDLL:
+    """liblbm_d2q9.so with the lbm64_* and the lbm_cols64_* prototypes set.  Raises if the library or one of the symbols is absent."""
+    global _cols_typed
+    if _cols_typed is None:
+        lib = load_library()
+        for name, (res, args) in _COLS_SIGNATURES.items():
+            fn = getattr(lib, name)           # AttributeError if the symbol is not exported
+            fn.restype, fn.argtypes = res, args
+        if lib.lbm_cols64_abi_version() != COLS_ABI_VERSION:
+            raise RuntimeError(f"liblbm_d2q9.so column-partition ABI {lib.lbm_cols64_abi_version()} != binding {COLS_ABI_VERSION}: rebuild")
+        _cols_typed = lib
+    return _cols_typed
+
+
+class Cols64(Rows64):
+    """A whole periodic grid in double precision, its columns dealt to `nranks` column blocks on one or several GPUs — one
+    `lbm_cols64` (include/lbm_d2q9_f64_cols.h): K steps per launch and exchange (lbm_cols_multi_kernel_f64), for grids much wider than
+    tall.  Rows64's arguments and methods; the populations are Grid64's bits for every rank count.  `flags`: 0 or a store form.  Taken:
+    even nx, every block at least 32 columns wide, ny >= 16; everything else raises LbmError (Rows64 takes every shape)."""
+
+    def __init__(self, params, obstacles: np.ndarray, nranks: int, devices=None, flags: int = 0):
+        self._lib = load_cols_library()
+        self.params = params
+        self.nranks = int(nranks)
+        self.obstacles = np.ascontiguousarray(obstacles, dtype=np.int32)
+        if self.obstacles.shape != (params.ny, params.nx):
+            raise ValueError("obstacles must be (ny, nx)")
+        self.free_cells = int(self.obstacles.size - np.count_nonzero(self.obstacles))
+        self._cp = _cparams(params)
+        self._run = _ctx()
+        dev = None
+        if devices is not None:
+            devices = [int(d) for d in devices]
+            if len(devices) != self.nranks:
+                raise ValueError("devices must name one device per rank")
+            dev = (C.c_int * max(len(devices), 1))(*devices)
+        check(self._lib.lbm_cols64_create(C.byref(self._run), C.byref(self._cp), self.free_cells, _capi.as_int_ptr(self.obstacles), self.nranks, dev, flags))
+
+    def close(self) -> None:
+        if getattr(self, "_run", None):
+            self._lib.lbm_cols64_destroy(self._run)
+            self._run = None
+
+    def __enter__(self) -> "Cols64":
+        return self
+
+    def run(self, n_steps: Optional[int] = None) -> np.ndarray:
+        """n_steps iterations (default max_iters) on every rank; returns av_vels, float64 (n_steps,)."""
+        n = self.params.max_iters if n_steps is None else int(n_steps)
+        av = np.zeros(max(n, 1), dtype=np.float64)
+        check(self._lib.lbm_cols64_run(self._run, n, _capi.as_double_ptr(av)))
+        return av[:n]
+
+    def get_cells(self) -> np.ndarray:
+        """(ny, nx, 9) float64 of the whole grid, the reference's AoS layout."""
+        cells = np.empty((self.params.ny, self.params.nx, 9), dtype=np.float64)
+        check(self._lib.lbm_cols64_get_cells(self._run, _capi.as_double_ptr(cells)))
+        return cells
+
+    def set_cells(self, cells: np.ndarray) -> None:
+        cells = np.ascontiguousarray(cells, dtype=np.float64)
+        if cells.size != self.params.ny * self.params.nx * 9:
+            raise ValueError("cells must hold ny * nx * 9 doubles")
+        check(self._lib.lbm_cols64_set_cells(self._run, _capi.as_double_ptr(cells)))
+
+    def get_observables(self) -> np.ndarray:
+        """(ny, nx, 4) float64 = {u_x, u_y, u, pressure} per cell, the fluid-cell formula for every cell."""
+        obs = np.empty((self.params.ny, self.params.nx, 4), dtype=np.float64)
+        check(self._lib.lbm_cols64_get_observables(self._run, _capi.as_double_ptr(obs)))
+        return obs
+
+    def av_velocity_sum(self) -> float:
+        """av_velocity()'s sum over the free cells, summed on the devices, the blocks' sums added rank after rank."""
+        tot = C.c_double(0.0)
+        check(self._lib.lbm_cols64_av_velocity_sum(self._run, C.byref(tot)))
+        return tot.value
+
+    # Inherited from Rows64 as they are, because they touch the run only through methods overridden here or not at all: reynolds and
+    # write_values (get_observables and the host half of the library), __exit__ and __del__ (close).  Every method that calls an
+    # lbm_rows64_* entry point is overridden: a Cols64 never reaches one.
+
+    def last_run_ms(self) -> tuple[float, int]:
+        """(device ms of the last run: the largest span over the ranks from its first launch to its last push, launches:
+        ceil(n_steps / K) * nranks)."""
+        ms, n = C.c_double(0.0), C.c_int(0)
+        check(self._lib.lbm_cols64_last_run_ms(self._run, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def digest(self, y_begin: Optional[int] = None, y_end: Optional[int] = None) -> tuple[np.ndarray, int]:
+        """Grid64.digest's pair for the whole grid's rows [y_begin, y_end): each rank digests its columns of them on its device, the
+        host adds the ranks' parts."""
+        load_cols_library()
+        return _device_digest(self._lib.lbm_cols64_digest, self._run, self.params.ny, y_begin, y_end)
+
+    def describe(self) -> dict:
+        name = C.create_string_buffer(256)
+        nranks, blocks, per_block, nbytes = C.c_int(0), C.c_longlong(0), C.c_longlong(0), C.c_longlong(0)
+        check(self._lib.lbm_cols64_describe(self._run, name, 256, C.byref(nranks), C.byref(blocks), C.byref(per_block), C.byref(nbytes)))
+        return {"kernel": name.value.decode(), "nranks": nranks.value, "blocks": blocks.value, "cells_per_block": per_block.value, "state_bytes": nbytes.value}
+
+
 __all__ = ["ABI_VERSION", "EXPORTS", "ROWS_ABI_VERSION", "ROWS_EXPORTS", "DIGEST_ABI_VERSION", "DIGEST_EXPORTS", "digest_host", "differing_rows", "load_digest_library", "FLAG_NT_STORES", "FLAG_NO_NT_STORES", "FLAG_TILE_STEPS", "FLAG_MULTI_STEPS", "FLAG_MULTI_ANY_SIZE", "FLAG_ROWS_MULTI_STEPS", "FLAG_ROWS_MULTI_ANY_SIZE", "CParams64", "Grid64", "Rows64",
-           "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64"]
+           "LbmError", "load_library", "load_rows_library", "read_params64", "write_av_vels64", "write_final_state_obs64",
+           "COLS_ABI_VERSION", "COLS_EXPORTS", "Cols64", "load_cols_library"]

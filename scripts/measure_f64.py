@@ -68,7 +68,16 @@ overhead, not a speed-up; --out appends.
     timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 4096x4096 --out $F &&
     timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 2048x2048 --steps 400 --out $F &&
     timeout -k 10 200 python scripts/measure_f64.py --ranks 1,2,8 --work 1024x1024 --steps 2000 --out $F &&
-    timeout -k 10 200 python scripts/measure_f64.py --ranks 1 --work 8192x1024 --out $F"""
+    timeout -k 10 200 python scripts/measure_f64.py --ranks 1 --work 8192x1024 --out $F
+
+--cols N [--devices LIST] [--steps S] --work NXxNY: column-partitioned runs (f64.Cols64, include/lbm_d2q9_f64_cols.h) on N ranks beside
+f64.Rows64 with LBM_ROWS64_FLAG_MULTI_ANY_SIZE on the same grid and rank count, and beside one column rank's share of the grid run
+alone, alternating: device and wall time per step.  One grid per process; --out appends.
+
+    F=profiles/r23/f64_cols.txt; rm -f $F
+    for w in 65536x128 32768x256 16384x512 32768x64 8192x8192; do
+      timeout -k 10 240 python scripts/measure_f64.py --cols 8 --devices 0 --work $w --steps 40 --out $F || break
+    done"""
 import argparse
 import ctypes as C
 import os
@@ -468,6 +477,51 @@ def measure_rows(name, ranks, devices, steps, reps, lines, baseline_lib=None):
     print("\n".join(lines[n0:]), flush=True)
 
 
+def measure_cols(name, nranks, devices, steps, reps, lines):
+    """Column-partitioned runs (f64.Cols64, include/lbm_d2q9_f64_cols.h) beside the row-partitioned run of the same grid and rank count
+    under LBM_ROWS64_FLAG_MULTI_ANY_SIZE (whatever kernel that takes: on thin ranks the one-step one), and beside ONE column rank's
+    share of the grid run alone as a periodic grid of its own (nx / nranks x ny on one column rank): device time (the largest span over
+    the ranks) and the host's wall time per step, the runs alternating.  With all ranks on one device their kernels serialise: this
+    compares the two partitions' work and exchange volume on one GPU, not a speed-up over several."""
+    import time
+    p, obst = deck(name)
+    n0 = len(lines)
+    os.environ["LBM_TUNE_MULTI64_MIN"] = "0"              # read when a run is made: the rows' multi-step kernel on every size it can tile
+    dev = None if devices is None else [devices[r % len(devices)] for r in range(nranks)]
+    runs = {f"{nranks} column ranks": f64.Cols64(p, obst, nranks, devices=dev),
+            f"{nranks} row ranks, any-size": f64.Rows64(p, obst, nranks, devices=dev, flags=f64.FLAG_ROWS_MULTI_ANY_SIZE)}
+    share_nx = p.nx // nranks
+    if nranks > 1 and share_nx % 2 == 0 and share_nx >= 32:
+        ps, os_ = deck(f"{share_nx}x{p.ny}")
+        runs["1 column rank's share alone"] = f64.Cols64(ps, os_, 1, devices=None if dev is None else dev[:1])
+    shapes = {k: q.describe() for k, q in runs.items()}
+    first = {k: q.run(steps) for k, q in runs.items()}     # the warm-up run: every run from the rest state
+    ck, rk = list(runs)[:2]
+    if not np.allclose(first[ck], first[rk], rtol=1e-12, atol=0.0):     # the same run: av_vels agree to the order of their additions
+        raise SystemExit(f"{name}: av_vels of the column and the row run differ by {np.max(np.abs(first[ck] - first[rk]) / first[rk]):.3e}")
+    dev_us, wall_us = {k: [] for k in runs}, {k: [] for k in runs}
+    for _ in range(reps):
+        for k, q in runs.items():                          # alternate: all see the same drift of the card
+            t0 = time.perf_counter()
+            q.run(steps)
+            wall_us[k].append(1e6 * (time.perf_counter() - t0) / steps)
+            dev_us[k].append(1e3 * q.last_run_ms()[0] / steps)
+    for q in runs.values():
+        q.close()
+    where = "the library's default (rank r on device r % device count)" if devices is None else f"devices {devices}, cycled"
+    lines.append(f"{name}  {steps} steps per run, {reps} runs each, alternating; ranks on {where}; us per step")
+    for k in runs:
+        d, w = dev_us[k], wall_us[k]
+        lines.append(f"  {k:32s} {shapes[k]['kernel']:40s} {shapes[k]['blocks']:6d} blocks  {shapes[k]['state_bytes'] / 2 ** 20:9.1f} MiB   device median {statistics.median(d):9.3f}  min {min(d):9.3f}"
+                     f"  max {max(d):9.3f}   wall median {statistics.median(w):9.3f}  min {min(w):9.3f}  max {max(w):9.3f}")
+    med = {k: statistics.median(dev_us[k]) for k in (ck, rk)}
+    gain = med[rk] - med[ck]
+    spreads = (max(dev_us[rk]) - min(dev_us[rk])) + (max(dev_us[ck]) - min(dev_us[ck]))
+    verdict = "columns win" if gain > spreads else "rows win" if -gain > spreads else "level"
+    lines.append(f"  rows / columns: {med[rk] / med[ck]:.3f} x; median difference {gain:.3f} us against the two max - min spreads together {spreads:.3f} us -> {verdict}")
+    print("\n".join(lines[n0:]), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true", help="small step counts (a functional check of this script)")
@@ -481,8 +535,22 @@ def main():
     ap.add_argument("--ranks", metavar="N[,N]", help="row-partitioned runs (f64.Rows64) with these rank counts beside the one-context runs; --work: NXxNY (default 8192x8192)")
     ap.add_argument("--devices", metavar="LIST", help="with --ranks: HIP ordinals, rank r on LIST[r %% len(LIST)] (default: the library's, r %% device count)")
     ap.add_argument("--steps", type=int, help="with --ranks: steps per run (default 200)")
+    ap.add_argument("--cols", type=int, metavar="N", help="column-partitioned runs (f64.Cols64) on N ranks beside Rows64 with LBM_ROWS64_FLAG_MULTI_ANY_SIZE; --work: NXxNY; --devices, --steps as for --ranks")
     a = ap.parse_args()
     lbm.build()
+    if a.cols:
+        if not a.work:
+            ap.error("--cols needs --work NXxNY")
+        lines = [] if a.out and os.path.exists(a.out) else [
+            "# scripts/measure_f64.py --cols: column-partitioned double-precision runs (lbm_cols_multi_kernel_f64 + lbm64_push_ghost_cols_kernel per rank-launch) beside the "
+            "row-partitioned run of the same grid and rank count under LBM_ROWS64_FLAG_MULTI_ANY_SIZE, and one column rank's share alone",
+            "# device: events around a run's launches, over its steps, the largest span over the ranks; wall: the host's clock around run()"]
+        measure_cols(a.work, a.cols, [int(v) for v in a.devices.split(",")] if a.devices else None, a.steps or (12 if a.quick else 200), 3 if a.quick else 5, lines)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "a") as fh:
+                fh.write("\n".join(lines) + "\n")
+        return 0
     if a.ranks:
         lines = [] if a.out and os.path.exists(a.out) else [
             "# scripts/measure_f64.py --ranks: row-partitioned double-precision runs (lbm_rows_kernel_f64 + lbm64_push_rows_kernel per rank-step; \"multi-step\": "
